@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py — Mrays/s of the path-tracing hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config C] [--scaling strong|weak]
+    python bench.py --gpus N --steps K --warmup W [--config C] [--scaling strong|weak] [--dump-outputs DIR]
 
 Workload (default) = BASELINE.json configs[1]: 1920x1080, 8 spp, 8 bounces, 16 analytic spheres +
 checkered ground quad, sky on (ray_tracing_amd.scenes.config2).  `--config 5` is the north_star's
@@ -40,6 +40,11 @@ counts).  This GPU's clocks do ramp for 20-30 ms after idling (profi
 +-5 %: the line therefore ALSO carries `regions` — R (default 7) further back-to-back regions of the same progressive render, each at
 least K steps and at least 50 ms long, each bracketed like the timed one — and `value_median_of_regions`, the figure A/B comparisons
 quote.  The number of steps per region is derived from an all-reduced time, so every rank renders the same frames.
+
+`--dump-outputs DIR` writes what the K timed steps computed — AccumulatedRender after Frame W + K and the FrameRender of that last step,
+the arrays a caller of rt_render_frame reads back (gathered over the ranks when N > 1) — as DIR/accumulated.npy and DIR/frame.npy, float32,
+at most 64 MB in all: larger images are reduced to a fixed, seeded sample of their pixels (DIR/sample_pixel_index.npy); `dump_outputs`
+in the line says which.  The scene, renderSeed and frame indices are fixed, so two builds given the same arguments can be compared file by file.
 
 Prints ONE JSON line on rank 0.
 """
@@ -90,6 +95,36 @@ def spawn_ranks(args):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     return subprocess.call(cmd, env=env)
+
+
+def dump_outputs(outdir, images, budget=64_000_000, seed=1):
+    """--dump-outputs: the images (name -> float32 [H, W, 4]) as outdir/<name>.npy, whole when they fit `budget` bytes together;
+    otherwise the same fixed, seeded sample of pixels from each ([n, 4], ascending row-major pixel index) and those indices as
+    outdir/sample_pixel_index.npy (float64).  Same arguments, same files: two builds can be compared output for output."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    h, w = next(iter(images.values())).shape[:2]
+    header = 128                                   # bytes of one .npy header
+    info = {"dir": os.path.abspath(outdir), "resolution": [w, h], "files": {}}
+    if sum(a.nbytes + header for a in images.values()) <= budget:
+        info["sampled_pixels"] = None
+        if os.path.exists(os.path.join(outdir, "sample_pixel_index.npy")):   # left by an earlier, sampled dump into the same DIR
+            os.remove(os.path.join(outdir, "sample_pixel_index.npy"))
+        for name, a in images.items():
+            np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+            info["files"][name + ".npy"] = list(a.shape)
+        return info
+    per_pixel = sum(4 * a.shape[2] for a in images.values()) + 8
+    n = min(h * w, (budget - header * (len(images) + 1)) // per_pixel)
+    idx = np.sort(np.random.default_rng(seed).choice(h * w, size=n, replace=False))
+    info["sampled_pixels"] = {"n": int(n), "of": h * w, "seed": seed}
+    np.save(os.path.join(outdir, "sample_pixel_index.npy"), idx.astype(np.float64))
+    info["files"]["sample_pixel_index.npy"] = [int(n)]
+    for name, a in images.items():
+        s = np.ascontiguousarray(a, dtype=np.float32).reshape(h * w, a.shape[2])[idx]
+        np.save(os.path.join(outdir, name + ".npy"), s)
+        info["files"][name + ".npy"] = list(s.shape)
+    return info
 
 
 def pin_to_gpu_numa_node(torch, dev_index):
@@ -457,6 +492,9 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="strong")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--frames-per-launch", type=int, default=16, help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the K timed steps, write what they computed (AccumulatedRender, and FrameRender of the last step) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed, seeded pixel sample when the whole images are larger)")
     args = ap.parse_args()
 
     if args.pmc_child:
@@ -474,6 +512,11 @@ def main():
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (torch.cuda.is_available() is False); there is no CPU fallback")
+    # one process per GPU: every rank of this node refuses before it selects a device or starts a collective when the node has too few
+    # (otherwise the rank without a GPU fails in set_device while its peers wait for it in the process group's set-up)
+    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", str(world)))
+    if not os.environ.get("RT_BENCH_ONE_DEVICE") and torch.cuda.device_count() < local_world:
+        raise SystemExit(f"bench.py: {local_world} ranks on this node need {local_world} GPUs, {torch.cuda.device_count()} visible")
     # Test hooks (single-GPU boxes): RT_BENCH_ONE_DEVICE=1 puts every rank on GPU 0 and
     # RT_BENCH_BACKEND=gloo replaces RCCL, so the N>1 code path can be exercised without N GPUs.
     dev_index = 0 if os.environ.get("RT_BENCH_ONE_DEVICE") else local_rank
@@ -572,6 +615,21 @@ def main():
     timed = tracer.counters()
     elapsed = t1 - t0
     segments = timed["segments"]
+
+    # ---- what the K timed steps computed, as a caller of rt_render_frame receives it (outside the timed region; collectives on every rank)
+    dumped = None
+    if args.dump_outputs:
+        if tiled:
+            acc_img = tiled.gather_accumulated(H, comm_device=comm_device)
+            frame_t = tiled.frame_t if comm_device == device else tiled.frame_t.to(comm_device)
+            frame_img = pkg.dist.gather_image(frame_t, rank, world, H, always_collective=True)
+            images = {"accumulated": acc_img.cpu().numpy(), "frame": frame_img.cpu().numpy()} if rank == 0 else None
+        else:
+            images = {"accumulated": tracer.read_accumulated(), "frame": tracer.read_frame()}
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, images)
+            dumped["frames_accumulated"] = accumulated[0]
+        del images
 
     # ---- R further regions of the same progressive render (>= K steps and >= --region-ms each): the median is what a 1 % change shows up in
     # (a single 13 ms region scatters by +-5 % with the device's clock ramp).  Steps per region from an ALL-REDUCED time: identical on every rank.
@@ -832,6 +890,7 @@ def main():
             "scene_load": scene_load,
             "parity": parity if parity is not None else "checked at N=1 (pytest -m gpu and the N=1 bench line)",
             "roofline": roof,
+            "dump_outputs": dumped,
         }
         if regions:
             vals = [sg / el / 1e6 for sg, el in zip(regions["segments"], regions["elapsed_s"])]

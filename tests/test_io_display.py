@@ -60,9 +60,9 @@ def test_obj_loader(pkg, tmp_path):
     assert pkg.meshes.check_winding(mu) == 1.0 and np.allclose(mu.vertices[:, 0], -m.vertices[:, 0])
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/Assets/Graphics/cube_rounded2.obj"), reason="reference asset not present")
 def test_reference_rounded_cube_obj_loads(pkg, api):
-    m = pkg.sceneio.load_obj("/root/reference/Assets/Graphics/cube_rounded2.obj")
+    # the reference's Assets/Graphics/cube_rounded2.obj, kept as a fixture
+    m = pkg.sceneio.load_obj(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cube_rounded2.obj"))
     assert m.triangle_count == 1724           # 858 quads + 8 triangles
     assert pkg.meshes.check_winding(m) == 1.0
     nodes, tris, stats = api.build_bvh_arrays(m.vertices, m.normals, m.triangles)
