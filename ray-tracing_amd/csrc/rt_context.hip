@@ -40,9 +40,26 @@
 #define RT_FUSE_TARGET_MS 20.0
 #define RT_FUSE_SLAB_BYTES ((size_t)1536 << 20) /* a staging slab: 16 bytes per pixel and frame; 1920x1080: 45 frames, 3840x2160: 16 (2.1 GB), an eighth of 1080p: 64 */
 #include "rt_layout.h"
+#include "rt_launch_order.h"
 #define RT_VERSION_STRING "raytrace_hip gfx950 abi=1"
 
 static thread_local char g_err[512] = "";
+
+struct RtContext;
+struct LaunchJob;
+/* The runtime of rt_launch_order.h: its nine events on the context's two render streams, and the kernels a launch's steps enqueue
+ * (defined with the launch path, below launch_frames' helpers). */
+struct HipOrder final : rt_order::Backend {
+    RtContext* ctx = nullptr;
+    hipEvent_t ev[rt_order::EVENT_COUNT] = {};
+    LaunchJob* job = nullptr; /* the launch LaunchOrder::run is issuing */
+    hipStream_t stream(int s) const;
+    int record(rt_order::Event e, int s) override;
+    int wait(int s, rt_order::Event e) override;
+    int sort(int s, int target) override;
+    int trace(int s, int part, int parts) override;
+    int accumulate(int s) override;
+};
 
 struct RtContext {
     int device = 0;
@@ -113,12 +130,7 @@ struct RtContext {
      * flight keep the order they were launched with), so it does not have to join the streams */
     uint32_t* dTileOrder[2] = {nullptr, nullptr};
     uint32_t* dTileKey = nullptr;   /* the sort's snapshot of the costs (kernels in flight keep raising them) */
-    int orderCur = 0;
     int orderTiles = 0;             /* tiles the two arrays are sized for; 0 = none */
-    bool orderValid = false;
-    long long framesSinceResize = 0;
-    long long nextSortAt = 1;
-    bool lptEnabled = true;
     int numCUs = 256;
     int occPerCU[16] = {0};
     size_t occBytes[16] = {0};
@@ -163,32 +175,10 @@ struct RtContext {
     float* dStaging[2] = {nullptr, nullptr};
     size_t stagingBytes[2] = {0, 0};
     bool stagingUnavailable = false; /* the slab could not be allocated at this image size: fused launches go out frame by frame (cleared by rt_resize) */
-    int stagedNext = 0;              /* stream / slab of the next fused launch */
-    bool fusedBehindFirstPart = true; /* RT_FUSED_BEHIND_FIRST_PART=0: plain alternation also after a two-part frame (A/B switch) */
-    bool alternate = true;           /* fused launches alternate between the two streams; off while the second slab does not fit (until the next rt_resize) */
     bool alternateWanted = true;     /* RT_ALTERNATE=0: every fused launch on the main stream (round-3 behaviour) */
-    /* ---- everything the context's two render streams wait for ACROSS each other, in one place (the rules: LaunchOrder's functions below)
-     * s = 0 the main stream, 1 the side stream */
-    struct Order {
-        hipEvent_t evFork = nullptr, evJoin = nullptr;
-        bool sideDirty = false; /* the side stream holds work the main stream has not been ordered after */
-        bool needFork = true;   /* the main stream holds non-render work the side stream must follow */
-        hipEvent_t evSort = nullptr;    /* after the last sort of the tile order; sortPending[s]: stream s has not been ordered after it yet */
-        bool sortPending[2] = {false, false};
-        hipEvent_t evOrderRetire[2] = {nullptr, nullptr}; /* per order buffer: recorded on the OTHER stream when the buffer went out of use; its next rewrite waits for it */
-        bool retireValid[2] = {false, false};
-        /* the accumulation buffer is added to in launch order whichever stream a launch runs on: evAccWriter[s] marks the last kernel on
-         * stream s that writes it; accWriterPending[s] = the other stream has not been ordered after it yet; accWriterFull[s] = that kernel
-         * touches every pixel (an accumulate kernel, a one-part frame; false = one half of a two-part frame) */
-        hipEvent_t evAccWriter[2] = {nullptr, nullptr};
-        bool accWriterPending[2] = {false, false};
-        bool accWriterFull[2] = {false, false};
-        /* the last WHOLE-IMAGE writer of a stream is tracked on its own: a half kernel launched behind it on the same stream re-records
-         * evAccWriter[s] with full = false, and the other stream's half of that very frame would then no longer wait for the whole-image
-         * writer (rt_render_frames(17): 16 fused frames + 1 two-part frame; found by tools/soak.py, round 4) */
-        hipEvent_t evAccFull[2] = {nullptr, nullptr};
-        bool accFullPending[2] = {false, false};
-    } ord;
+    /* where launches run and everything the two render streams wait for across each other (rt_launch_order.h) */
+    rt_order::LaunchOrder order;
+    HipOrder backend;
     int lastLaunched = 0;            /* frames the last launch_frames call really enqueued (flush_pending rolls back the rest) */
     void* dDisplay = nullptr;  /* scratch of the display pass, kept between calls (grows on demand) */
     size_t displayBytes = 0;
@@ -220,14 +210,7 @@ static int fail(RtContext* ctx, int status, const char* fmt, ...)
  * use of the stream other than a render launch goes through here. */
 static hipStream_t joined(RtContext* ctx)
 {
-    if (ctx->ord.sideDirty) {
-        hipEventRecord(ctx->ord.evJoin, ctx->sideStream);
-        hipStreamWaitEvent(ctx->stream, ctx->ord.evJoin, 0);
-        ctx->ord.sideDirty = false;
-        ctx->ord.accWriterPending[1] = false; /* whatever the side stream adds to the accumulation buffer now precedes the main stream's next kernel */
-        ctx->ord.accFullPending[1] = false;
-    }
-    ctx->ord.needFork = true;
+    (void)ctx->order.join(ctx->backend);
     return ctx->stream;
 }
 
@@ -325,6 +308,7 @@ int rt_create(int device_id, RtContext** out)
     if (device_id < 0 || device_id >= n) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_create: device %d out of range [0,%d)", device_id, n);
     RtContext* ctx = new RtContext();
     ctx->device = device_id;
+    ctx->backend.ctx = ctx;
     auto init = [&]() -> int {
         HIP_TRY(ctx, hipSetDevice(device_id));
         hipDeviceProp_t prop;
@@ -344,15 +328,7 @@ int rt_create(int device_id, RtContext** out)
         HIP_TRY(ctx, hipStreamSynchronize(ctx->ownStream));
         HIP_TRY(ctx, hipEventCreate(&ctx->evStart));
         HIP_TRY(ctx, hipEventCreate(&ctx->evStop));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evFork, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evJoin, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evAccWriter[0], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evAccWriter[1], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evAccFull[0], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evAccFull[1], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evSort, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evOrderRetire[0], hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ord.evOrderRetire[1], hipEventDisableTiming));
+        for (hipEvent_t& ev : ctx->backend.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
         return RT_OK;
     };
     if (int rc = init()) { /* the message stays readable through rt_last_error(NULL) */
@@ -365,12 +341,12 @@ int rt_create(int device_id, RtContext** out)
     if (const char* g = getenv("RT_POOL_FAULT")) { if (atoi(g)) ctx->poolSpinLimit = 64u | 0x80000000u; }
     if (getenv("RT_VERBOSE")) ctx->verbose = true;
     if (const char* f = getenv("RT_FUSE_FRAMES")) ctx->fuseFrames = atoi(f) != 0;
-    if (const char* l = getenv("RT_LPT")) ctx->lptEnabled = atoi(l) != 0;
-    if (const char* l = getenv("RT_FUSED_BEHIND_FIRST_PART")) ctx->fusedBehindFirstPart = atoi(l) != 0;
+    if (const char* l = getenv("RT_LPT")) ctx->order.lpt = atoi(l) != 0;
     if (const char* t = getenv("RT_TWO_STREAMS")) ctx->twoStreams = atoi(t) != 0;
     if (const char* c = getenv("RT_COALESCE")) ctx->coalesce = atoi(c) != 0;
     if (const char* fg = getenv("RT_FRAME_GROUP")) ctx->frameGroupOverride = atoi(fg);
-    if (const char* al = getenv("RT_ALTERNATE")) ctx->alternate = ctx->alternateWanted = atoi(al) != 0;
+    if (const char* al = getenv("RT_ALTERNATE")) ctx->order.alternate = ctx->alternateWanted = atoi(al) != 0;
+    ctx->order.set_two_streams(ctx->twoStreams && ctx->sideStream);
     if (const char* fc = getenv("RT_FUSE_CAP")) {
         const int v = atoi(fc);
         if (v >= 1) { ctx->fuseCap = v > RT_FUSE_MAX ? RT_FUSE_MAX : v; ctx->fuseCapPinned = true; }
@@ -410,13 +386,9 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dTileOrder[0]);
     hipFree(ctx->dTileOrder[1]);
     hipFree(ctx->dTileKey);
-    if (ctx->ord.evSort) hipEventDestroy(ctx->ord.evSort);
-    for (int i = 0; i < 2; i++) if (ctx->ord.evOrderRetire[i]) hipEventDestroy(ctx->ord.evOrderRetire[i]);
     hipFree(ctx->dDisplay);
     hipFree(ctx->dStaging[0]);
     hipFree(ctx->dStaging[1]);
-    for (int i = 0; i < 2; i++) if (ctx->ord.evAccWriter[i]) hipEventDestroy(ctx->ord.evAccWriter[i]);
-    for (int i = 0; i < 2; i++) if (ctx->ord.evAccFull[i]) hipEventDestroy(ctx->ord.evAccFull[i]);
     hipFree(ctx->dPxCold);
     for (auto& pr : ctx->tuner.probe) {
         if (pr.start) hipEventDestroy(pr.start);
@@ -429,8 +401,7 @@ void rt_destroy(RtContext* ctx)
     for (auto& fp : ctx->fuseProbe) { if (fp.start) hipEventDestroy(fp.start); if (fp.stop) hipEventDestroy(fp.stop); }
     if (ctx->evStart) hipEventDestroy(ctx->evStart);
     if (ctx->evStop) hipEventDestroy(ctx->evStop);
-    if (ctx->ord.evFork) hipEventDestroy(ctx->ord.evFork);
-    if (ctx->ord.evJoin) hipEventDestroy(ctx->ord.evJoin);
+    for (hipEvent_t ev : ctx->backend.ev) if (ev) hipEventDestroy(ev);
     if (ctx->sideStream) hipStreamDestroy(ctx->sideStream);
     if (ctx->ownStream) hipStreamDestroy(ctx->ownStream);
     delete ctx;
@@ -443,6 +414,7 @@ int rt_set_stream(RtContext* ctx, void* hip_stream)
     hipStreamSynchronize(joined(ctx));
     flush_timer(ctx);
     ctx->stream = hip_stream ? (hipStream_t)hip_stream : ctx->ownStream;
+    ctx->order.set_two_streams(ctx->twoStreams && ctx->stream == ctx->ownStream); /* a caller's stream: its order is the contract, one stream */
     return RT_OK;
 }
 
@@ -493,7 +465,7 @@ int rt_resize(RtContext* ctx, int width, int height)
             ctx->stagingBytes[i] = 0;
         }
     ctx->stagingUnavailable = false;
-    ctx->alternate = ctx->alternateWanted; /* (a slab that did not fit the old image may fit this one: ADVICE r4) */
+    ctx->order.alternate = ctx->alternateWanted; /* (a slab that did not fit the old image may fit this one: ADVICE r4) */
     if (!ctx->fuseCapPinned) ctx->fuseCap = RT_FUSE_MIN; /* frame times of the old geometry say nothing */
     for (auto& fp : ctx->fuseProbe) fp.live = false;
     ctx->fuseLast = -1;
@@ -1571,7 +1543,8 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
  * The launch path.  rt_render_frame / rt_render_frames / flush_pending end in launch_frames(ctx, frame0, nFrames):
  *     choose_variant    which kernel instantiation, how much LDS, how many workgroups the chip keeps resident (LaunchPlan)
  *     prepare_*         the buffers a launch needs — pixel records, tile order, staging slab; may synchronise (rarely)
- *     enqueue_*         kernels and events, in the order LaunchOrder's rules demand
+ *     LaunchOrder       place: which stream(s), how many parts, whether the tile order is re-sorted (rt_launch_order.h);
+ *                       run: the sort, trace and accumulate kernels through HipOrder, with the events that order the two streams
  * Dispatch semantics kept: RayComputeManager.cs:84-95 (one RayTrace dispatch per frame, Frame counts the accumulated frames).
  * ===================================================================================================================== */
 struct LaunchPlan {
@@ -1583,105 +1556,6 @@ struct LaunchPlan {
     int wavesPerGroup = 1;       /* waves of a workgroup: each is one persistent wave of the launch */
     long long resident = 0;      /* workgroups the chip keeps resident */
 };
-
-/* ---------------------------------------------------------------------------------------------------------------------
- * LaunchOrder — every wait between the context's two render streams (s = 0 main, 1 side), as named steps.
- *
- *   what                          who writes it                     rule
- *   non-render work (uploads,     the main stream, through           fork_side: before the side stream's next kernel it waits for evFork,
- *    resets, read-backs)           joined()                          recorded on the main stream (needFork); joined() itself makes the main
- *                                                                    stream wait for what the side stream holds (evJoin, sideDirty)
- *   tile order buffer b           rt_order_kernel on stream ss       begin_sort: the rewrite of b waits for b's last readers on the other stream
- *                                                                    (evOrderRetire[b]) and — the sorts share one key snapshot — for the previous
- *                                                                    sort if that ran on the other stream; end_sort records evSort, marks the
- *                                                                    other stream (sortPending) and retires the buffer going out of use;
- *                                                                    before_order_read: a stream's next trace kernel waits for evSort once
- *   accumulation buffer           single-frame trace kernels          before_acc_write(s, whole): wait for the OTHER stream's last whole-image
- *                                  (whole image, or the half of a     writer (evAccFull) and, if this kernel or that stream's last writer covers
- *                                  two-part frame), accumulate        the whole image, for its last writer of any kind (evAccWriter).  Halves of
- *                                  kernels (whole image)              consecutive two-part frames need no wait: between two sorts a stream's half
- *                                                                    is the same set of pixels — end_sort therefore declares both last writers
- *                                                                    "whole".  after_acc_write records the events.
- *   staging slab i, pixel         launches on stream i only          stream order (nothing here)
- *    records i, tile counter i
- * --------------------------------------------------------------------------------------------------------------------- */
-namespace LaunchOrder {
-static inline hipStream_t stream_of(RtContext* ctx, int s) { return s ? ctx->sideStream : ctx->stream; }
-
-static int fork_side(RtContext* ctx)
-{
-    if (!ctx->ord.needFork) return RT_OK;
-    HIP_TRY(ctx, hipEventRecord(ctx->ord.evFork, ctx->stream));
-    HIP_TRY(ctx, hipStreamWaitEvent(ctx->sideStream, ctx->ord.evFork, 0));
-    ctx->ord.needFork = false;
-    return RT_OK;
-}
-static void side_used(RtContext* ctx) { ctx->ord.sideDirty = true; }
-
-static int begin_sort(RtContext* ctx, int ss, int target)
-{
-    RtContext::Order& o = ctx->ord;
-    if (ss == 1) { int rc = fork_side(ctx); if (rc) return rc; }
-    hipStream_t S = stream_of(ctx, ss);
-    if (o.retireValid[target]) HIP_TRY(ctx, hipStreamWaitEvent(S, o.evOrderRetire[target], 0));
-    if (o.sortPending[ss]) HIP_TRY(ctx, hipStreamWaitEvent(S, o.evSort, 0)); /* (two sorts in consecutive launches on alternating streams) */
-    return RT_OK;
-}
-static int end_sort(RtContext* ctx, int ss, bool twoStreams, int retiring /* buffer going out of use, or -1 */)
-{
-    RtContext::Order& o = ctx->ord;
-    HIP_TRY(ctx, hipEventRecord(o.evSort, stream_of(ctx, ss)));
-    o.sortPending[ss] = false;
-    o.sortPending[1 - ss] = twoStreams;
-    if (retiring >= 0 && twoStreams) { /* whatever the other stream holds so far may still read it */
-        HIP_TRY(ctx, hipEventRecord(o.evOrderRetire[retiring], stream_of(ctx, 1 - ss)));
-        o.retireValid[retiring] = true;
-    }
-    if (ss == 1) side_used(ctx);
-    /* a new order moves pixels between the two halves of a two-part frame: the next such frame's halves must come after BOTH
-     * streams' last kernels that add into the accumulation buffer */
-    o.accWriterFull[0] = o.accWriterFull[1] = true;
-    return RT_OK;
-}
-static int before_order_read(RtContext* ctx, int s)
-{
-    if (!ctx->ord.sortPending[s]) return RT_OK;
-    HIP_TRY(ctx, hipStreamWaitEvent(stream_of(ctx, s), ctx->ord.evSort, 0));
-    ctx->ord.sortPending[s] = false;
-    return RT_OK;
-}
-static void forget_order(RtContext* ctx) /* the order buffers were re-made (another image size) */
-{
-    ctx->ord.sortPending[0] = ctx->ord.sortPending[1] = false;
-    ctx->ord.retireValid[0] = ctx->ord.retireValid[1] = false;
-}
-
-static int before_acc_write(RtContext* ctx, int s, bool whole)
-{
-    RtContext::Order& o = ctx->ord;
-    hipStream_t st = stream_of(ctx, s);
-    if (o.accFullPending[1 - s]) { /* once waited for, everything later on this stream follows it */
-        HIP_TRY(ctx, hipStreamWaitEvent(st, o.evAccFull[1 - s], 0));
-        o.accFullPending[1 - s] = false;
-    }
-    if (o.accWriterPending[1 - s] && (whole || o.accWriterFull[1 - s])) HIP_TRY(ctx, hipStreamWaitEvent(st, o.evAccWriter[1 - s], 0));
-    return RT_OK;
-}
-static int after_acc_write(RtContext* ctx, int s, bool whole)
-{
-    RtContext::Order& o = ctx->ord;
-    HIP_TRY(ctx, hipEventRecord(o.evAccWriter[s], stream_of(ctx, s)));
-    o.accWriterPending[s] = true;
-    o.accWriterFull[s] = whole;
-    if (whole) {
-        HIP_TRY(ctx, hipEventRecord(o.evAccFull[s], stream_of(ctx, s)));
-        o.accFullPending[s] = true;
-    }
-    return RT_OK;
-}
-/* a whole-image writer on stream s was ordered after everything the other stream wrote (before_acc_write(s, true)): later writers wait for it */
-static void other_stream_settled(RtContext* ctx, int s) { ctx->ord.accWriterPending[1 - s] = false; }
-} // namespace LaunchOrder
 
 /* ---- choose variant: kernel instantiation, LDS, resident workgroups */
 static int choose_variant(RtContext* ctx, KArgs& a, LaunchPlan& plan, bool* manyOut)
@@ -1757,9 +1631,9 @@ static int prepare_records(RtContext* ctx, const LaunchPlan& plan)
  * ... frames have been recorded; the sort runs on the stream of the launch that first uses it, writes the order buffer that no running
  * kernel reads, works on its own snapshot of the costs (running kernels keep raising them) — it never joins the two streams (a join in the
  * middle of back-to-back launches serialises the next launch behind the drain of the previous one; round 4). */
-static int prepare_tile_order(RtContext* ctx, KArgs& a, int tiles, int nFrames, int lane, bool twoOwn)
+static int prepare_tile_order(RtContext* ctx, KArgs& a, int tiles)
 {
-    if (!ctx->lptEnabled) return RT_OK;
+    if (!ctx->order.lpt) return RT_OK;
     if (ctx->orderTiles != tiles) {
         HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
         hipFree(ctx->dTileCost); ctx->dTileCost = nullptr;
@@ -1771,34 +1645,16 @@ static int prepare_tile_order(RtContext* ctx, KArgs& a, int tiles, int nFrames, 
         HIP_TRY(ctx, hipMalloc(&ctx->dTileKey, sizeof(uint32_t) * tiles));
         HIP_TRY(ctx, hipMemsetAsync(ctx->dTileCost, 0, sizeof(uint32_t) * tiles, joined(ctx)));
         ctx->orderTiles = tiles;
-        ctx->orderValid = false;
-        ctx->orderCur = 0;
-        LaunchOrder::forget_order(ctx);
-        ctx->framesSinceResize = 0;
-        ctx->nextSortAt = 1;
-    }
-    if (ctx->framesSinceResize >= ctx->nextSortAt) {
-        while (ctx->nextSortAt <= ctx->framesSinceResize) ctx->nextSortAt *= 2;
-        const int target = ctx->orderValid ? 1 - ctx->orderCur : 0;
-        const int ss = lane; /* a single frame's two halves: sorted on the main stream, the side stream waits */
-        int rc = LaunchOrder::begin_sort(ctx, ss, target);
-        if (rc) return rc;
-        hipLaunchKernelGGL(rtk::rt_order_kernel, dim3(1), dim3(1024), 0, LaunchOrder::stream_of(ctx, ss), ctx->dTileCost, ctx->dTileKey, ctx->dTileOrder[target], tiles);
-        HIP_TRY(ctx, hipGetLastError());
-        if ((rc = LaunchOrder::end_sort(ctx, ss, twoOwn, ctx->orderValid ? ctx->orderCur : -1))) return rc;
-        ctx->orderCur = target;
-        ctx->orderValid = true;
+        ctx->order.forget_order();
     }
     a.tileCost = ctx->dTileCost;
-    a.tileOrder = ctx->orderValid ? ctx->dTileOrder[ctx->orderCur] : nullptr;
-    ctx->framesSinceResize += nFrames;
     return RT_OK;
 }
 
 /* ---- prepare buffers: the staging slab of a fused launch ([frame][pixel] colours awaiting rt_accumulate_kernel), one per stream so that
  * consecutive fused launches can alternate between the streams.  Returns 1 when the launch cannot be staged on this lane (the caller
  * falls back), 0 when a.staging is set. */
-static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, int lane, bool twoOwn, bool* unavailable)
+static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, int lane, bool split, bool* unavailable)
 {
     *unavailable = false;
     const size_t need = (size_t)nFrames * nPix * 16;
@@ -1806,7 +1662,7 @@ static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, i
         HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
         /* both slabs are made by the first fused launch (a warm-up launch then pays for both: an allocation of this size takes
          * milliseconds); sized for the largest batch this context forms; if memory is short, for this batch */
-        for (int sl = 0; sl < (twoOwn && ctx->alternate ? 2 : 1); sl++) {
+        for (int sl = 0; sl < (split && ctx->order.alternate ? 2 : 1); sl++) {
             const int b = sl == 0 ? lane : 1 - lane;
             if (ctx->stagingBytes[b] >= need) continue;
             hipFree(ctx->dStaging[b]);
@@ -1835,7 +1691,7 @@ static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, i
                 }
             }
             ctx->stagingBytes[b] = got;
-            if (got < need && b != lane) ctx->alternate = false; /* no room for the second slab: fused launches stay on one stream (until rt_resize) */
+            if (got < need && b != lane) ctx->order.alternate = false; /* no room for the second slab: fused launches stay on one stream (until rt_resize) */
         }
     }
     if (ctx->stagingUnavailable || ctx->stagingBytes[lane] < need) {
@@ -1848,7 +1704,7 @@ static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, i
 }
 
 /* ---- launch tuner (suspension threshold 3/8 or 4/8) and the frames-per-launch budget: collect what has passed, decide for this launch */
-static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool staged, int nFrames)
+static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool staged, int nFrames, long long framesSinceResize)
 {
     RtContext::Tuner& tn = ctx->tuner;
     RtContext::Tuner::Probe* probe = nullptr;
@@ -1868,7 +1724,7 @@ static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool stage
             tn.done = true;
             a.suspendNum = tn.decided;
             if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch tuner: 3/8 %.3f ms/frame, 4/8 %.3f ms/frame -> %d/8\n", tn.ms[0] / tn.n[0], tn.ms[1] / tn.n[1], tn.decided);
-        } else if (staged && nFrames >= 8 && !ctx->stats && ctx->framesSinceResize >= 48) { /* only long progressive renders are tuned: short runs keep 3/8 */
+        } else if (staged && nFrames >= 8 && !ctx->stats && framesSinceResize >= 48) { /* only long progressive renders are tuned: short runs keep 3/8 */
             for (auto& pr : tn.probe)
                 if (!pr.live) { probe = &pr; break; }
             if (probe) {
@@ -1936,7 +1792,37 @@ static void mark_fused_launch_end(RtContext* ctx, int slot, hipStream_t st, int 
     }
 }
 
-/* ---- enqueue: the trace kernel(s) of one launch.
+/* ---- HipOrder: the steps LaunchOrder::run issues, on HIP streams and events */
+struct LaunchJob {
+    KArgs& a;
+    const LaunchPlan& plan;
+    int tiles, nFrames;
+    size_t nPix;
+    RtContext::Tuner::Probe* probe;
+};
+
+hipStream_t HipOrder::stream(int s) const { return s ? ctx->sideStream : ctx->stream; }
+
+int HipOrder::record(rt_order::Event e, int s)
+{
+    HIP_TRY(ctx, hipEventRecord(ev[e], stream(s)));
+    return RT_OK;
+}
+
+int HipOrder::wait(int s, rt_order::Event e)
+{
+    HIP_TRY(ctx, hipStreamWaitEvent(stream(s), ev[e], 0));
+    return RT_OK;
+}
+
+int HipOrder::sort(int s, int target)
+{
+    hipLaunchKernelGGL(rtk::rt_order_kernel, dim3(1), dim3(1024), 0, stream(s), ctx->dTileCost, ctx->dTileKey, ctx->dTileOrder[target], job->tiles);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+/* The trace kernel of part `part` of a launch.
  * Persistent launches.  Queue position q of part p is entry q*parts + p of the (longest chain first) tile order, so the parts are
  * disjoint and equally heavy.  Each kernel is given as many single-wave workgroups as the chip keeps resident, never more than it has
  * work items: its first `grid` positions are taken by blockIdx, the rest through the part's atomic queue, which counts monotonically
@@ -1944,80 +1830,72 @@ static void mark_fused_launch_end(RtContext* ctx, int slot, hipStream_t st, int 
  * Two parts on two streams for a single frame while the context runs on its own stream: a kernel ends with a drain phase as long as one
  * pixel's serial chain, during which waves retire one by one; the other stream's kernel — different pixels, no dependence — picks up
  * every slot that frees.  With a caller-provided stream the caller's stream order is the contract: one kernel on that stream. */
-static int enqueue_trace(RtContext* ctx, KArgs& a, const LaunchPlan& plan, int tiles, int nFrames, int lane, int parts, RtContext::Tuner::Probe* probe)
+int HipOrder::trace(int s, int p, int parts)
 {
+    KArgs& a = job->a;
+    const LaunchPlan& plan = job->plan;
+    const int nFrames = job->nFrames;
     const bool staged = nFrames > 1;
-    for (int p = 0; p < parts; p++) {
-        const int partTiles = (tiles - p + parts - 1) / parts;
-        /* frames per item: 1 = the most items and the shortest tail.  The FLAT scenes' per-frame chains are short and uniform; there one
-         * pixel set-up per group of frames is worth 7 % (config 2: 0.765 -> 0.710 ms/frame at groups of 4) as long as every resident wave
-         * still gets >= 8 items; fewer items than that, or groups of 8+, lose it to the tail again, and the BVH scenes gain nothing
-         * measurable (profiles/r02_frame_group_sweep.txt; their kernel variants are compiled without groups). */
-        int group = 1;
-        if (staged && ctx->flatScene && ctx->params.numRaysPerPixel < 65536) {
-            if (ctx->frameGroupOverride > 0) group = ctx->frameGroupOverride;
-            else
-                while (group < 4 && 2 * group <= nFrames && (long long)partTiles * ((nFrames + 2 * group - 1) / (2 * group)) >= 8 * plan.resident * plan.wavesPerGroup) group *= 2;
-            if (group > nFrames) group = nFrames;
-        }
-        a.frameGroup = group;
-        a.frameGroupShift = 0;
-        while ((2 << a.frameGroupShift) <= group) a.frameGroupShift++;
-        a.frameGroups = staged ? (nFrames + group - 1) / group : 1;
-        const long long items = (long long)partTiles * a.frameGroups;
-        /* the grid: workgroups of wavesPerGroup persistent waves each — as many as the chip keeps resident, never more waves than there
-         * are items (rounded up to whole workgroups: a wave without an item of its own goes to the queue, finds it empty and ends) */
-        const int wpb = plan.wavesPerGroup;
-        long long wantWaves = plan.resident * wpb < items ? plan.resident * wpb : items;
-        if (ctx->gridOverride > 0) wantWaves = ctx->gridOverride < items ? ctx->gridOverride : items;
-        const int grid = (int)((wantWaves + wpb - 1) / wpb);
-        const unsigned long long gridWaves = (unsigned long long)grid * wpb;
-        const unsigned long long byIndex = gridWaves < (unsigned long long)items ? gridWaves : (unsigned long long)items; /* positions taken by wave index */
-        a.launchTiles = partTiles;
-        a.launchItems = (int)items;
-        a.orderOffset = p;
-        a.orderStride = parts;
-        /* One kernel alone: all its workgroups become resident at once, the first `grid` positions go by blockIdx and only the rest
-         * through the queue.  Two kernels sharing the chip: workgroups are dispatched as slots free up, possibly late, so every
-         * position — the longest chains first — comes from the queue. */
-        a.queueStart = parts == 2 ? 1 : 0;
-        if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch variant=%d part=%d/%d tiles=%d grid=%d x %d waves perCU=%d lds=%zu\n", plan.variant, p, parts, partTiles, grid, wpb, ctx->occPerCU[plan.variant], plan.ldsBytes);
-        /* stream, pixel-record slot and tile-queue counter of this kernel: part p of a two-part frame, or the fused launch's lane */
-        const int q = parts == 2 ? p : lane;
-        hipStream_t st = LaunchOrder::stream_of(ctx, q);
-        a.pxCold = (float4*)((char*)ctx->dPxCold + (size_t)q * ctx->pxColdWaves * RT_COLD_STRIDE_BYTES);
-        a.tileQueue = ctx->dTileQueue + q;
-        a.tileQueueBase = ctx->tileQueueNext[q] - (a.queueStart ? 0ull : byIndex);
-        int rc;
-        if ((rc = LaunchOrder::before_order_read(ctx, q))) return rc;
-        if (!staged && (rc = LaunchOrder::before_acc_write(ctx, q, parts == 1))) return rc; /* the trace kernel itself adds into the accumulation buffer (RCC:20-23) */
-        const int fuseSlot = staged ? mark_fused_launch_begin(ctx, st) : -1;
-        if (probe) hipEventRecord(probe->start, st);
-        hipLaunchKernelGGL(parts == 2 ? plan.kernHalf : plan.kern, dim3(grid), dim3(plan.blockThreads), plan.ldsBytes, st, a);
-        if (probe) { hipEventRecord(probe->stop, st); probe->live = true; }
-        HIP_TRY(ctx, hipGetLastError()); /* a refused launch ran no wave: the device counter did not move */
-        mark_fused_launch_end(ctx, fuseSlot, st, nFrames);
-        /* every position not taken by wave index is one successful fetch, and each of the grid's waves overshoots once */
-        ctx->tileQueueNext[q] += (unsigned long long)items - (a.queueStart ? 0ull : byIndex) + gridWaves;
-        if (q == 1) LaunchOrder::side_used(ctx);
-        if (!staged && (rc = LaunchOrder::after_acc_write(ctx, q, parts == 1))) return rc;
+    const int partTiles = (job->tiles - p + parts - 1) / parts;
+    a.tileOrder = ctx->order.orderValid ? ctx->dTileOrder[ctx->order.orderCur] : nullptr; /* (a sort of this launch may just have written it) */
+    /* frames per item: 1 = the most items and the shortest tail.  The FLAT scenes' per-frame chains are short and uniform; there one
+     * pixel set-up per group of frames is worth 7 % (config 2: 0.765 -> 0.710 ms/frame at groups of 4) as long as every resident wave
+     * still gets >= 8 items; fewer items than that, or groups of 8+, lose it to the tail again, and the BVH scenes gain nothing
+     * measurable (profiles/r02_frame_group_sweep.txt; their kernel variants are compiled without groups). */
+    int group = 1;
+    if (staged && ctx->flatScene && ctx->params.numRaysPerPixel < 65536) {
+        if (ctx->frameGroupOverride > 0) group = ctx->frameGroupOverride;
+        else
+            while (group < 4 && 2 * group <= nFrames && (long long)partTiles * ((nFrames + 2 * group - 1) / (2 * group)) >= 8 * plan.resident * plan.wavesPerGroup) group *= 2;
+        if (group > nFrames) group = nFrames;
     }
-    if (!staged && parts == 1) LaunchOrder::other_stream_settled(ctx, 0); /* ordered before the main stream's kernel just launched */
+    a.frameGroup = group;
+    a.frameGroupShift = 0;
+    while ((2 << a.frameGroupShift) <= group) a.frameGroupShift++;
+    a.frameGroups = staged ? (nFrames + group - 1) / group : 1;
+    const long long items = (long long)partTiles * a.frameGroups;
+    /* the grid: workgroups of wavesPerGroup persistent waves each — as many as the chip keeps resident, never more waves than there
+     * are items (rounded up to whole workgroups: a wave without an item of its own goes to the queue, finds it empty and ends) */
+    const int wpb = plan.wavesPerGroup;
+    long long wantWaves = plan.resident * wpb < items ? plan.resident * wpb : items;
+    if (ctx->gridOverride > 0) wantWaves = ctx->gridOverride < items ? ctx->gridOverride : items;
+    const int grid = (int)((wantWaves + wpb - 1) / wpb);
+    const unsigned long long gridWaves = (unsigned long long)grid * wpb;
+    const unsigned long long byIndex = gridWaves < (unsigned long long)items ? gridWaves : (unsigned long long)items; /* positions taken by wave index */
+    a.launchTiles = partTiles;
+    a.launchItems = (int)items;
+    a.orderOffset = p;
+    a.orderStride = parts;
+    /* One kernel alone: all its workgroups become resident at once, the first `grid` positions go by blockIdx and only the rest
+     * through the queue.  Two kernels sharing the chip: workgroups are dispatched as slots free up, possibly late, so every
+     * position — the longest chains first — comes from the queue. */
+    a.queueStart = parts == 2 ? 1 : 0;
+    if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch variant=%d part=%d/%d tiles=%d grid=%d x %d waves perCU=%d lds=%zu\n", plan.variant, p, parts, partTiles, grid, wpb, ctx->occPerCU[plan.variant], plan.ldsBytes);
+    /* the stream's pixel-record slot and tile-queue counter */
+    hipStream_t st = stream(s);
+    a.pxCold = (float4*)((char*)ctx->dPxCold + (size_t)s * ctx->pxColdWaves * RT_COLD_STRIDE_BYTES);
+    a.tileQueue = ctx->dTileQueue + s;
+    a.tileQueueBase = ctx->tileQueueNext[s] - (a.queueStart ? 0ull : byIndex);
+    RtContext::Tuner::Probe* probe = job->probe;
+    const int fuseSlot = staged ? mark_fused_launch_begin(ctx, st) : -1;
+    if (probe) hipEventRecord(probe->start, st);
+    hipLaunchKernelGGL(parts == 2 ? plan.kernHalf : plan.kern, dim3(grid), dim3(plan.blockThreads), plan.ldsBytes, st, a);
+    if (probe) { hipEventRecord(probe->stop, st); probe->live = true; }
+    HIP_TRY(ctx, hipGetLastError()); /* a refused launch ran no wave: the device counter did not move */
+    mark_fused_launch_end(ctx, fuseSlot, st, nFrames);
+    /* every position not taken by wave index is one successful fetch, and each of the grid's waves overshoots once */
+    ctx->tileQueueNext[s] += (unsigned long long)items - (a.queueStart ? 0ull : byIndex) + gridWaves;
     return RT_OK;
 }
 
-/* ---- enqueue: RCC:18-23 for a fused launch's frames, in frame order, after every earlier frame's */
-static int enqueue_accumulate(RtContext* ctx, const KArgs& a, int nFrames, size_t nPix, int lane)
+/* RCC:18-23 for a fused launch's frames, in frame order */
+int HipOrder::accumulate(int s)
 {
-    int blocks = (int)((nPix + 255) / 256);
+    int blocks = (int)((job->nPix + 255) / 256);
     if (blocks > 4096) blocks = 4096;
-    int rc = LaunchOrder::before_acc_write(ctx, lane, true);
-    if (rc) return rc;
-    hipLaunchKernelGGL(rtk::rt_accumulate_kernel, dim3(blocks), dim3(256), 0, LaunchOrder::stream_of(ctx, lane), (const float4*)ctx->dStaging[lane], nFrames, nPix,
-                       (float4*)a.accumulated, (float4*)a.frameRender, nPix);
+    hipLaunchKernelGGL(rtk::rt_accumulate_kernel, dim3(blocks), dim3(256), 0, stream(s), (const float4*)ctx->dStaging[s], job->nFrames, job->nPix,
+                       (float4*)job->a.accumulated, (float4*)job->a.frameRender, job->nPix);
     HIP_TRY(ctx, hipGetLastError());
-    if ((rc = LaunchOrder::after_acc_write(ctx, lane, true))) return rc;
-    LaunchOrder::other_stream_settled(ctx, lane); /* this accumulate is ordered after it; later writers wait for this one */
     return RT_OK;
 }
 
@@ -2032,29 +1910,28 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
     int rc = choose_variant(ctx, a, plan, &many);
     if (rc) return rc;
     if ((rc = prepare_records(ctx, plan))) return rc;
+    if ((rc = prepare_tile_order(ctx, a, tiles))) return rc;
     /* Fused launches (several frames: (tile, frame) items, per-frame colours staged and summed in frame order afterwards) alternate
      * between the context's two streams (own streams only), each with its own staging slab: the trace kernel of launch k+1 — other
      * frames, nothing shared but the scene — starts while launch k drains, and only the rt_accumulate_kernels, which add into the
-     * accumulation buffer in FRAME order, are chained by events. */
-    const bool staged = nFrames > 1;
-    const size_t nPix = (size_t)ctx->localRows * ctx->W;
-    /* Two kernels sharing the chip refill each other's freed wave slots one by one — with single-wave workgroups.  A 12-wave workgroup frees
+     * accumulation buffer in FRAME order, are chained by events.
+     * Two kernels sharing the chip refill each other's freed wave slots one by one — with single-wave workgroups.  A 12-wave workgroup frees
      * its slots and its LDS only when its LAST wave ends, and the other kernel's workgroups need twelve slots at once: overlapping launches then
      * wait for each other instead of filling gaps (config 4 / 5: 7.8 / 50.2 ms per frame for K back-to-back rt_render_frame against 6.2 / 42.1 on
-     * one stream, profiles/r06_groups_and_streams.txt).  The BVH variants' group launches therefore stay on ONE stream, one kernel per launch;
-     * RT_GROUP_STREAMS=2 restores the overlap for A/B runs. */
-    static const bool groupsOverlap = getenv("RT_GROUP_STREAMS") && atoi(getenv("RT_GROUP_STREAMS")) == 2;
-    const bool twoOwn = ctx->twoStreams && ctx->stream == ctx->ownStream && ctx->sideStream && (plan.wavesPerGroup == 1 || groupsOverlap);
-    const int lane = (staged && twoOwn && ctx->alternate) ? ctx->stagedNext : 0;
-    if ((rc = prepare_tile_order(ctx, a, tiles, nFrames, lane, twoOwn))) return rc;
-    if (staged) {
+     * one stream, profiles/r06_groups_and_streams.txt).  The BVH variants' group launches therefore stay on ONE stream, one kernel per launch. */
+    rt_order::Shape shape;
+    shape.frames = nFrames;
+    shape.singleWave = plan.wavesPerGroup == 1;
+    shape.tiles = tiles;
+    const rt_order::Placement pl = ctx->order.place(shape);
+    const size_t nPix = (size_t)ctx->localRows * ctx->W;
+    if (pl.staged) {
         bool unavailable = false;
-        if ((rc = prepare_staging(ctx, a, nFrames, nPix, lane, twoOwn, &unavailable))) return rc;
+        if ((rc = prepare_staging(ctx, a, nFrames, nPix, pl.lane, pl.split, &unavailable))) return rc;
         if (unavailable) {
-            if (ctx->lptEnabled) ctx->framesSinceResize -= nFrames; /* counted again by the launches below */
-            if (lane == 1) { /* no room for the second slab: every fused launch on the main stream from now on */
-                ctx->alternate = false;
-                ctx->stagedNext = 0;
+            if (pl.lane == 1) { /* no room for the second slab: every fused launch on the main stream from now on */
+                ctx->order.alternate = false;
+                ctx->order.stagedNext = 0;
                 return launch_frames(ctx, frame0, nFrames);
             }
             /* not even one slab: the frames go out one launch each (a single-frame launch needs no staging) — a render call never
@@ -2065,18 +1942,11 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
             return RT_OK;
         }
     }
-    RtContext::Tuner::Probe* probe = tune_launch(ctx, a, staged, nFrames);
-    const int parts = (!staged && twoOwn && tiles >= 2) ? 2 : 1;
-    if ((parts == 2 || lane == 1) && (rc = LaunchOrder::fork_side(ctx))) return rc; /* the side stream follows what the main stream holds so far */
-    if ((rc = enqueue_trace(ctx, a, plan, tiles, nFrames, lane, parts, probe))) return rc;
-    if (staged) {
-        if ((rc = enqueue_accumulate(ctx, a, nFrames, nPix, lane))) return rc;
-        if (twoOwn && ctx->alternate) ctx->stagedNext = 1 - lane;
-    } else if (parts == 2 && ctx->fusedBehindFirstPart) {
-        /* a fused launch that follows a two-part frame goes behind the part that started first and ends first (the main stream's), so
-         * its waves take the slots the other part's drain leaves empty instead of waiting for that drain to end */
-        ctx->stagedNext = 0;
-    }
+    LaunchJob job{a, plan, tiles, nFrames, nPix, tune_launch(ctx, a, pl.staged, nFrames, pl.framesAfter)};
+    ctx->backend.job = &job;
+    rc = ctx->order.run(pl, ctx->backend);
+    ctx->backend.job = nullptr;
+    if (rc) return rc;
     ctx->pixelFrames += (uint64_t)ctx->localRows * ctx->W * nFrames;
     ctx->lastLaunched += nFrames;
     return RT_OK;
@@ -2097,7 +1967,7 @@ static int check_renderable(RtContext* ctx)
 static bool gpu_idle(RtContext* ctx)
 {
     if (hipStreamQuery(ctx->stream) != hipSuccess) return false;
-    if (ctx->sideStream && ctx->ord.sideDirty && hipStreamQuery(ctx->sideStream) != hipSuccess) return false;
+    if (ctx->sideStream && ctx->order.sideDirty && hipStreamQuery(ctx->sideStream) != hipSuccess) return false;
     return true;
 }
 

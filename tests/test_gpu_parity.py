@@ -708,6 +708,40 @@ def test_caller_stream_keeps_stream_order(pkg, api, orc):
     assert bits_equal(a, b)
 
 
+def test_pooled_and_unpooled_launches_of_one_context_across_sort_points(pkg, api, orc, monkeypatch):
+    """rt_render_frames(2, 3, 2, 2, 3, 2) back to back on a FLAT scene sized so that 3-frame launches run as pooled workgroups (main
+    stream only) and 2-frame launches as single waves (alternating streams); sorts fall in launches 2, 3 and 5.  Before the tile order's
+    bookkeeping followed the context, the pooled launch's sort on the main stream left the side stream unmarked and the last launch read
+    the order buffer that sort was still writing (the shortest such sequence tests/test_launch_order.py's checker finds).  A race on the
+    GPU shows only when the kernels meet: the CPU checker proves the rule, this guards against regressions."""
+    import ctypes
+    monkeypatch.setenv("RT_POOL_MIN_ITEMS", "1")
+    cus = ctypes.c_int()
+    assert ctypes.CDLL("libamdhip64.so").hipDeviceGetAttribute(ctypes.byref(cus), 63, 0) == 0  # hipDeviceAttributeMultiprocessorCount
+    # a FLAT launch is pooled from RT_POOL_MIN_ITEMS (tile, frame) items per resident wave: CUs x 4 SIMDs x 8 waves (choose_variant)
+    items = cus.value * 4 * 8
+    lo, hi = -(-items // 3), -(-items // 2) - 1   # tiles: 3 frames pooled, 2 frames not
+    rows = -(-lo // 64)                           # 8 x 8 tiles, 64 per row of a 512-pixel image
+    assert 64 * rows <= hi
+    w, h = 512, 8 * rows
+    shapes = (2, 3, 2, 2, 3, 2)
+    out = []
+    for lib, reps in ((orc, 1), (api, 3)):
+        for _ in range(reps):
+            tr = lib.create_tracer(16 if lib is orc else 0)
+            mgr = pkg.scenes.get(2).make_manager(tr, lib, w, h)
+            mgr.OnEnable(renderSeed=13)
+            mgr.InitFrame()
+            for n in shapes:
+                tr.render_frames(n)                   # nothing between the launches: no read, upload or synchronise
+            out.append((tr.read_accumulated().copy(), tr.read_frame().copy(), tr.frame()))
+            tr.close()
+    (b, fb, nb), *got = out
+    for a, fa, na in got:
+        assert na == nb == 1 + sum(shapes)
+        assert bits_equal(a, b) and bits_equal(fa, fb), int(np.any(a.view(np.uint32) != b.view(np.uint32), axis=-1).sum())
+
+
 def test_tile_order_learning_does_not_change_results(pkg, api, orc):
     """9 frames: the longest-chain-first queue order is re-learnt after frames 1, 2, 4 and 8."""
     a, b, ca, cb = pair(pkg, api, orc, 2, 96, 54, 9)

@@ -1,0 +1,121 @@
+"""The ordering of a context's two render streams (ray-tracing_amd/csrc/rt_launch_order.h), checked without a GPU.
+
+tests/launch_order_driver.cpp is built against the header with the host compiler.  Its fake backend turns what the module issues into a
+happens-before model (stream order, event edges: a wait binds to the latest record of the event issued before it, host synchronises)
+and the buffers each step touches; a small context mirrors launch_frames around place() / run().  The checks:
+(a) every pair of conflicting accesses is ordered in issue order; (b) the halves of a two-part frame, and in steady state the trace
+kernels of consecutive fused launches on different streams, are NOT ordered against each other; (c) the exact record / wait lists
+of three steady-state sequences; (d) the checker itself: dropping the waits of an event kind that matters produces a violation."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    exe = str(tmp_path_factory.mktemp("launch_order") / "driver")
+    subprocess.check_call([cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "launch_order_driver.cpp"), "-o", exe])
+
+    def run(*args):
+        return subprocess.check_output([exe, *args], text=True, timeout=600).splitlines()
+    return run
+
+
+def findings(lines):
+    return [l for l in lines if l.startswith(("VIOLATION", "ORDERED", "FOUND"))]
+
+
+DIRECTED = [
+    "f f f f f f f f f",                         # single frames from idle, sorts after 1, 2, 4, 8 frames
+    "f F16s F16s F16s F16s F16s",                # config-4-like
+    "f F16p F16p F16p F16p F16p",                # config-2-like
+    "F16s f F16s f F17s f f F33s w f",           # rt_render_frames(17) and friends: fused + two-part frames back to back
+    "F2s F4p F2s F3p F2s F2s",                   # pooled and unpooled launches of one context across sort points
+    "F2s F3p F2s F2s F3p F2s",
+    "F5g f F5g F64g w F3g f",                    # group launches stay on the main stream
+    "f F9s w r f F9s F2p F9s r F3s F3s",         # resizes
+    "f F8s c f F8s F8s w o f F8s F8s",           # a caller's stream and back
+]
+
+
+@pytest.mark.parametrize("opts", [[], ["two=0"], ["alt=0"], ["lpt=0"], ["slab1=0"], ["slabs=0"]], ids=lambda o: ",".join(o) or "default")
+def test_directed_sequences_are_ordered(driver, opts):
+    for seq in DIRECTED:
+        out = driver("run", seq, *opts)
+        assert not findings(out), (seq, opts, findings(out))
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3, 4])
+def test_random_sequences_are_ordered(driver, seed):
+    """Seeded random sequences: single frames, fused launches of 2-64 frames (pooled, group or single-wave), non-render work, resizes,
+    caller streams, RT_TWO_STREAMS=0 / RT_LPT=0 / RT_ALTERNATE=0, staging slabs that do not fit."""
+    out = driver("random", str(seed), "3000")
+    assert out[0] == "clean 3000", out[:12]
+
+
+def test_shortest_sequences_over_pooled_and_unpooled_launches_are_ordered(driver):
+    """Every sequence of up to six launches of 1 (two parts), 2 (single-wave) and 3 (pooled) frames.  Before the sort's bookkeeping
+    followed the context, a pooled launch that sorted on the main stream cleared the side stream's pending sort, and
+    `F2s F3p F2s F2s F3p F2s` let the last launch read the order buffer the sort before it was still writing."""
+    assert driver("shortest", "6", "f F2s F3p w") == ["clean"]
+
+
+STEADY = {
+    # one frame, then back-to-back pooled fused launches: one stream; the sorts inside them still retire the old buffer on the side stream
+    "f F16p F16p F16p F16p": [
+        "f: sync sync zero-costs +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 traceB@1 +ACC_WRITER1@1",
+        "F16p: +JOIN@1 main<JOIN sync sync sort0@0 +SORT@0 trace@0 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16p: sort1@0 +SORT@0 +ORDER_RETIRE0@1 trace@0 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16p: main<ORDER_RETIRE0 sort0@0 +SORT@0 +ORDER_RETIRE1@1 trace@0 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16p: trace@0 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+    ],
+    # one frame, then single-wave fused launches alternating between the streams
+    "f F16s F16s F16s F16s F16s F16s": [
+        "f: sync sync zero-costs +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 traceB@1 +ACC_WRITER1@1",
+        "F16s: +JOIN@1 main<JOIN sync sort0@0 +SORT@0 trace@0 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16s: +FORK@0 side<FORK side<SORT sort1@1 +SORT@1 +ORDER_RETIRE0@0 trace@1 side<ACC_FULL0 side<ACC_WRITER0 acc@1 +ACC_WRITER1@1 +ACC_FULL1@1",
+        "F16s: main<ORDER_RETIRE0 main<SORT sort0@0 +SORT@0 +ORDER_RETIRE1@1 trace@0 main<ACC_FULL1 main<ACC_WRITER1 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16s: side<SORT trace@1 side<ACC_FULL0 side<ACC_WRITER0 acc@1 +ACC_WRITER1@1 +ACC_FULL1@1",
+        "F16s: main<ORDER_RETIRE1 sort1@0 +SORT@0 +ORDER_RETIRE0@1 trace@0 main<ACC_FULL1 main<ACC_WRITER1 acc@0 +ACC_WRITER0@0 +ACC_FULL0@0",
+        "F16s: side<SORT trace@1 side<ACC_FULL0 side<ACC_WRITER0 acc@1 +ACC_WRITER1@1 +ACC_FULL1@1",
+    ],
+    # two-part frames interleaved with reads
+    "f w f w f f w f f": [
+        "f: sync sync zero-costs +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 traceB@1 +ACC_WRITER1@1",
+        "w: +JOIN@1 main<JOIN work",
+        "f: sort0@0 +SORT@0 +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 side<SORT traceB@1 +ACC_WRITER1@1",
+        "w: +JOIN@1 main<JOIN work",
+        "f: sort1@0 +SORT@0 +ORDER_RETIRE0@1 +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 side<SORT traceB@1 +ACC_WRITER1@1",
+        "f: traceA@0 +ACC_WRITER0@0 traceB@1 +ACC_WRITER1@1",
+        "w: +JOIN@1 main<JOIN work",
+        "f: main<ORDER_RETIRE0 sort0@0 +SORT@0 +ORDER_RETIRE1@1 +FORK@0 side<FORK traceA@0 +ACC_WRITER0@0 side<SORT traceB@1 +ACC_WRITER1@1",
+        "f: traceA@0 +ACC_WRITER0@0 traceB@1 +ACC_WRITER1@1",
+    ],
+}
+
+
+@pytest.mark.parametrize("seq", list(STEADY))
+def test_steady_state_records_and_waits(driver, seq):
+    """The exact events per launch.  Steady state starts at the third launch: the first fused launch makes the staging slabs (a host
+    synchronise), so the side stream's next launch follows the main stream's work so far (FORK)."""
+    out = driver("run", seq, "steady=3")
+    assert out == STEADY[seq]
+
+
+MATTERS = ["FORK", "JOIN", "SORT", "ACC_WRITER1", "ACC_FULL0"]
+# ORDER_RETIRE0/1, ACC_WRITER0 and ACC_FULL1: under today's placement another wait always covers them (every stream that reads an
+# order buffer adds into the accumulation buffer before the other stream's next sort; a two-part frame starts on the main stream).
+# They stay: they state the rule for each resource, and the placement may change.
+
+
+@pytest.mark.parametrize("event", MATTERS)
+def test_the_checker_sees_a_dropped_wait(driver, event):
+    out = driver("random", "7", "4000", f"drop={event}")
+    assert out[0].startswith("FOUND") and any(l.startswith("VIOLATION") for l in out), (event, out[:3])
