@@ -29,18 +29,9 @@
 
 #include "rt_kernels.h"
 
-/* Frames per fused launch: a budget, not a constant.  A launch ends with a tail as long as one pixel chain, so short
- * frames want many per launch (a rank that renders 1/8 of config 2: 0.108 ms per frame, 7.9 work items per resident wave at 16 frames);
- * long frames must not turn into launches that last seconds.  RT_FUSE_MIN frames always; more — up to RT_FUSE_MAX — while the launch
- * stays under RT_FUSE_TARGET_MS at the frame time MEASURED on the previous fused launches (stop event to stop event — or, for a launch
- * without a predecessor, its own start to stop — polled, never waited for).  BVH scenes (>= 1.3 ms per frame) stay at 16.  RT_FUSE_CAP=n
- * pins it. */
-#define RT_FUSE_MIN 16
-#define RT_FUSE_MAX 64
-#define RT_FUSE_TARGET_MS 20.0
-#define RT_FUSE_SLAB_BYTES ((size_t)1536 << 20) /* a staging slab: 16 bytes per pixel and frame; 1920x1080: 45 frames, 3840x2160: 16 (2.1 GB), an eighth of 1080p: 64 */
 #include "rt_layout.h"
 #include "rt_launch_order.h"
+#include "rt_launch_plan.h"
 #define RT_VERSION_STRING "raytrace_hip gfx950 abi=1"
 
 static thread_local char g_err[512] = "";
@@ -347,10 +338,8 @@ int rt_create(int device_id, RtContext** out)
     if (const char* fg = getenv("RT_FRAME_GROUP")) ctx->frameGroupOverride = atoi(fg);
     if (const char* al = getenv("RT_ALTERNATE")) ctx->order.alternate = ctx->alternateWanted = atoi(al) != 0;
     ctx->order.set_two_streams(ctx->twoStreams && ctx->sideStream);
-    if (const char* fc = getenv("RT_FUSE_CAP")) {
-        const int v = atoi(fc);
-        if (v >= 1) { ctx->fuseCap = v > RT_FUSE_MAX ? RT_FUSE_MAX : v; ctx->fuseCapPinned = true; }
-    }
+    if (const char* fc = getenv("RT_FUSE_CAP"))
+        if (const int cap = rt_plan::pinned_fuse_cap(atoi(fc))) { ctx->fuseCap = cap; ctx->fuseCapPinned = true; }
     *out = ctx;
     return RT_OK;
 }
@@ -704,18 +693,15 @@ static std::vector<DFilter> append_filter_pairs(const std::vector<DFilter>& f)
 /* Chunks of the two-level model hierarchy (rt_device.h, DChunk): only built for more than 64 models.
  * Models the filter cannot reject (`always`) are kept in chunks of their own so that they do not spoil the
  * boxes of the others; the rest is clustered by the Morton code of the filter box centre. */
-#define RT_MAX_FILTER_EXT_WORDS 32
 static void make_chunks(const std::vector<DFilter>& filters, std::vector<DChunk>& chunks, int* nFiltered, int* extWords)
 {
     const int n = (int)filters.size();
     chunks.clear();
-    *nFiltered = n < 64 ? n : 64;
-    *extWords = 0;
+    const rt_plan::Filtering fl = rt_plan::filtering(n);
+    *nFiltered = fl.nFiltered;
+    *extWords = fl.extWords;
     if (n <= 64) return;
-    const int maxModels = 63 + 32 * RT_MAX_FILTER_EXT_WORDS;
-    const int nf = n < maxModels ? n : maxModels;
-    *nFiltered = nf;
-    *extWords = (nf - 63 + 31) / 32;
+    const int nf = fl.nFiltered;
     double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
     for (int i = 0; i < nf; i++)
         if (!filters[i].always)
@@ -973,43 +959,6 @@ struct PreparedScene {
     int wavesPerGroup = 1; /* plan_groups: what the layout's cache prefix was sized for */
 };
 
-/* ---- the BVH trace kernels' workgroups (round 6).  A CU keeps 4 x RT_MIN_WAVES_PER_SIMD waves of them (VGPR bound) if the LDS allows:
- * a wave needs (stack + pixel fields + mask extension) x 256 B.  What the CU's 160 KB leave over becomes the top-of-tree cache — one copy
- * per WORKGROUP, so the fewer, larger workgroups the more records it holds: 12 waves (2 groups per CU) unless RT_WAVES_PER_GROUP says
- * otherwise.  Pure arithmetic on the scene's tree height and model count (no device query): every context, the multi-device upload and
- * rt_debug_layout agree on it.  choose_variant confirms the occupancy with the runtime's own query. */
-#define RT_LDS_BYTES_PER_CU (160 * 1024)
-struct GroupPlan { int wavesPerGroup = 1; int cacheRecords = 0; };
-static size_t wave_lds_bytes(int stackEntries, int extWords)
-{
-    return (size_t)(stackEntries + RT_PIXEL_FIELDS + (extWords ? 2 + extWords : 0)) * RT_WAVE * sizeof(uint32_t);
-}
-static GroupPlan plan_groups(int maxHeight, int nModels)
-{
-    GroupPlan g;
-    const int nf = nModels <= 64 ? 0 : (nModels < 63 + 32 * 32 ? nModels : 63 + 32 * 32); /* make_chunks: extWords */
-    const int extWords = nf ? (nf - 63 + 31) / 32 : 0;
-    const size_t waveBytes = wave_lds_bytes(maxHeight, extWords);
-    int wavesPerCU = 4 * RT_MIN_WAVES_PER_SIMD;
-    if ((size_t)wavesPerCU * waveBytes > RT_LDS_BYTES_PER_CU) wavesPerCU = (int)(RT_LDS_BYTES_PER_CU / waveBytes);
-    if (wavesPerCU < 1) return g;
-    int want = RT_MAX_WAVES_PER_GROUP;
-    if (const char* e = getenv("RT_WAVES_PER_GROUP")) want = atoi(e);
-    if (want < 1) want = 1;
-    if (want > RT_MAX_WAVES_PER_GROUP) want = RT_MAX_WAVES_PER_GROUP;
-    while (want > 1 && wavesPerCU % want) want--; /* whole groups fill the CU's wave slots */
-    const int groupsPerCU = wavesPerCU / want;
-    /* LDS is handed out in blocks: keep 1 KB per group clear of the nominal share */
-    const long long share = (long long)RT_LDS_BYTES_PER_CU / groupsPerCU - 1024 - (long long)want * (long long)waveBytes;
-    long long records = share > 0 ? share / (long long)sizeof(DPair) : 0;
-    if (const char* e = getenv("RT_HOT_KB")) { const long long cap = atoll(e) * 1024 / (long long)sizeof(DPair); if (cap < records) records = cap < 0 ? 0 : cap; }
-    if (records > (1 << 16)) records = 1 << 16;
-    if (records < 16) return g; /* not worth a workgroup: single-wave groups, no cache */
-    g.wavesPerGroup = want;
-    g.cacheRecords = (int)records;
-    return g;
-}
-
 /* errors are reported on `ctx` (may be any context of the caller) */
 static int prepare_scene(RtContext* ctx, const RtModel* models, int n_models, const RtTriangle* triangles, int n_triangles,
                          const RtBVHNode* nodes, int n_nodes, const RtSphere* spheres, int n_spheres, PreparedScene& ps, const char* layoutOverride = nullptr)
@@ -1159,7 +1108,11 @@ static int prepare_scene(RtContext* ctx, const RtModel* models, int n_models, co
         {   /* the top-of-tree cache: as many records as the workgroups' LDS holds (or what RT_LAYOUT's cache=N says, within that) */
             bool anyInner = false;
             for (int i = 0; i < n_models; i++) anyInner = anyInner || !(rootCodes[i] & RT_CODE_LEAF);
-            const GroupPlan gp = anyInner ? plan_groups(maxHeight, n_models) : GroupPlan();
+            const char* wantWaves = getenv("RT_WAVES_PER_GROUP");
+            const char* hotKB = getenv("RT_HOT_KB");
+            const rt_plan::GroupPlan gp = anyInner ? rt_plan::plan_groups(maxHeight, n_models, wantWaves ? atoi(wantWaves) : RT_MAX_WAVES_PER_GROUP, hotKB != nullptr,
+                                                                           hotKB ? atoll(hotKB) : 0)
+                                                   : rt_plan::GroupPlan();
             ps.wavesPerGroup = gp.wavesPerGroup;
             /* Default rule (no `cache` word): the cache is used where it was measured to pay — scenes whose trees are small enough that the
              * records the LDS holds are at least 1/16 of all node pairs (configs 3 and 6: 96 % / 73 % of the inner steps served, frame time
@@ -1530,11 +1483,8 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
     }
     a.counters = ctx->dCounters;
     a.travLimit = ctx->travLimit;
+    a.poolSpinLimit = ctx->poolSpinLimit;
     a.wavesPerGroup = 1; /* (choose_variant decides the workgroup shape of the trace kernels; the debug hooks run single waves without a cache) */
-    a.hotUnits = 0;
-    a.waveLdsDwords = 0;
-    a.poolCells = 0;
-    a.poolSpinLimit = 1u << 16;
 }
 
 } /* extern "C" */
@@ -1545,79 +1495,75 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
  *     prepare_*         the buffers a launch needs — pixel records, tile order, staging slab; may synchronise (rarely)
  *     LaunchOrder       place: which stream(s), how many parts, whether the tile order is re-sorted (rt_launch_order.h);
  *                       run: the sort, trace and accumulate kernels through HipOrder, with the events that order the two streams
+ * Every size on this path — workgroup shape, LDS, grid, items, tile-queue positions, slab frames, frames per fused launch, the tuner's
+ * choice — is decided by rt_launch_plan.h; what is left here is the HIP work around it.
  * Dispatch semantics kept: RayComputeManager.cs:84-95 (one RayTrace dispatch per frame, Frame counts the accumulated frames).
  * ===================================================================================================================== */
 struct LaunchPlan {
     void (*kern)(const KArgs) = nullptr;     /* a launch that renders a whole frame or a batch of frames */
     void (*kernHalf)(const KArgs) = nullptr; /* the same code under a second name: the two halves of a two-part frame (rt_kernels.h) */
-    size_t ldsBytes = 0;
-    int blockThreads = RT_WAVE;
-    int variant = 0;             /* slot of the occupancy cache */
-    int wavesPerGroup = 1;       /* waves of a workgroup: each is one persistent wave of the launch */
+    rt_plan::LaunchShape shape;  /* workgroup shape, LDS, variant = slot of the occupancy cache */
     long long resident = 0;      /* workgroups the chip keeps resident */
 };
 
 /* ---- choose variant: kernel instantiation, LDS, resident workgroups */
-static int choose_variant(RtContext* ctx, KArgs& a, LaunchPlan& plan, bool* manyOut)
+/* the trace kernel's instantiations <STATS, FLAT, MANY, HOT>, indexed by rt_plan::LaunchShape::variant = stats + 2 flat + 4 many + 6 hot */
+#define RT_TRACE_VARIANT(STATS, FLAT, MANY, HOT) {rtk::rt_trace_kernel<STATS, FLAT, MANY, HOT>, rtk::rt_trace_half_kernel<STATS, FLAT, MANY, HOT>}
+static const struct { void (*kern)(const KArgs); void (*kernHalf)(const KArgs); } kTraceVariants[] = {
+    RT_TRACE_VARIANT(false, false, false, false), RT_TRACE_VARIANT(true, false, false, false), /* 0, 1: BVH, single waves */
+    RT_TRACE_VARIANT(false, true, false, false),  RT_TRACE_VARIANT(true, true, false, false),  /* 2, 3: FLAT, single waves */
+    RT_TRACE_VARIANT(false, false, true, false),  RT_TRACE_VARIANT(true, false, true, false),  /* 4, 5: BVH > 64 models, single waves */
+    RT_TRACE_VARIANT(false, false, false, true),  RT_TRACE_VARIANT(true, false, false, true),  /* 6, 7: BVH, top-of-tree cache */
+    RT_TRACE_VARIANT(false, true, false, true),   RT_TRACE_VARIANT(true, true, false, true),   /* 8, 9: FLAT, chain pool */
+    RT_TRACE_VARIANT(false, false, true, true),   RT_TRACE_VARIANT(true, false, true, true),   /* 10, 11: BVH > 64 models, top-of-tree cache */
+};
+#undef RT_TRACE_VARIANT
+static_assert(sizeof(kTraceVariants) / sizeof(kTraceVariants[0]) == RT_TRACE_VARIANTS, "one trace kernel per variant slot");
+static_assert(RT_TRACE_VARIANTS <= sizeof(RtContext::occPerCU) / sizeof(int), "the occupancy cache has a slot per variant");
+
+static int choose_variant(RtContext* ctx, KArgs& a, LaunchPlan& plan)
 {
-    const size_t coldBytes = ctx->flatScene ? (size_t)2 * RT_WAVE * 16 : 0; /* the FLAT variant keeps its pixel records in LDS (rt_kernels.h, PX_COLD) */
-    /* a wave: traversal stack + pixel fields + (more than 64 models) the mask extension: summary + words + the MANY variant's bounce row;
-     * a workgroup of the BVH variants: the top-of-tree cache, then its waves' regions (plan_groups) */
-    const size_t waveBytes = wave_lds_bytes(ctx->stackEntries, ctx->extWords) + coldBytes;
-    /* the shared region in front of the waves' regions: the BVH variants' top-of-tree cache, or the FLAT variant's chain pool */
-    /* ... for launches with enough work: a pooled workgroup is 16 persistent waves that leave together, and a launch with a few items per wave is
-     * all tail (config 1, 256 x 256: + 11 % with the pool) — at least RT_POOL_MIN_ITEMS (tile, frame) pairs per wave the chip keeps resident */
-    const bool pooled = ctx->flatScene && ctx->poolCells > 0 &&
-                        (long long)a.tilesX * a.tilesY * (a.nFrames > 0 ? a.nFrames : 1) >= (long long)ctx->poolMinItems * ctx->numCUs * 4 * RT_MIN_WAVES_PER_SIMD_FLAT;
-    const uint32_t hotUnits = ctx->flatScene ? (pooled ? (uint32_t)(RT_POOL_DWORDS / 4u) : 0u) : ctx->hotUnits;
-    const int wpb = ctx->flatScene ? (pooled ? ctx->poolWaves : 1) : (hotUnits ? ctx->wavesPerGroup : 1);
-    plan.wavesPerGroup = wpb;
-    plan.blockThreads = RT_WAVE * wpb;
-    plan.ldsBytes = (size_t)hotUnits * 16 + (size_t)wpb * waveBytes;
-    a.wavesPerGroup = wpb;
-    a.hotUnits = (int32_t)hotUnits;
-    a.poolCells = pooled ? ctx->poolCells : 0;
-    a.poolSpinLimit = ctx->poolSpinLimit;
-    a.waveLdsDwords = (int32_t)(waveBytes / sizeof(uint32_t));
+    rt_plan::SceneShape sc;
+    sc.flat = ctx->flatScene;
+    sc.stats = ctx->stats;
+    sc.stackEntries = ctx->stackEntries;
+    sc.extWords = ctx->extWords;
+    sc.nChunks = ctx->nChunks;
+    sc.hotUnits = ctx->hotUnits;
+    sc.wavesPerGroup = ctx->wavesPerGroup;
+    sc.poolCells = ctx->poolCells;
+    sc.poolWaves = ctx->poolWaves;
+    sc.poolMinItems = ctx->poolMinItems;
+    sc.numCUs = ctx->numCUs;
+    const rt_plan::LaunchShape& sh = plan.shape = rt_plan::launch_shape(sc, (long long)a.tilesX * a.tilesY, a.nFrames);
+    plan.kern = kTraceVariants[sh.variant].kern;
+    plan.kernHalf = kTraceVariants[sh.variant].kernHalf;
+    a.wavesPerGroup = sh.wavesPerGroup;
+    a.hotUnits = (int32_t)sh.hotUnits;
+    a.poolCells = sh.poolCells;
+    a.waveLdsDwords = sh.waveLdsDwords;
     a.stackEntries = ctx->stackEntries;
-    const bool many = ctx->nChunks > 0 && !ctx->flatScene;
-    *manyOut = many;
-    const bool hot = hotUnits > 0; /* the instantiations launched as multi-wave workgroups: with the LDS top-of-tree cache, or (FLAT) the chain pool */
-    plan.kern = ctx->flatScene ? (pooled ? (ctx->stats ? rtk::rt_trace_kernel<true, true, false, true> : rtk::rt_trace_kernel<false, true, false, true>)
-                                         : (ctx->stats ? rtk::rt_trace_kernel<true, true> : rtk::rt_trace_kernel<false, true>))
-                : many         ? (hot ? (ctx->stats ? rtk::rt_trace_kernel<true, false, true, true> : rtk::rt_trace_kernel<false, false, true, true>)
-                                      : (ctx->stats ? rtk::rt_trace_kernel<true, false, true> : rtk::rt_trace_kernel<false, false, true>))
-                               : (hot ? (ctx->stats ? rtk::rt_trace_kernel<true, false, false, true> : rtk::rt_trace_kernel<false, false, false, true>)
-                                      : (ctx->stats ? rtk::rt_trace_kernel<true, false> : rtk::rt_trace_kernel<false, false>));
-    plan.kernHalf = ctx->flatScene ? (pooled ? (ctx->stats ? rtk::rt_trace_half_kernel<true, true, false, true> : rtk::rt_trace_half_kernel<false, true, false, true>)
-                                             : (ctx->stats ? rtk::rt_trace_half_kernel<true, true> : rtk::rt_trace_half_kernel<false, true>))
-                    : many         ? (hot ? (ctx->stats ? rtk::rt_trace_half_kernel<true, false, true, true> : rtk::rt_trace_half_kernel<false, false, true, true>)
-                                          : (ctx->stats ? rtk::rt_trace_half_kernel<true, false, true> : rtk::rt_trace_half_kernel<false, false, true>))
-                                   : (hot ? (ctx->stats ? rtk::rt_trace_half_kernel<true, false, false, true> : rtk::rt_trace_half_kernel<false, false, false, true>)
-                                          : (ctx->stats ? rtk::rt_trace_half_kernel<true, false> : rtk::rt_trace_half_kernel<false, false>));
-    plan.variant = (ctx->flatScene ? 2 : many ? 4 : 0) + (ctx->stats ? 1 : 0) + (hot ? 6 : 0);
-    if (ctx->occBytes[plan.variant] != plan.ldsBytes + 1) { /* occupancy query cached per (variant, LDS bytes) */
+    if (ctx->occBytes[sh.variant] != sh.ldsBytes + 1) { /* occupancy query cached per (variant, LDS bytes) */
         int perCU = 0;
-        if (plan.ldsBytes > 48 * 1024) { /* more dynamic LDS than the default limit of a launch */
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.ldsBytes));
-            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.kernHalf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.ldsBytes));
+        if (sh.ldsBytes > 48 * 1024) { /* more dynamic LDS than the default limit of a launch */
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.ldsBytes));
+            HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(plan.kernHalf), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.ldsBytes));
         }
-        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, plan.kern, plan.blockThreads, plan.ldsBytes));
-        ctx->occPerCU[plan.variant] = perCU > 0 ? perCU : 1;
-        ctx->occBytes[plan.variant] = plan.ldsBytes + 1;
+        HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, plan.kern, sh.blockThreads, sh.ldsBytes));
+        ctx->occPerCU[sh.variant] = perCU > 0 ? perCU : 1;
+        ctx->occBytes[sh.variant] = sh.ldsBytes + 1;
         if (getenv("RT_DEBUG_LAUNCH"))
             fprintf(stderr, "[rt] kernel variant %d: %d stack entries, %zu B of LDS per workgroup of %d threads (%u B of it the top-of-tree cache: %u records), %d workgroups per CU\n",
-                    plan.variant, ctx->stackEntries, plan.ldsBytes, plan.blockThreads, hotUnits * 16u, hotUnits / 4u, perCU);
+                    sh.variant, ctx->stackEntries, sh.ldsBytes, sh.blockThreads, sh.hotUnits * 16u, sh.hotUnits / 4u, perCU);
     }
-    plan.resident = (long long)ctx->occPerCU[plan.variant] * ctx->numCUs;
+    plan.resident = (long long)ctx->occPerCU[sh.variant] * ctx->numCUs;
     return RT_OK;
 }
 
 /* ---- prepare buffers: the resident waves' pixel records */
 static int prepare_records(RtContext* ctx, const LaunchPlan& plan)
 {
-    const long long resWaves = plan.resident * plan.wavesPerGroup;
-    const long long waves = (ctx->gridOverride > resWaves ? ctx->gridOverride : resWaves) + plan.wavesPerGroup;
+    const long long waves = rt_plan::record_waves(plan.resident, plan.shape.wavesPerGroup, ctx->gridOverride);
     if (ctx->pxColdWaves < waves) { /* kernels in flight use the old block: freed after a synchronise, not now */
         HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
         hipFree(ctx->dPxCold); ctx->dPxCold = nullptr; ctx->pxColdWaves = 0;
@@ -1654,10 +1600,11 @@ static int prepare_tile_order(RtContext* ctx, KArgs& a, int tiles)
 /* ---- prepare buffers: the staging slab of a fused launch ([frame][pixel] colours awaiting rt_accumulate_kernel), one per stream so that
  * consecutive fused launches can alternate between the streams.  Returns 1 when the launch cannot be staged on this lane (the caller
  * falls back), 0 when a.staging is set. */
+static_assert(sizeof(float4) == RT_STAGED_PIXEL_BYTES, "a staged colour is one float4");
 static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, int lane, bool split, bool* unavailable)
 {
     *unavailable = false;
-    const size_t need = (size_t)nFrames * nPix * 16;
+    const size_t need = (size_t)nFrames * nPix * RT_STAGED_PIXEL_BYTES;
     if (!ctx->stagingUnavailable && ctx->stagingBytes[lane] < need) {
         HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
         /* both slabs are made by the first fused launch (a warm-up launch then pays for both: an allocation of this size takes
@@ -1669,16 +1616,13 @@ static int prepare_staging(RtContext* ctx, KArgs& a, int nFrames, size_t nPix, i
             ctx->dStaging[b] = nullptr;
             ctx->stagingBytes[b] = 0;
             /* room for the largest batch this context will ever form, so that a growing cap never re-makes a slab in the middle of a
-             * render: as many frames as fit RT_FUSE_SLAB_BYTES, between RT_FUSE_MIN and RT_FUSE_MAX (the cap is held to what the slabs hold) */
+             * render (rt_plan::slab_frames; the cap is held to what the slabs hold: rt_plan::fuse_cap) */
             /* (sized ONCE, at the first fused launch, on purpose: growing a slab later costs a synchronise + an allocation of this size in the
              * middle of a progressive render.  BVH scenes never batch more than RT_FUSE_MIN frames: a host that runs many contexts of such
              * scenes lowers the budget with RT_FUSE_SLAB_MB — ADVICE r5) */
             size_t slabBudget = RT_FUSE_SLAB_BYTES;
             if (const char* e = getenv("RT_FUSE_SLAB_MB")) { const long long mb = atoll(e); if (mb > 0) slabBudget = (size_t)mb << 20; }
-            size_t capFrames = nPix ? slabBudget / (nPix * 16) : RT_FUSE_MAX;
-            capFrames = capFrames < RT_FUSE_MIN ? RT_FUSE_MIN : capFrames > RT_FUSE_MAX ? RT_FUSE_MAX : capFrames;
-            if (capFrames < (size_t)nFrames) capFrames = (size_t)nFrames;
-            const size_t cap = capFrames * nPix * 16;
+            const size_t cap = rt_plan::slab_frames(nPix, slabBudget, nFrames) * nPix * RT_STAGED_PIXEL_BYTES;
             size_t got = cap;
             if (hipMalloc(&ctx->dStaging[b], cap) != hipSuccess) {
                 (void)hipGetLastError();
@@ -1709,7 +1653,7 @@ static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool stage
     RtContext::Tuner& tn = ctx->tuner;
     RtContext::Tuner::Probe* probe = nullptr;
     a.suspendNum = tn.decided;
-    if (!tn.done && !ctx->flatScene) {
+    if (!tn.done) {
         for (auto& pr : tn.probe)
             if (pr.live && hipEventQuery(pr.stop) == hipSuccess) {
                 float ms = 0;
@@ -1719,12 +1663,12 @@ static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool stage
                 }
                 pr.live = false;
             }
-        if (tn.n[0] >= 3 && tn.n[1] >= 3) {
-            tn.decided = (tn.ms[1] / tn.n[1] < 0.99 * (tn.ms[0] / tn.n[0])) ? 4 : 3; /* 4/8 has to win by more than the noise */
+        if (const int decided = rt_plan::tuner_decision(tn.ms, tn.n)) {
+            tn.decided = decided;
             tn.done = true;
             a.suspendNum = tn.decided;
             if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch tuner: 3/8 %.3f ms/frame, 4/8 %.3f ms/frame -> %d/8\n", tn.ms[0] / tn.n[0], tn.ms[1] / tn.n[1], tn.decided);
-        } else if (staged && nFrames >= 8 && !ctx->stats && framesSinceResize >= 48) { /* only long progressive renders are tuned: short runs keep 3/8 */
+        } else if (rt_plan::tuner_samples(ctx->flatScene, staged, nFrames, ctx->stats, framesSinceResize)) {
             for (auto& pr : tn.probe)
                 if (!pr.live) { probe = &pr; break; }
             if (probe) {
@@ -1748,21 +1692,9 @@ static RtContext::Tuner::Probe* tune_launch(RtContext* ctx, KArgs& a, bool stage
              * (a slot re-recorded by a later launch gives a negative or failing difference: skipped) */
             hipEvent_t from = fp.prev >= 0 ? ctx->fuseProbe[fp.prev].stop : fp.start;
             if (!from || hipEventElapsedTime(&ms, from, fp.stop) != hipSuccess || !(ms > 0)) { (void)hipGetLastError(); continue; }
-            const double perFrame = (double)ms / fp.frames;
-            int cap = (int)ceil(RT_FUSE_TARGET_MS / perFrame);
-            cap = cap < RT_FUSE_MIN ? RT_FUSE_MIN : cap > RT_FUSE_MAX ? RT_FUSE_MAX : cap;
-            {   /* never more than the staging slabs hold (they are sized once, prepare_staging) */
-                const size_t nPixNow = (size_t)ctx->localRows * ctx->W;
-                size_t slab = 0;
-                for (int b = 0; b < 2; b++)
-                    if (ctx->stagingBytes[b] && (slab == 0 || ctx->stagingBytes[b] < slab)) slab = ctx->stagingBytes[b];
-                if (nPixNow && slab) {
-                    const size_t holds = slab / (nPixNow * 16);
-                    if ((size_t)cap > holds) cap = holds < RT_FUSE_MIN ? RT_FUSE_MIN : (int)holds;
-                }
-            }
-            if (cap != ctx->fuseCap && ctx->verbose) fprintf(stderr, "[raytrace_hip] fused launches: %.3f ms per frame -> up to %d frames per launch\n", perFrame, cap);
-            ctx->fuseCap = cap;
+            const rt_plan::FuseCap fc = rt_plan::fuse_cap(ms, fp.frames, (size_t)ctx->localRows * ctx->W, ctx->stagingBytes);
+            if (fc.cap != ctx->fuseCap && ctx->verbose) fprintf(stderr, "[raytrace_hip] fused launches: %.3f ms per frame -> up to %d frames per launch\n", fc.msPerFrame, fc.cap);
+            ctx->fuseCap = fc.cap;
         }
     return probe;
 }
@@ -1822,11 +1754,8 @@ int HipOrder::sort(int s, int target)
     return RT_OK;
 }
 
-/* The trace kernel of part `part` of a launch.
- * Persistent launches.  Queue position q of part p is entry q*parts + p of the (longest chain first) tile order, so the parts are
- * disjoint and equally heavy.  Each kernel is given as many single-wave workgroups as the chip keeps resident, never more than it has
- * work items: its first `grid` positions are taken by blockIdx, the rest through the part's atomic queue, which counts monotonically
- * across launches (this launch's positions start at tileQueueBase).
+/* The trace kernel of part `part` of a launch: persistent waves over (tile, frame group) items, their count, grid and tile-queue
+ * bookkeeping from rt_plan::plan_part.
  * Two parts on two streams for a single frame while the context runs on its own stream: a kernel ends with a drain phase as long as one
  * pixel's serial chain, during which waves retire one by one; the other stream's kernel — different pixels, no dependence — picks up
  * every slot that frees.  With a caller-provided stream the caller's stream order is the contract: one kernel on that stream. */
@@ -1835,56 +1764,39 @@ int HipOrder::trace(int s, int p, int parts)
     KArgs& a = job->a;
     const LaunchPlan& plan = job->plan;
     const int nFrames = job->nFrames;
-    const bool staged = nFrames > 1;
-    const int partTiles = (job->tiles - p + parts - 1) / parts;
+    rt_plan::Work w;
+    w.tiles = job->tiles;
+    w.nFrames = nFrames;
+    w.flat = ctx->flatScene;
+    w.spp = ctx->params.numRaysPerPixel;
+    w.frameGroupOverride = ctx->frameGroupOverride;
+    w.gridOverride = ctx->gridOverride;
+    w.residentGroups = plan.resident;
+    w.wavesPerGroup = plan.shape.wavesPerGroup;
+    const rt_plan::PartPlan pp = rt_plan::plan_part(w, p, parts, ctx->tileQueueNext[s]);
     a.tileOrder = ctx->order.orderValid ? ctx->dTileOrder[ctx->order.orderCur] : nullptr; /* (a sort of this launch may just have written it) */
-    /* frames per item: 1 = the most items and the shortest tail.  The FLAT scenes' per-frame chains are short and uniform; there one
-     * pixel set-up per group of frames is worth 7 % (config 2: 0.765 -> 0.710 ms/frame at groups of 4) as long as every resident wave
-     * still gets >= 8 items; fewer items than that, or groups of 8+, lose it to the tail again, and the BVH scenes gain nothing
-     * measurable (profiles/r02_frame_group_sweep.txt; their kernel variants are compiled without groups). */
-    int group = 1;
-    if (staged && ctx->flatScene && ctx->params.numRaysPerPixel < 65536) {
-        if (ctx->frameGroupOverride > 0) group = ctx->frameGroupOverride;
-        else
-            while (group < 4 && 2 * group <= nFrames && (long long)partTiles * ((nFrames + 2 * group - 1) / (2 * group)) >= 8 * plan.resident * plan.wavesPerGroup) group *= 2;
-        if (group > nFrames) group = nFrames;
-    }
-    a.frameGroup = group;
-    a.frameGroupShift = 0;
-    while ((2 << a.frameGroupShift) <= group) a.frameGroupShift++;
-    a.frameGroups = staged ? (nFrames + group - 1) / group : 1;
-    const long long items = (long long)partTiles * a.frameGroups;
-    /* the grid: workgroups of wavesPerGroup persistent waves each — as many as the chip keeps resident, never more waves than there
-     * are items (rounded up to whole workgroups: a wave without an item of its own goes to the queue, finds it empty and ends) */
-    const int wpb = plan.wavesPerGroup;
-    long long wantWaves = plan.resident * wpb < items ? plan.resident * wpb : items;
-    if (ctx->gridOverride > 0) wantWaves = ctx->gridOverride < items ? ctx->gridOverride : items;
-    const int grid = (int)((wantWaves + wpb - 1) / wpb);
-    const unsigned long long gridWaves = (unsigned long long)grid * wpb;
-    const unsigned long long byIndex = gridWaves < (unsigned long long)items ? gridWaves : (unsigned long long)items; /* positions taken by wave index */
-    a.launchTiles = partTiles;
-    a.launchItems = (int)items;
+    a.frameGroup = pp.frameGroup;
+    a.frameGroupShift = pp.frameGroupShift;
+    a.frameGroups = pp.frameGroups;
+    a.launchTiles = pp.partTiles;
+    a.launchItems = (int)pp.items;
     a.orderOffset = p;
     a.orderStride = parts;
-    /* One kernel alone: all its workgroups become resident at once, the first `grid` positions go by blockIdx and only the rest
-     * through the queue.  Two kernels sharing the chip: workgroups are dispatched as slots free up, possibly late, so every
-     * position — the longest chains first — comes from the queue. */
-    a.queueStart = parts == 2 ? 1 : 0;
-    if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch variant=%d part=%d/%d tiles=%d grid=%d x %d waves perCU=%d lds=%zu\n", plan.variant, p, parts, partTiles, grid, wpb, ctx->occPerCU[plan.variant], plan.ldsBytes);
+    a.queueStart = pp.queueStart;
+    if (ctx->verbose) fprintf(stderr, "[raytrace_hip] launch variant=%d part=%d/%d tiles=%d grid=%d x %d waves perCU=%d lds=%zu\n", plan.shape.variant, p, parts, pp.partTiles, pp.grid, plan.shape.wavesPerGroup, ctx->occPerCU[plan.shape.variant], plan.shape.ldsBytes);
     /* the stream's pixel-record slot and tile-queue counter */
     hipStream_t st = stream(s);
     a.pxCold = (float4*)((char*)ctx->dPxCold + (size_t)s * ctx->pxColdWaves * RT_COLD_STRIDE_BYTES);
     a.tileQueue = ctx->dTileQueue + s;
-    a.tileQueueBase = ctx->tileQueueNext[s] - (a.queueStart ? 0ull : byIndex);
+    a.tileQueueBase = pp.tileQueueBase;
     RtContext::Tuner::Probe* probe = job->probe;
-    const int fuseSlot = staged ? mark_fused_launch_begin(ctx, st) : -1;
+    const int fuseSlot = nFrames > 1 ? mark_fused_launch_begin(ctx, st) : -1;
     if (probe) hipEventRecord(probe->start, st);
-    hipLaunchKernelGGL(parts == 2 ? plan.kernHalf : plan.kern, dim3(grid), dim3(plan.blockThreads), plan.ldsBytes, st, a);
+    hipLaunchKernelGGL(parts == 2 ? plan.kernHalf : plan.kern, dim3(pp.grid), dim3(plan.shape.blockThreads), plan.shape.ldsBytes, st, a);
     if (probe) { hipEventRecord(probe->stop, st); probe->live = true; }
     HIP_TRY(ctx, hipGetLastError()); /* a refused launch ran no wave: the device counter did not move */
     mark_fused_launch_end(ctx, fuseSlot, st, nFrames);
-    /* every position not taken by wave index is one successful fetch, and each of the grid's waves overshoots once */
-    ctx->tileQueueNext[s] += (unsigned long long)items - (a.queueStart ? 0ull : byIndex) + gridWaves;
+    ctx->tileQueueNext[s] = pp.queueNext;
     return RT_OK;
 }
 
@@ -1906,8 +1818,7 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
     LaunchPlan plan;
-    bool many = false;
-    int rc = choose_variant(ctx, a, plan, &many);
+    int rc = choose_variant(ctx, a, plan);
     if (rc) return rc;
     if ((rc = prepare_records(ctx, plan))) return rc;
     if ((rc = prepare_tile_order(ctx, a, tiles))) return rc;
@@ -1921,7 +1832,7 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
      * one stream, profiles/r06_groups_and_streams.txt).  The BVH variants' group launches therefore stay on ONE stream, one kernel per launch. */
     rt_order::Shape shape;
     shape.frames = nFrames;
-    shape.singleWave = plan.wavesPerGroup == 1;
+    shape.singleWave = plan.shape.wavesPerGroup == 1;
     shape.tiles = tiles;
     const rt_order::Placement pl = ctx->order.place(shape);
     const size_t nPix = (size_t)ctx->localRows * ctx->W;

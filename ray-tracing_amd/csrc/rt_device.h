@@ -27,21 +27,11 @@
 
 #include <stdint.h>
 
-#define RT_WAVE 64
+#include "rt_launch_plan.h" /* RT_WAVE, RT_PIXEL_FIELDS, the workgroup maxima, the chain pool's sizes, RT_MIN_WAVES_PER_SIMD* */
+
 #define RT_STACK_DEPTH 34            /* >= RT_MAX_BVH_DEPTH + 2 */
 #define RT_COUNTER_SLOTS 1024        /* counters are spread over slots to avoid same-address atomics */
-#define RT_PIXEL_FIELDS 4
 #define RT_N_PHASES 12
-#define RT_MAX_WAVES_PER_GROUP 12      /* the BVH trace kernels' workgroups: up to 12 waves share one LDS top-of-tree cache (rt_kernels.h) */
-/* the FLAT trace kernel's workgroups (round 6): up to 16 waves share one LDS CHAIN POOL (rt_kernels.h, pool_exchange): two queues (chains
- * waiting for the sky phase / for the shade phase) of RT_POOL_CELLS cells each (a power of two; 32 measured 10 % slower than 64 on the headline
- * scene, 128 the same as 64: profiles/r06_chain_pool.txt); a cell = RT_POOL_QUADS x 16 bytes of chain state.
- * LDS of a workgroup: [header: RT_POOL_HEADER_DWORDS][seq: 2 x RT_POOL_CELLS dwords][payload: 2 x RT_POOL_QUADS x RT_POOL_CELLS x 16 B][wave regions] */
-#define RT_MAX_WAVES_PER_GROUP_FLAT 16
-#define RT_POOL_CELLS 64u
-#define RT_POOL_QUADS 8u
-#define RT_POOL_HEADER_DWORDS 16u
-#define RT_POOL_DWORDS (RT_POOL_HEADER_DWORDS + 2u * RT_POOL_CELLS + 2u * RT_POOL_QUADS * RT_POOL_CELLS * 4u)
 /* bytes of a wave's record in KArgs::pxCold: two float4 per lane (+ the traversal stack in the RT_GLOBAL_STACK experiment) */
 #define RT_COLD_STRIDE_BYTES (2 * RT_WAVE * 16)
 #define RT_COUNTER_FIELDS (8 + 2 * RT_N_PHASES + 4) /* ... + hot-cache steps, node-uniform steps (>= 48 lanes, >= 3/4 of the active lanes) */
@@ -72,7 +62,7 @@ struct DTriN {
     float n[9];
 };
 /* the kernels address these records with shifted 32-bit byte offsets (rt_kernels.h: unit << 4) */
-static_assert(sizeof(DPair) == 64 && sizeof(DTri) == 48 && sizeof(DTriN) == 36, "rt_kernels.h hard-codes the record sizes");
+static_assert(sizeof(DPair) == RT_PAIR_BYTES && sizeof(DTri) == 48 && sizeof(DTriN) == 36, "rt_kernels.h hard-codes the record sizes");
 struct DModel {
     float w2l[12]; /* row r: m[r], m[4+r], m[8+r], m[12+r] of worldToLocal */
     float l2w[12];

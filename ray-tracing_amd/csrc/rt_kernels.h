@@ -40,18 +40,7 @@
 #define RT_SUSPEND_NUM 3
 #define RT_SUSPEND_DEN 8
 #endif
-/* waves per SIMD the register allocator must leave room for (launch_bounds 2nd argument).  Built without the SLP
- * vectoriser (Makefile) the BVH variants need 83 VGPRs: 6 waves = 80 VGPRs costs no spill and is worth 2–7 % per frame
- * (7 waves: 30 spilled dwords, slower); the FLAT variant fits 8 waves = 64 VGPRs (−9 % on config 2). */
-#ifndef RT_MIN_WAVES_PER_SIMD
-#define RT_MIN_WAVES_PER_SIMD 6
-#endif
-#ifndef RT_MIN_WAVES_PER_SIMD_MANY
-#define RT_MIN_WAVES_PER_SIMD_MANY RT_MIN_WAVES_PER_SIMD /* the > 64-model instantiation (measured at 5 as well: see DESIGN.md §4.12) */
-#endif
-#ifndef RT_MIN_WAVES_PER_SIMD_FLAT
-#define RT_MIN_WAVES_PER_SIMD_FLAT 8
-#endif
+/* (waves per SIMD of the launch bounds, RT_MIN_WAVES_PER_SIMD*: rt_launch_plan.h, which the host's launch rules share) */
 /* inner steps per vote won by phase B (lanes that reach a leaf or run out wait for the next vote) */
 #ifndef RT_INNER_BURST
 #define RT_INNER_BURST 3

@@ -6,12 +6,15 @@
 //   run <ops> [options]          one sequence: per-op step lists, then VIOLATION / ORDERED lines
 //   random <seed> <n> [options]  n seeded random sequences: the first violating one, or "clean n"
 //   shortest <len> <alphabet> [options]  every sequence over the alphabet up to len ops, shortest first: the first violating one
-// Ops (space separated): f = a single frame; F<n><k> = a launch of n frames, k = p pooled, g group, s single-wave (1 <= n <= 64);
+// Ops (space separated): f = a single frame; F<n><k> = a launch of n frames, k = p pooled, g group, s single-wave (1 <= n <= 64): the
+// workgroup shape comes from rt_launch_plan.h (launch_shape) for a 1080p FLAT scene with the chain pool / a BVH scene with a top-of-tree
+// cache / a FLAT scene without the pool;
 // w = non-render work (upload, reset, read-back); r = resize; c / o = switch to a caller's stream / back to the own stream.
 // Options: two=0 (RT_TWO_STREAMS=0), lpt=0, alt=0 (RT_ALTERNATE=0), slab1=0 (the second staging slab does not fit),
 // slabs=0 (no slab fits), drop=<event> (the backend drops that event's waits), steady=<k> (fused launches k, k+1, ... and their
 // successors: the trace kernels of two consecutive ones on different streams must not be ordered).
 #include "../ray-tracing_amd/csrc/rt_launch_order.h"
+#include "../ray-tracing_amd/csrc/rt_launch_plan.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -45,6 +48,20 @@ struct Node {
     std::vector<Access> acc;
     std::string what;
 };
+
+static const int kTiles = 240 * 135;  // 1920 x 1080
+
+static bool single_wave(char kind, int nFrames)
+{
+    rt_plan::SceneShape sc;
+    sc.flat = kind != 'g';
+    sc.stackEntries = sc.flat ? 0 : 20;
+    sc.hotUnits = sc.flat ? 0u : 448u * 4u;
+    sc.wavesPerGroup = RT_MAX_WAVES_PER_GROUP;
+    sc.poolCells = kind == 'p' ? (int)RT_POOL_CELLS : 0;
+    sc.poolWaves = RT_MAX_WAVES_PER_GROUP_FLAT;
+    return rt_plan::launch_shape(sc, kTiles, nFrames).wavesPerGroup == 1;
+}
 
 struct Options {
     bool two = true, lpt = true, alt = true, slab1 = true, slabs = true;
@@ -167,8 +184,8 @@ struct Sim final : Backend {
         }
         Shape shape;
         shape.frames = nFrames;
-        shape.singleWave = kind == 's';
-        shape.tiles = 64;
+        shape.singleWave = single_wave(kind, nFrames);
+        shape.tiles = kTiles;
         const Placement p = order.place(shape);
         if (p.staged) {  // prepare_staging
             if (!stagingUnavailable && !slab[p.lane]) {
