@@ -205,6 +205,34 @@ static hipStream_t joined(RtContext* ctx)
     return ctx->stream;
 }
 
+/* The watchdog word: both watchdogs (rt_kernels.h, traverse and pool_exchange) add to word 7 of counter slot 0.  A set word
+ * means that walks were cut short or chains dropped, i.e. the accumulated image and the frames rendered since the word was
+ * last cleared are wrong.  rt_reset_counters leaves it alone; only rt_reset_accumulation, rt_write_accumulated and rt_resize
+ * clear it — stream-ordered behind every launch that could still raise it. */
+static const size_t kWatchdogWord = 7;
+
+static int clear_watchdog(RtContext* ctx)
+{
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dCounters + kWatchdogWord, 0, sizeof(unsigned long long), joined(ctx)));
+    return RT_OK;
+}
+
+static int watchdog_failure(RtContext* report, const char* call, unsigned long long fired)
+{
+    return fail(report, RT_ERR_HIP, "%s: a kernel watchdog fired %llu times since the last rt_reset_accumulation / rt_write_accumulated / rt_resize: "
+                "walks were cut short or chains dropped, the image is not valid (rt_reset_accumulation clears this)", call, fired);
+}
+
+/* Called by every path that hands pixels to a caller, AFTER the synchronise it already performs (8 bytes read back; never on
+ * the render path).  `report` receives the message (a multi-context reports through its context 0). */
+static int check_watchdog(RtContext* ctx, RtContext* report, const char* call)
+{
+    unsigned long long fired = 0;
+    const hipError_t e = hipMemcpy(&fired, ctx->dCounters + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(report, RT_ERR_HIP, "%s: reading the watchdog word: %s", call, hipGetErrorString(e));
+    return fired ? watchdog_failure(report, call, fired) : RT_OK;
+}
+
 static int local_rows_for(int H, int stripRows, int partIndex, int partCount)
 {
     int rows = 0;
@@ -445,6 +473,7 @@ int rt_resize(RtContext* ctx, int width, int height)
         HIP_TRY(ctx, hipMemsetAsync(ctx->ownFrame, 0, bytes, joined(ctx)));
         HIP_TRY(ctx, hipMemsetAsync(ctx->ownAccum, 0, bytes, joined(ctx)));
     }
+    if (int rc = clear_watchdog(ctx)) return rc; /* new targets: nothing rendered into them yet */
     ctx->boundFrame = ctx->boundAccum = nullptr;
     ctx->orderTiles = 0; /* tile costs belong to the old geometry */
     for (int i = 0; i < 2; i++)
@@ -1416,6 +1445,7 @@ int rt_reset_accumulation(RtContext* ctx)
         hipLaunchKernelGGL(rtk::rt_reset_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (float4*)accum, n);
         HIP_TRY(ctx, hipGetLastError());
     }
+    if (int rc = clear_watchdog(ctx)) return rc;
     ctx->frame = 1; /* RCM:71 */
     return RT_OK;
 }
@@ -1989,6 +2019,7 @@ static int read_target(RtContext* ctx, const float* src, float* rgba, size_t byt
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
+    if (int rc = check_watchdog(ctx, ctx, "rt_read")) return rc;
     if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, src, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -2042,6 +2073,7 @@ int rt_display(RtContext* ctx, int frame, int use_accumulated, float* rgba, size
     hipLaunchKernelGGL(rtk::rt_display_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (const float4*)src, tmp, n, frame);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(joined(ctx));
+    if (e == hipSuccess && (rc = check_watchdog(ctx, ctx, "rt_display"))) return rc;
     if (e == hipSuccess) e = hipMemcpy(rgba, tmp, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_display: %s", hipGetErrorString(e));
     return RT_OK;
@@ -2063,6 +2095,7 @@ int rt_display_srgb8(RtContext* ctx, int frame, int use_accumulated, int flip_y,
     hipLaunchKernelGGL(rtk::rt_display_srgb8_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (const float4*)src, tmp, ctx->W, ctx->localRows, frame, flip_y);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(joined(ctx));
+    if (e == hipSuccess && (rc = check_watchdog(ctx, ctx, "rt_display_srgb8"))) return rc;
     if (e == hipSuccess) e = hipMemcpy(rgba8, tmp, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_display_srgb8: %s", hipGetErrorString(e));
     return RT_OK;
@@ -2077,7 +2110,7 @@ int rt_write_accumulated(RtContext* ctx, const float* rgba, size_t bytes)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     if (bytes) HIP_TRY(ctx, hipMemcpy(ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum, rgba, bytes, hipMemcpyHostToDevice));
-    return RT_OK;
+    return clear_watchdog(ctx); /* the accumulated image is the caller's checkpoint now */
 }
 
 int rt_enable_stats(RtContext* ctx, int enabled)
@@ -2096,8 +2129,11 @@ int rt_reset_counters(RtContext* ctx)
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
     /* stream-ordered: the next launch on this stream starts after the fill (a null-stream hipMemset is not ordered
-     * against the non-blocking render streams and may land after the next kernel's first waves have counted) */
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dCounters, 0, sizeof(unsigned long long) * RT_COUNTER_SLOTS * RT_COUNTER_FIELDS, joined(ctx)));
+     * against the non-blocking render streams and may land after the next kernel's first waves have counted).
+     * Every word but the watchdog word: the images it condemns are still in the targets (clear_watchdog) */
+    const size_t words = (size_t)RT_COUNTER_SLOTS * RT_COUNTER_FIELDS;
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dCounters, 0, sizeof(unsigned long long) * kWatchdogWord, joined(ctx)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dCounters + kWatchdogWord + 1, 0, sizeof(unsigned long long) * (words - kWatchdogWord - 1), joined(ctx)));
     ctx->pixelFrames = 0;
     ctx->gpuMs = 0;
     return RT_OK;
@@ -2124,9 +2160,9 @@ int rt_get_counters(RtContext* ctx, RtCounters* out)
     out->modelVisits = sum[5];
     out->pixelFrames = ctx->pixelFrames;
     out->gpuMs = ctx->gpuMs;
-    /* slot 7 = the watchdogs (rt_kernels.h): traverse — a wave ended its lanes' walks because no validated scene needs that many steps; pool_exchange — a wave
-     * gave up waiting for a cell of the FLAT variant's chain pool */
-    if (h[7]) return fail(ctx, RT_ERR_HIP, "a kernel watchdog fired %llu times: a traversal did not end (scene validation has a hole, or device memory is corrupt) or, in a scene without trees, a cell of the chain pool was never handed over; the images since the last rt_reset_counters are not valid", h[7]);
+    /* word 7 = the watchdogs (rt_kernels.h): traverse — a wave ended its lanes' walks because no validated scene needs that many steps; pool_exchange — a wave
+     * gave up waiting for a cell of the FLAT variant's chain pool.  Not cleared by rt_reset_counters (clear_watchdog) */
+    if (h[kWatchdogWord]) return fail(ctx, RT_ERR_HIP, "a kernel watchdog fired %llu times: a traversal did not end (scene validation has a hole, or device memory is corrupt) or, in a scene without trees, a cell of the chain pool was never handed over; the images since the last rt_reset_accumulation / rt_write_accumulated / rt_resize are not valid", h[kWatchdogWord]);
     return RT_OK;
 }
 
@@ -2414,6 +2450,10 @@ static int multi_gather(RtMulti* m, float* rgba, size_t bytes, bool accumulated)
         HIP_TRY(c, hipSetDevice(c->device));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         flush_timer(c);
+        if ((rc = check_watchdog(c, c0, "rt_gather"))) { /* the later contexts' copies still write into m->pinned */
+            multi_drain(m);
+            return rc;
+        }
         /* packed local rows -> their global rows; a strip's rows are contiguous in both */
         for (int l = 0; l < rows;) {
             const int g = rt_local_to_global_row(c, l);
@@ -2469,6 +2509,8 @@ static int multi_gather_device(RtMulti* m, int root, void* d_rgba, size_t bytes,
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         flush_timer(c);
     }
+    for (RtContext* c : m->ctx) /* after every copy into the caller's buffer has completed */
+        if (c->localRows && (rc = check_watchdog(c, c0, "rt_gather_*_to_device"))) return rc;
     m->lastGatherMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return RT_OK;
 }
@@ -2536,30 +2578,36 @@ int rt_gather_rccl(RtContext* ctx, void* nccl_comm, int root, int use_accumulate
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = joined(ctx);
     const float* src = use_accumulated ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame);
-    /* root: one staging area for every rank's packed tile (H rows in all), in the display scratch */
+    /* root: one staging area for every rank's packed tile (H rows in all), then one watchdog word per rank, in the display scratch */
     std::vector<size_t> rowOff(world + 1, 0);
     for (int r = 0; r < world; r++) rowOff[r + 1] = rowOff[r] + (size_t)local_rows_for(H, ctx->stripRows, r, world);
+    const size_t tileBytes = rowOff[world] * (size_t)W * 16;
     char* staging = nullptr;
+    unsigned long long* flags = nullptr;
     if (isRoot) {
         void* p = nullptr;
-        const int rc = display_scratch(ctx, rowOff[world] * (size_t)W * 16, &p);
+        const int rc = display_scratch(ctx, tileBytes + (size_t)world * sizeof(unsigned long long), &p);
         if (rc) return rc;
         staging = (char*)p;
+        flags = (unsigned long long*)(staging + tileBytes);
     }
     auto check = [&](int e, const char* what) -> int {
         if (e == 0) return RT_OK;
         return fail(ctx, RT_ERR_HIP, "rt_gather_rccl: %s: %s", what, R->GetErrorString ? R->GetErrorString(e) : "RCCL error");
     };
     /* every rank sends its tile to root, root receives from every rank — its own included, so that a one-rank communicator runs the
-     * same code; one group: the transfers progress together */
+     * same code; one group: the transfers progress together.  Behind its tile each rank sends its watchdog word (a tripped rank still
+     * takes part in the exchange: the root learns of it and fails) */
     int rc = check(R->GroupStart(), "ncclGroupStart");
     if (rc) return rc;
     int e = 0;
     if (ctx->localRows) e = R->Send(src, (size_t)ctx->localRows * W * 4, /*ncclFloat32*/ 7, root, nccl_comm, st);
+    if (e == 0) e = R->Send(ctx->dCounters + kWatchdogWord, 1, /*ncclUint64*/ 5, root, nccl_comm, st);
     if (isRoot)
         for (int r = 0; r < world && e == 0; r++) {
             const size_t rows = rowOff[r + 1] - rowOff[r];
             if (rows) e = R->Recv(staging + rowOff[r] * (size_t)W * 16, rows * W * 4, 7, r, nccl_comm, st);
+            if (e == 0) e = R->Recv(flags + r, 1, 5, r, nccl_comm, st);
         }
     const int eEnd = R->GroupEnd();
     if ((rc = check(e, "ncclSend / ncclRecv"))) return rc;
@@ -2577,6 +2625,17 @@ int rt_gather_rccl(RtContext* ctx, void* nccl_comm, int root, int use_accumulate
         }
     HIP_TRY(ctx, hipStreamSynchronize(st));
     flush_timer(ctx);
+    if ((rc = check_watchdog(ctx, ctx, "rt_gather_rccl"))) return rc;
+    if (isRoot) {
+        std::vector<unsigned long long> fired(world);
+        HIP_TRY(ctx, hipMemcpy(fired.data(), flags, (size_t)world * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        for (int r = 0; r < world; r++)
+            if (fired[r]) {
+                char what[64];
+                snprintf(what, sizeof(what), "rt_gather_rccl (rank %d of %d)", r, world);
+                return watchdog_failure(ctx, what, fired[r]);
+            }
+    }
     if (badDst) return fail(ctx, RT_ERR_INVALID_ARG, "rt_gather_rccl: bytes %zu != H*W*16 = %zu (the tiles were received and dropped)", bytes, (size_t)W * H * 16);
     return RT_OK;
 }
@@ -2589,10 +2648,11 @@ int rt_multi_get_counters(RtMulti* m, RtCounters* out)
         int rc = multi_flush_all(m);
         if (rc) return rc;
     }
-    for (RtContext* c : m->ctx) {
+    for (size_t i = 0; i < m->ctx.size(); i++) {
+        RtContext* c = m->ctx[i];
         RtCounters k;
         int rc = rt_get_counters(c, &k);
-        if (rc != RT_OK) return rc;
+        if (rc != RT_OK) return i == 0 ? rc : fail(m->ctx[0], rc, "context %zu: %s", i, c->err); /* read through context 0 */
         out->segments += k.segments; out->innerSteps += k.innerSteps; out->leafSteps += k.leafSteps; out->triTests += k.triTests;
         out->sphereTests += k.sphereTests; out->modelVisits += k.modelVisits; out->pixelFrames += k.pixelFrames;
         if (k.gpuMs > out->gpuMs) out->gpuMs = k.gpuMs;

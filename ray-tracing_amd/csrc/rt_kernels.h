@@ -527,8 +527,8 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
      * — but a traversal that does not end would occupy a shared GPU until the driver resets it, and validation is code like any other.
      * Every iteration of the loop below advances at least one lane by one step, and a lane has at most travSteps steps in a scene
      * (every model's pairs and leaves once): more than 64 x travSteps iterations in ONE call cannot happen on validated buffers.  A wave
-     * that gets there ends its lanes' walks where they are and raises counter slot 7: rt_get_counters / rt_read_* then FAIL (the image
-     * is wrong by then, the device is not lost).  Wave-uniform: one scalar add and compare per vote. */
+     * that gets there ends its lanes' walks where they are and raises word 7 of counter slot 0: every read, display and gather then FAILS
+     * until rt_reset_accumulation / rt_write_accumulated / rt_resize (the image is wrong by then, the device is not lost).  Wave-uniform: one scalar add and compare per vote. */
     uint32_t watchdog = 0;
 #define RT_TRAV_VOTE()                                                                                         \
     do {                                                                                                       \
@@ -801,7 +801,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
  *   withdraw: wait until seq[cell] == p + 1 (the writer is done), read the payload, seq[cell] = p + C (release: free for the next lap)
  * Every wait is for a wave that is in the middle of straight-line code of the same kind on an EARLIER position, so waits cannot form a
  * cycle; a wave never exits while it holds a chain or a queue is non-empty (trace_body), so every deposited chain is withdrawn by a
- * live wave.  A wait that exceeds KArgs::poolSpinLimit (65,536) polls raises the watchdog counter (slot 7: rt_get_counters / rt_read_* then FAIL)
+ * live wave.  A wait that exceeds KArgs::poolSpinLimit (65,536) polls raises the watchdog counter (word 7: every read, display and gather then FAILS)
  * and goes on — a broken pool must cost a wrong image that says so, never a hung device.
  * ------------------------------------------------------------------------- */
 #ifndef RT_POOL_ATTEMPTS
