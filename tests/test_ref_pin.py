@@ -369,6 +369,22 @@ def test_row_window_of_the_dispatcher(pkg, orc, ref_spheres):
     assert np.array_equal(bits(imgs[0]), bits(imgs[1]))
 
 
+DEGENERATE = [(1, 1), (1, 13), (13, 1), (2, 2)]
+
+
+@pytest.mark.parametrize("shape", DEGENERATE, ids=[f"{w}x{h}" for w, h in DEGENERATE])
+def test_degenerate_images_equal_the_reference_text(pkg, orc, ref, ref_spheres, shape):
+    """One pixel wide or high: uv = id.xy / (Resolution - 1) = 0 / 0 = NaN (RCC:15) for every pixel, so every primary ray has a NaN
+    focus point and direction, and the float -> uint pixel coordinate (RC:551) converts NaN.  The oracle must give the reference
+    text's bits and counters there too: config 2 (spheres, through the sphere hook) and config 3 (BVH models), 2 x 2 beside them."""
+    w, h = shape
+    for cfg, lib, pair in ((2, ref_spheres, render_pair_with_spheres), (3, ref, render_pair)):
+        out = pair(pkg, orc, lib, lambda: pkg.scenes.get(cfg), w, h, 3, 4)
+        assert_same(out, f"config {cfg} {w}x{h}")
+        acc = out[1][0]
+        assert np.all(np.isfinite(acc)) and np.all(acc[..., 3] == 3), f"config {cfg} {w}x{h}: the reference text's image"
+
+
 @pytest.mark.skipif(not ref_lib.make_ref.available(), reason="needs the reference checkout")
 def test_the_sphere_hook_is_the_only_semantic_rewrite():
     """Take S1's two insertions out of the --spheres translation unit: what is left is the plain translation unit, character for
