@@ -28,6 +28,7 @@
 #include <unordered_map>
 
 #include "rt_kernels.h"
+#include "../../include/rt_cost.h"
 
 #include "rt_layout.h"
 #include "rt_launch_order.h"
@@ -2250,6 +2251,86 @@ int rt_debug_math_eval(RtContext* ctx, int op, const float* x, const float* y, f
     return RT_OK;
 }
 
+/* ---- rt_render_cost (include/rt_cost.h): per-pixel work of one frame ----------------------
+ * The stats build of the trace kernel in its single-wave, unpooled form without the top-of-tree cache (rt_kernels.h, rt_cost_kernel):
+ * one lane owns a pixel from set-up to finish, so the lane's exact counters between the two are that pixel's.  The launch is the
+ * context's in nothing but the scene, the parameters and the stream: its own tile counter, identity tile order, no tile costs, no
+ * pixel-record slot of the render streams, and a counter block of its own — RtCounters and the watchdog word of the context stay as they
+ * are, and a watchdog that fires here fails this call only. */
+int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_cost: frame %d < 1 (the first frame after a reset is 1)", frame);
+    int rc = check_renderable(ctx);
+    if (rc) return rc;
+    const size_t nPix = (size_t)ctx->localRows * ctx->W;
+    if (bytes != nPix * sizeof(RtPixelCost) || (bytes && !out))
+        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_cost: need exactly %zu bytes (%d rows x %d x %zu), got %zu", nPix * sizeof(RtPixelCost), ctx->localRows, ctx->W,
+                    sizeof(RtPixelCost), bytes);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    KArgs a;
+    fill_args(ctx, frame, 1, a);
+    const int tiles = a.tilesX * a.tilesY;
+    if (tiles == 0) return RT_OK;
+    rt_plan::SceneShape sc; /* no cache, no pool: single waves */
+    sc.flat = ctx->flatScene;
+    sc.stats = true;
+    sc.stackEntries = ctx->stackEntries;
+    sc.extWords = ctx->extWords;
+    sc.nChunks = ctx->nChunks;
+    sc.numCUs = ctx->numCUs;
+    const rt_plan::LaunchShape sh = rt_plan::launch_shape(sc, tiles, 1);
+    void (*kern)(const KArgs, uint32_t*) = sh.many ? rtk::rt_cost_kernel<false, true> : ctx->flatScene ? rtk::rt_cost_kernel<true, false> : rtk::rt_cost_kernel<false, false>;
+    a.wavesPerGroup = 1;
+    a.hotUnits = 0;
+    a.poolCells = 0;
+    a.waveLdsDwords = sh.waveLdsDwords;
+    a.stackEntries = ctx->stackEntries;
+    a.suspendNum = ctx->tuner.decided; /* scheduling only: the counts of a ray do not depend on it */
+    if (sh.ldsBytes > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.ldsBytes));
+    int perCU = 0;
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, sh.blockThreads, sh.ldsBytes));
+    rt_plan::Work w;
+    w.tiles = tiles;
+    w.nFrames = 1;
+    w.flat = ctx->flatScene;
+    w.spp = ctx->params.numRaysPerPixel;
+    w.residentGroups = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs;
+    w.wavesPerGroup = 1;
+    const rt_plan::PartPlan pp = rt_plan::plan_part(w, 0, 1, 0ull); /* one kernel, a tile counter that starts at 0 */
+    a.tileOrder = nullptr;
+    a.tileCost = nullptr;
+    a.frameGroup = pp.frameGroup;
+    a.frameGroupShift = pp.frameGroupShift;
+    a.frameGroups = pp.frameGroups;
+    a.launchTiles = pp.partTiles;
+    a.launchItems = (int)pp.items;
+    a.orderOffset = 0;
+    a.orderStride = 1;
+    a.queueStart = pp.queueStart;
+    a.tileQueueBase = pp.tileQueueBase;
+    /* [0, RT_COUNTER_FIELDS): the launch's counter slot (only the watchdog word is written), then the tile counter */
+    DevScratch dWords, dCold, dOut;
+    HIP_TRY(ctx, dWords.alloc(sizeof(unsigned long long) * (RT_COUNTER_FIELDS + 1)));
+    if (!ctx->flatScene) HIP_TRY(ctx, dCold.alloc((size_t)pp.grid * RT_COLD_STRIDE_BYTES)); /* (the FLAT variant keeps its pixel records in LDS) */
+    HIP_TRY(ctx, dOut.alloc(bytes));
+    unsigned long long* const words = (unsigned long long*)dWords.p;
+    a.counters = words;
+    a.tileQueue = words + RT_COUNTER_FIELDS;
+    a.pxCold = (float4*)dCold.p;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned long long) * (RT_COUNTER_FIELDS + 1), st));
+    HIP_TRY(ctx, hipMemsetAsync(dOut.p, 0, bytes, st));
+    hipLaunchKernelGGL(kern, dim3(pp.grid), dim3(sh.blockThreads), sh.ldsBytes, st, a, (uint32_t*)dOut.p);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    unsigned long long fired = 0;
+    HIP_TRY(ctx, hipMemcpy(&fired, words + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if (fired) return watchdog_failure(ctx, "rt_render_cost", fired);
+    HIP_TRY(ctx, hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
 
 /* ------------------------------------------------------------------------------------------
  * Several GPUs from one host process: n contexts with cyclic 8-row strips, gather at readback.

@@ -958,8 +958,12 @@ __device__ __forceinline__ void pool_exchange(const KArgs& a, uint32_t* const po
  * LDS: the per-lane traversal stack, [level][lane], sized by the host to the deepest
  * BVH of the scene (dynamic shared memory).
  * ------------------------------------------------------------------------- */
-template <bool STATS, bool FLAT, bool MANY, bool HOT>
-__device__ __forceinline__ void trace_body(const KArgs& a)
+/* COST (rt_render_cost, include/rt_cost.h): the stats build, single waves without a pool or cache, one frame per launch (nFrames == 1),
+ * so that one lane owns a pixel from set-up to finish.  `cost` holds the pixel's RtPixelCost (eight dwords); the lane keeps its
+ * snapshots there — set-up: segments / inner / leaf / tri of the lane's counters (Stats); camera ray: primary fields minus the
+ * counters, closed (plus the counters) when that ray's first traversal returns; finish: the deltas.  No image is written. */
+template <bool STATS, bool FLAT, bool MANY, bool HOT, bool COST = false>
+__device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost = nullptr)
 {
     /* A workgroup is wavesPerGroup waves (1 for the FLAT variant) that share ONE thing: the LDS copy of the top of the scene's trees
      * (traverse(), phase B).  LDS: [hot cache: hotUnits x 16 B][wave 0: stack, pixel fields, ...][wave 1: ...] ...  After the fill and its
@@ -1061,6 +1065,7 @@ __device__ __forceinline__ void trace_body(const KArgs& a)
                          : ((c).pxCold + (size_t)gw * (RT_COLD_STRIDE_BYTES / 16) + (size_t)lane)) /* [wave][2][lane]: a wave's store covers 1 KB without gaps */
 #define PXU(k) pxu[(k) * RT_WAVE]
 #define PXF(k) pxf[(k) * RT_WAVE]
+#define RT_COST_SLOT(c) (reinterpret_cast<uint4*>(cost) + 2 * (size_t)__float_as_uint(PX_COLD(c)[RT_WAVE].x)) /* COST: the lane's pixel's RtPixelCost */
     uint32_t rng = 0;
 
     bool pathActive = false; /* a ray is waiting to be intersected / is being intersected */
@@ -1131,6 +1136,11 @@ __device__ __forceinline__ void trace_body(const KArgs& a)
                     pathActive = false;
                     inTrav = false;
                     laneDone = false;
+                    if constexpr (COST) { /* the lane's counters at set-up; primary sums and first hit from 0 */
+                        uint4* const o = reinterpret_cast<uint4*>(cost) + 2 * (size_t)((uint32_t)lrow * c.W + (uint32_t)x);
+                        o[0] = make_uint4(segments, st.inner, st.leaf, st.tri);
+                        o[1] = make_uint4(0u, 0u, 0u, 0u);
+                    }
                 }
             }
             const int wanted = __popcll(idle);
@@ -1161,7 +1171,11 @@ __device__ __forceinline__ void trace_body(const KArgs& a)
                     const int frameNow = frameFirst + (grouped ? (int)(sampleWord >> 16) : 0);
                     const size_t pixOff = (size_t)pixLinear * 4;
                     rt_f3 col = rt_v3(PXF(PX_TIX), PXF(PX_TIY), PXF(PX_TIZ)) * c.rcpSpp; /* / NumRaysPerPixel */
-                    if (c.nFrames > 1) {
+                    if constexpr (COST) { /* the pixel's work: the lane's counters now minus at set-up; no image is written */
+                        uint4* const o = reinterpret_cast<uint4*>(cost) + 2 * (size_t)pixLinear;
+                        const uint4 s0 = o[0];
+                        o[0] = make_uint4(segments - s0.x, st.inner - s0.y, st.leaf - s0.z, st.tri - s0.w);
+                    } else if (c.nFrames > 1) {
                         /* one of several frames of this launch: the colour waits in its frame's slab for
                          * rt_accumulate_kernel, which performs RCC:18-23 for the frames in order */
                         const size_t slab = (size_t)(frameNow - c.frame0) * c.stagingStride;
@@ -1238,6 +1252,12 @@ __device__ __forceinline__ void trace_body(const KArgs& a)
                     PXU(PX_SAMPLE) = grouped ? (PXU(PX_SAMPLE) & 0xffff0000u) | (uint32_t)(sample + 1) : (uint32_t)(sample + 1);
                     if (c.maxBounce >= 0) pathActive = true;                /* RC:485: the loop runs for i = 0 */
                     else { PXF(PX_TIX) = PXF(PX_TIX) + 0.0f; PXF(PX_TIY) = PXF(PX_TIY) + 0.0f; PXF(PX_TIZ) = PXF(PX_TIZ) + 0.0f; } /* Trace returned 0 (RC:578) */
+                    if constexpr (COST) if (pathActive) { /* open the camera ray's primary snapshot (closed in rt_shade_phase.inl) */
+                        uint4* const o = RT_COST_SLOT(c) + 1;
+                        uint4 p = *o;
+                        p.x -= st.inner; p.y -= st.leaf; p.z -= st.tri;
+                        *o = p;
+                    }
                 }
             }
             if (pathActive) {
@@ -1261,9 +1281,11 @@ __device__ __forceinline__ void trace_body(const KArgs& a)
     }
 
 #undef RT_SET_POOL
+#undef RT_COST_SLOT
 #undef PXU
 #undef PXF
 #undef PX_COLD
+    if constexpr (COST) return; /* a cost launch leaves the context's counters as they were (its watchdog word is its own) */
     /* exact work counters: one set of atomics per wave, spread over slots */
     uint32_t segSum = wave_sum(segments);
     unsigned long long* slot = a.counters + (size_t)((uint32_t)gw % RT_COUNTER_SLOTS) * RT_COUNTER_FIELDS;
@@ -1315,6 +1337,13 @@ template <bool STATS, bool FLAT, bool MANY = false, bool HOT = false>
 __global__ void __launch_bounds__(HOT ? RT_WAVE * (FLAT ? RT_MAX_WAVES_PER_GROUP_FLAT : RT_MAX_WAVES_PER_GROUP) : RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_trace_half_kernel(const KArgs a)
 {
     trace_body<STATS, FLAT, MANY, HOT>(a);
+}
+/* rt_render_cost: the stats build of the single-wave kernel, one frame, per-pixel work into `cost` (RtPixelCost, 8 dwords per pixel of
+ * this context's rows in rt_read_frame order) instead of colours into the targets */
+template <bool FLAT, bool MANY>
+__global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_cost_kernel(const KArgs a, uint32_t* cost)
+{
+    trace_body<true, FLAT, MANY, false, true>(a, cost);
 }
 
 /* ---- test hooks (rt_debug_*): the same device functions, one ray / value per lane */

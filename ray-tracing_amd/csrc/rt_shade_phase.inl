@@ -5,6 +5,15 @@
  * lane of the wave present.  Not a header: it reads and writes trace_body's locals. */
         if (inTrav && (FLAT || traverse<STATS, true, MANY, HOT>(a, rpos, rdir, stackBase, extBase, h, t, st, hotLds, hotUnits))) {
             inTrav = false;
+            if constexpr (COST) { /* a camera ray's first segment is complete (bounce 0): close its primary snapshot; camera ray 0's outcome */
+                if ((MANY ? extBase[(1 + a.extWords) * RT_WAVE] : (uint32_t)bounce) == 0u) {
+                    uint4* const o = RT_COST_SLOT(cold_args()) + 1;
+                    uint4 p = *o;
+                    p.x += st.inner; p.y += st.leaf; p.z += st.tri;
+                    if (PXU(PX_SAMPLE) == 1u) p.w = h.obj < 0 ? 0u : (a.materials[h.obj].flag == RT_MATERIAL_GLASS ? 2u : 1u);
+                    *o = p;
+                }
+            }
             /* the rest of one iteration of Trace's bounce loop — RC:488-538 */
             bool endPath = false;
             if (h.obj < 0) {

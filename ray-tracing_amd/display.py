@@ -66,6 +66,36 @@ def write_pfm(path, rgb):
         f.write(np.ascontiguousarray(rgb, dtype="<f4").tobytes())
 
 
+# ---------------------------------------------------------------- traversal-cost heatmap
+def cost_heatmap_srgb8(cost, field, scale, flip_y=True):
+    """RGBA8 heatmap of one column of a per-pixel cost image (HipTracer.render_cost / MultiTracer.render_cost: (rows, W, 8) uint32,
+    rows bottom-up) — the role of the reference's declared but unused visMode / debugVisScale uniforms (RC:24-26).
+    `field` is one of hip.COST_FIELDS, or "boxTests" = 2 * innerSteps (the reference's own unit, RC:271).  With t = value / scale
+    in fp32, a pixel with t > 1 is pure red (255, 0, 0, 255), any other is grey g = uint8(t * 255 + 0.5).  flip_y: top row first."""
+    from .hip import COST_FIELDS
+    cost = np.asarray(cost)
+    if cost.ndim != 3 or cost.shape[2] != len(COST_FIELDS):
+        raise ValueError(f"cost image must be (rows, W, {len(COST_FIELDS)}), got {cost.shape}")
+    scale = np.float32(scale)
+    if not scale > 0 or not np.isfinite(scale):
+        raise ValueError(f"scale must be a positive finite number, got {scale}")
+    if field == "boxTests":
+        value = 2 * cost[..., COST_FIELDS.index("innerSteps")].astype(np.uint64)
+    elif field in COST_FIELDS:
+        value = cost[..., COST_FIELDS.index(field)]
+    else:
+        raise ValueError(f"unknown cost field {field!r}: one of {', '.join(COST_FIELDS + ('boxTests',))}")
+    t = value.astype(np.float32) / scale
+    over = t > np.float32(1)
+    g = (np.where(over, np.float32(0), t) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+    out = np.empty(value.shape + (4,), dtype=np.uint8)
+    out[..., 0] = np.where(over, 255, g)
+    out[..., 1] = np.where(over, 0, g)
+    out[..., 2] = np.where(over, 0, g)
+    out[..., 3] = 255
+    return out[::-1].copy() if flip_y else out
+
+
 # ---------------------------------------------------------------- checkpoint / resume
 def save_checkpoint(path, manager):
     """Everything a progressive render needs to continue bit-identically: the accumulation sum,

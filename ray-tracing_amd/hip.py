@@ -29,6 +29,10 @@ ABI_SYMBOLS = [
     "rt_multi_get_counters", "rt_multi_last_gather_ms", "rt_multi_peer_access", "rt_gather_accumulated_to_device", "rt_gather_frame_to_device",
     "rt_gather_rccl",
 ]
+# every symbol include/rt_cost.h declares (kept apart: ABI_SYMBOLS mirrors rt_abi.h alone)
+COST_SYMBOLS = ["rt_render_cost"]
+# RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
+COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
 
 class HipApi(abi.CApi):
@@ -80,6 +84,7 @@ class HipApi(abi.CApi):
         "gather_accumulated_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
         "gather_frame_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
         "gather_rccl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+        "render_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -298,6 +303,16 @@ class MultiTracer:
         self._check(self.api.multi_get_counters(self.h, C.byref(c)))
         return c.as_dict()
 
+    def render_cost(self, frame):
+        """rt_render_cost on every context, assembled into the whole image: (H, W, 8) uint32, rows bottom-up (COST_FIELDS)."""
+        _, h = self.size
+        out = None
+        for i in range(self.api.multi_count(self.h)):
+            ctx = self.context(i)
+            part = scatter_rows(ctx.render_cost(frame), ctx.local_to_global_rows(), h)
+            out = part if out is None else out + part  # (the contexts' rows are disjoint: elsewhere each part is 0)
+        return out
+
 
 class HipTracer(abi.Tracer):
     """An RtContext on one MI355X."""
@@ -367,6 +382,13 @@ class HipTracer(abi.Tracer):
         prof["inner_on_one_node_48_lanes"] = (int(out[2 * n + 2]), 0)
         prof["inner_on_one_node_3_of_4_active"] = (int(out[2 * n + 3]), 0)
         return prof
+
+    def render_cost(self, frame):
+        """rt_render_cost: the work the rays of frame `frame` (>= 1) do per pixel of this context's rows, as a (local_rows, W, 8)
+        uint32 array in rt_read_frame's order; the columns are COST_FIELDS.  Changes no state of the context."""
+        out = np.zeros((max(self.local_rows(), 0), self.width, len(COST_FIELDS)), dtype=np.uint32)
+        self._check(self.api.render_cost(self.h, int(frame), out.ctypes.data if out.size else None, out.nbytes))
+        return out
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -1,0 +1,360 @@
+"""rt_render_cost (include/rt_cost.h) on the GPU: the per-pixel work of a frame's rays, counted by the stats build of the
+trace kernel, against
+
+  1. the oracle's per-pixel work log (oracle_trace_pixel_schedule), every field of every pixel;
+  2. per 8-row strip, the oracle's counters over that row window and the reference text's own `stats` (RC:254 triangle tests,
+     RC:271 box tests / 2) compiled as C++ (oracle/_ref, as tests/test_gpu_ref_pin.py loads it);
+  3. over a whole 1920x1080 frame, the RtCounters delta of the same frame rendered with stats on;
+
+and checks that the call changes nothing a caller can see (images, frame counter, counters, watchdog word), does not depend on
+the device layout or the row partition, and reports its own watchdog without condemning the context's images."""
+import ctypes as C
+import importlib.util
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KEYS = ("segments", "innerSteps", "leafSteps", "triTests")
+
+# ---------------------------------------------------------------- the oracle's work log (oracle/rt_oracle.cpp, sched_tok)
+# 'R' camera ray | 'S' segment | 'A' model entered | 'B' d inner step | 'C' n d leaf with n (capped at 255) tests | 'K' / 'O' / 'G'
+# the segment's outcome (miss, opaque hit, glass hit) | 'E' path ended.  Parsed token by token: d and n are bytes that may equal a tag.
+_R, _S, _A, _B, _C, _E = (ord(c) for c in "RSABCE")
+_OUTCOME = {ord("K"): 0, ord("O"): 1, ord("G"): 2}
+
+
+def cost_of_log(log):
+    """The eight RtPixelCost fields of one pixel from its work log; second value: a leaf's count was capped (255)."""
+    f = [0] * 8
+    capped = False
+    ray, seg, primary, i = -1, 0, False, 0
+    while i < len(log):
+        t = log[i]
+        if t == _R:
+            ray, seg, i = ray + 1, 0, i + 1
+        elif t == _S:
+            f[0] += 1
+            seg += 1
+            primary = seg == 1  # the camera ray's first segment (bounce 0)
+            i += 1
+        elif t == _B:
+            f[1] += 1
+            f[4] += primary
+            i += 2
+        elif t == _C:
+            n = log[i + 1]
+            capped |= n == 255
+            f[2] += 1
+            f[3] += n
+            if primary:
+                f[5] += 1
+                f[6] += n
+            i += 3
+        elif t in _OUTCOME:
+            if primary and ray == 0:
+                f[7] = _OUTCOME[t]
+            primary = False
+            i += 1
+        elif t in (_A, _E):
+            i += 1
+        else:
+            raise ValueError(f"unknown work-log token {t} at byte {i}")
+    return f, capped
+
+
+@pytest.fixture(scope="module")
+def orc_log(orc):
+    """The oracle with oracle_trace_pixel_schedule bound (as tools/sched_trace.py binds it)."""
+    orc._bind("trace_pixel_schedule", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int])
+    return orc
+
+
+def scene_of(pkg, spec):
+    if spec == "crowded70":  # more than 64 models: the two-level filter, candidate masks and bounce count in LDS (MANY)
+        import sys
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import test_gpu_fuzz
+        return test_gpu_fuzz.crowded_scene(pkg, 70, 5)
+    cfg, kw = spec
+    return pkg.scenes.get(cfg, **kw)
+
+
+def manager(pkg, lib, tracer, spec, w, h, tweak=None, seed=1):
+    mgr = scene_of(pkg, spec).make_manager(tracer, lib, w, h)
+    for k, v in (tweak or {}).items():
+        setattr(mgr, k, v)
+    mgr.OnEnable(renderSeed=seed)
+    return mgr
+
+
+def gpu_cost(pkg, api, spec, w, h, frame, tweak=None, seed=1):
+    tr = api.create_tracer(0)
+    try:
+        manager(pkg, api, tr, spec, w, h, tweak, seed)
+        return tr.render_cost(frame)
+    finally:
+        tr.close()
+
+
+def oracle_cost(pkg, orc_log, spec, w, h, frame, tweak=None, seed=1):
+    tr = orc_log.create_tracer(1)
+    try:
+        manager(pkg, orc_log, tr, spec, w, h, tweak, seed)
+        buf = (C.c_uint8 * (1 << 22))()
+        out = np.zeros((h, w, 8), dtype=np.uint32)
+        for y in range(h):
+            for x in range(w):
+                n = orc_log.trace_pixel_schedule(tr.h, x, y, frame, buf, len(buf))
+                assert 0 < n <= len(buf)
+                f, capped = cost_of_log(bytes(buf[:n]))
+                assert not capped, "a leaf with 255+ triangles: the log cannot count it (rule 2 covers such scenes)"
+                out[y, x] = f
+        return out
+    finally:
+        tr.close()
+
+
+def assert_cost_equal(got, want, what):
+    assert got.shape == want.shape and got.dtype == np.uint32, (what, got.shape, want.shape)
+    bad = np.argwhere(np.any(got != want, axis=-1))
+    if len(bad):
+        y, x = bad[0]
+        raise AssertionError(f"{what}: {len(bad)} pixels differ; first at row {y}, column {x}: got {got[y, x].tolist()}, want {want[y, x].tolist()}")
+
+
+# ---------------------------------------------------------------- 1. per pixel, every field, against the oracle's work log
+PIXEL_CASES = [  # name, scene, W, H, frame, manager tweaks
+    ("config1_f1", (1, {}), 64, 36, 1, {}),
+    ("config1_f5_spp3", (1, {}), 64, 36, 5, {"numRaysPerPixel": 3}),
+    ("config2_f1_spp1", (2, {}), 64, 36, 1, {"numRaysPerPixel": 1}),
+    ("config2_f5_nosky", (2, {}), 64, 36, 5, {"useSky": False}),
+    ("config3_f1", (3, {}), 64, 36, 1, {}),
+    ("config3_f5_spp3", (3, {}), 64, 36, 5, {"numRaysPerPixel": 3}),
+    ("config3_lowq_f5", (3, {}), 48, 27, 5, {"bvhQuality": 0}),
+    ("config4s3_f1", (4, {"subdivisions": 3}), 64, 36, 1, {}),
+    ("config4s3_f5_spp1", (4, {"subdivisions": 3}), 64, 36, 5, {"numRaysPerPixel": 1}),
+    ("glassballs_f1", (6, {}), 72, 40, 1, {}),
+    ("glassballs_f5_spp3", (6, {}), 72, 40, 5, {"numRaysPerPixel": 3}),
+    ("crowded70_f1", "crowded70", 64, 36, 1, {}),
+    ("crowded70_f5_spp3_nosky", "crowded70", 64, 36, 5, {"numRaysPerPixel": 3, "useSky": False}),
+]
+
+
+@pytest.mark.parametrize("case", PIXEL_CASES, ids=[c[0] for c in PIXEL_CASES])
+def test_every_pixel_equals_the_oracle_work_log(pkg, api, orc_log, case):
+    name, spec, w, h, frame, tweak = case
+    got = gpu_cost(pkg, api, spec, w, h, frame, tweak)
+    want = oracle_cost(pkg, orc_log, spec, w, h, frame, tweak)
+    assert_cost_equal(got, want, name)
+    assert got[..., 0].min() >= 1  # every pixel traced at least its camera rays
+    if spec != (1, {}):  # (config 1 is spheres only)
+        assert got[..., 3].sum() > 0 and got[..., 6].sum() > 0
+    if spec == (6, {}):
+        assert (got[..., 7] == 2).any() and (got[..., 7] == 1).any()  # glass and opaque first hits
+    if spec == (2, {}) and tweak.get("useSky", True):
+        assert (got[..., 7] == 0).any()  # camera rays that see the sky
+
+
+# ---------------------------------------------------------------- 2. per 8-row strip, against the oracle's counters and the reference text
+_spec = importlib.util.spec_from_file_location("rt_ref_lib", os.path.join(ROOT, "oracle", "ref_lib.py"))
+ref_lib = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(ref_lib)
+
+
+def _checked_ref(pkg, variant, name):
+    """As tests/test_gpu_ref_pin.py: absent = skip, built from other inputs than oracle/REF_EXPECTED.json names = fail."""
+    lib = ref_lib.load(pkg, variant)
+    if lib is None:
+        pytest.skip(f"oracle/_ref/{name} did not travel with the snapshot")
+    why = ref_lib.stale_reason([name])
+    if why:
+        pytest.fail("stale reference library: " + why)
+    return lib
+
+
+def window_counters(pkg, lib, builder, spec, w, h, frame, rows, tweak=None, threads=16):
+    """Counters of frame `frame` rendered by `lib` (oracle or reference text) over the row window [rows[0], rows[1])."""
+    tr = lib.create_tracer(threads)
+    try:
+        mgr = manager(pkg, builder, tr, spec, w, h, tweak)
+        mgr.numAccumulatedFrames = frame
+        mgr.SetShaderParams()
+        lib.set_row_window(tr.h, rows[0], rows[1])
+        tr.reset_counters()
+        tr.render_frame()
+        return tr.counters()
+    finally:
+        tr.close()
+
+
+STRIP_CASES = [  # name, scene, W, H, frame, strips (first rows), tweaks
+    ("config2_1080p", (2, {}), 1920, 1080, 2, (0, 536, 1072), {}),
+    ("config3_1080p", (3, {}), 1920, 1080, 2, (0, 536, 1072), {}),
+    ("config4_1080p", (4, {}), 1920, 1080, 1, (0, 544), {}),
+    ("config3_nobvh_48x27", (3, {}), 48, 27, 3, (0, 8, 16, 24), {"bvhQuality": 2}),  # leaves of 255+ triangles: beyond the log's reach
+]
+
+
+@pytest.mark.parametrize("case", STRIP_CASES, ids=[c[0] for c in STRIP_CASES])
+def test_row_sums_equal_the_oracle_and_the_reference_text(pkg, api, orc, case):
+    name, spec, w, h, frame, strips, tweak = case
+    ref = _checked_ref(pkg, "spheres", "libref_spheres.so") if spec[0] == 2 else _checked_ref(pkg, "", "libref.so")
+    cost = gpu_cost(pkg, api, spec, w, h, frame, tweak)
+    assert cost.shape == (h, w, 8)
+    for r0 in strips:
+        rows = (r0, min(r0 + 8, h))
+        got = cost[rows[0]:rows[1]].reshape(-1, 8).sum(axis=0, dtype=np.uint64)
+        want = window_counters(pkg, orc, orc, spec, w, h, frame, rows, tweak)
+        for k, key in enumerate(KEYS):
+            assert int(got[k]) == want[key], (name, rows, key, int(got[k]), want[key])
+        stats = window_counters(pkg, ref, orc, spec, w, h, frame, rows, tweak)  # the reference text has no BVH builder: the oracle's (same bytes)
+        assert int(got[3]) == stats["triTests"], (name, rows, "RC:254", int(got[3]), stats)
+        assert int(got[1]) == stats["innerSteps"], (name, rows, "RC:271 / 2", int(got[1]), stats)
+        assert int(got[0]) == stats["segments"], (name, rows, int(got[0]), stats)
+
+
+# ---------------------------------------------------------------- 3. the whole image against the stats kernel
+@pytest.mark.parametrize("cfg", [2, 3])
+def test_image_sum_equals_the_stats_frame(pkg, api, cfg):
+    tr = api.create_tracer(0)
+    try:
+        tr.enable_stats(True)
+        mgr = manager(pkg, api, tr, (cfg, {}), 1920, 1080, seed=7)
+        tr.reset_counters()
+        cost = tr.render_cost(1)
+        c0 = tr.counters()
+        assert all(c0[k] == 0 for k in KEYS) and c0["pixelFrames"] == 0  # the cost launch added nothing to the context's counters
+        mgr.RenderFrame()  # frame 1
+        c1 = tr.counters()
+        total = cost.reshape(-1, 8).sum(axis=0, dtype=np.uint64)
+        for k, key in enumerate(KEYS):
+            assert int(total[k]) == c1[key], (cfg, key, int(total[k]), c1[key])
+        assert c1["pixelFrames"] == 1920 * 1080
+    finally:
+        tr.close()
+
+
+# ---------------------------------------------------------------- 4. no side effects
+def test_cost_calls_leave_no_trace(pkg, api, orc):
+    cfg, w, h, seed = (3, {}), 96, 54, 5
+    snaps = []
+    costs = {}
+    for with_cost in (True, False):
+        tr = api.create_tracer(0)
+        tr.enable_stats(True)
+        mgr = manager(pkg, api, tr, cfg, w, h, seed=seed)
+
+        def probe(tag):
+            if with_cost:
+                a = tr.render_cost(tr.frame())  # the frame the context renders next
+                assert np.array_equal(a, tr.render_cost(tr.frame())), tag  # the same frame twice: the same work
+                costs[tr.frame()] = a
+                first = tr.render_cost(1)
+                assert np.array_equal(first, costs.setdefault(1, first)), tag  # and frame 1 whenever it is asked for
+        mgr.RenderFrame()                       # frame 1
+        probe("after rt_render_frame")
+        mgr.RenderFrames(17)                    # frames 2-18: a fused launch, still running when the cost call comes
+        probe("after rt_render_frames(17)")
+        for _ in range(3):                      # frames 19-21: rt_render_frame may hold them back (pending)
+            mgr.RenderFrame()
+        probe("after held-back frames")
+        mgr.RenderFrames(14)                    # frames 22-35: past the tile re-sort at 32 recorded frames
+        probe("across a tile re-sort")
+        snaps.append((tr.read_accumulated(), tr.read_frame(), tr.frame(), tr.counters()))
+        tr.close()
+    (acc_a, frame_a, n_a, c_a), (acc_b, frame_b, n_b, c_b) = snaps
+    assert acc_a.tobytes() == acc_b.tobytes() and frame_a.tobytes() == frame_b.tobytes()
+    assert n_a == n_b == 36 and c_a == c_b
+    assert sorted(costs) == [1, 2, 19, 22, 36]
+    assert all(c[..., 0].min() >= 1 for c in costs.values())
+    ot = orc.create_tracer(16)
+    manager(pkg, orc, ot, cfg, w, h, seed=seed).RenderFrames(35)
+    acc_o = ot.read_accumulated()
+    ot.close()
+    assert acc_a.view(np.uint32).tobytes() == acc_o.view(np.uint32).tobytes(), "accumulated image != oracle"
+
+
+# ---------------------------------------------------------------- 5. layout and partition independence
+def test_layout_does_not_change_the_cost(pkg, api, monkeypatch):
+    out = []
+    for layout in ("dense", "pre,arena,cache"):
+        monkeypatch.setenv("RT_LAYOUT", layout)  # read at rt_create
+        out.append(gpu_cost(pkg, api, (3, {}), 96, 54, 3))
+        monkeypatch.delenv("RT_LAYOUT")
+    assert_cost_equal(out[0], out[1], "RT_LAYOUT dense vs pre,arena,cache")
+
+
+@pytest.mark.parametrize("spec", [(3, {}), (2, {})], ids=["bvh", "flat"])
+def test_partitions_and_multi_context_reassemble_the_image(pkg, api, spec):
+    w, h, frame = 80, 45, 2
+    full = gpu_cost(pkg, api, spec, w, h, frame)
+    parts = 3
+    seen = np.zeros(h, dtype=int)
+    for i in range(parts):
+        tr = api.create_tracer(0)
+        tr.set_partition(8, i, parts)
+        manager(pkg, api, tr, spec, w, h)
+        local = tr.render_cost(frame)
+        rows = tr.local_to_global_rows()
+        assert local.shape == (len(rows), w, 8)
+        assert_cost_equal(local, full[rows], f"partition {i} of {parts}")
+        seen[rows] += 1
+        tr.close()
+    assert (seen == 1).all()
+    mt = api.create_multi_tracer([0, 0, 0])
+    try:
+        manager(pkg, api, mt, spec, w, h)
+        assert_cost_equal(mt.render_cost(frame), full, "MultiTracer.render_cost")
+    finally:
+        mt.close()
+
+
+# ---------------------------------------------------------------- 6. errors and the watchdog
+def test_errors(pkg, api):
+    abi = pkg.abi
+    tr = api.create_tracer(0)
+    try:
+        buf = np.zeros((36, 64, 8), dtype=np.uint32)
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes) == abi.RT_ERR_STATE  # before rt_resize
+        tr.resize(64, 36)
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes) == abi.RT_ERR_STATE  # before rt_upload_scene
+        manager(pkg, api, tr, (3, {}), 64, 36)
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes - 32) == abi.RT_ERR_INVALID_ARG
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes + 32) == abi.RT_ERR_INVALID_ARG
+        assert api.render_cost(tr.h, 1, None, buf.nbytes) == abi.RT_ERR_INVALID_ARG
+        assert api.render_cost(tr.h, 0, buf.ctypes.data, buf.nbytes) == abi.RT_ERR_INVALID_ARG
+        assert api.render_cost(tr.h, -3, buf.ctypes.data, buf.nbytes) == abi.RT_ERR_INVALID_ARG
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes) == abi.RT_OK and buf[..., 0].min() >= 1
+    finally:
+        tr.close()
+    tr = api.create_tracer(0)
+    try:
+        tr.resize(64, 36)
+        mgr = scene_of(pkg, (3, {})).make_manager(tr, api, 64, 36)
+        mgr.InitTexturesAndBuffers()
+        mgr.InitBVH()  # a scene, but no rt_set_params yet
+        assert api.render_cost(tr.h, 1, buf.ctypes.data, buf.nbytes) == abi.RT_ERR_STATE
+    finally:
+        tr.close()
+
+
+def test_watchdog_fails_the_call_not_the_context(pkg, api, monkeypatch):
+    """RT_TRAV_LIMIT=4 (read at rt_upload_scene; the step limit is a software counter, nothing can hang): the cost launch's
+    walks are cut short, the call says so — and the context's counters and images, which no frame of it touched, stay readable."""
+    tr = api.create_tracer(0)
+    try:
+        monkeypatch.setenv("RT_TRAV_LIMIT", "4")
+        manager(pkg, api, tr, (3, {}), 64, 36)
+        monkeypatch.delenv("RT_TRAV_LIMIT")
+        with pytest.raises(pkg.abi.RtError) as e:
+            tr.render_cost(1)
+        assert e.value.status == pkg.abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+        c = tr.counters()  # RT_OK: the context's watchdog word was not set
+        assert c["segments"] == 0
+        assert not tr.read_accumulated().any()
+        assert tr.frame() == 1
+    finally:
+        tr.close()

@@ -5,6 +5,11 @@
     python tools/rt_render.py scene.json --size 960x540 --frames 32 --png out.png --pfm out.pfm --checkpoint ck.npz
     python tools/rt_render.py scene.json --resume ck.npz --frames 32 --png more.png
     python tools/rt_render.py "Assets/Scenes/Glass Balls.unity" --stand-in Icosphere.obj=icosphere:4 --dump-json balls.json
+    python tools/rt_render.py 3 --frames 1 --cost-png cost.png --cost-field boxTests --cost-scale 200
+
+--cost-png writes a heatmap of the work the rays of one frame (--cost-frame, default 1) do per pixel (rt_render_cost,
+include/rt_cost.h): --cost-field is a column of RtPixelCost or boxTests (= 2 x innerSteps, RC:271); a pixel is grey
+value / --cost-scale, or pure red above the scale.
 
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
@@ -26,7 +31,13 @@ def main():
     ap.add_argument("--dump-json", help="write the scene as JSON and exit (no GPU needed)")
     ap.add_argument("--assets", help="Unity Assets directory (for .unity scenes; default: the scene's project)")
     ap.add_argument("--stand-in", action="append", default=[], metavar="NAME=SPEC", help="mesh stand-in for a .unity scene")
+    ap.add_argument("--cost-png", help="heatmap of the per-pixel traversal cost of one frame (rt_render_cost)")
+    ap.add_argument("--cost-field", default="boxTests", help="RtPixelCost column, or boxTests = 2 x innerSteps (default)")
+    ap.add_argument("--cost-scale", type=float, help="value drawn white; above it a pixel is red (required with --cost-png)")
+    ap.add_argument("--cost-frame", type=int, default=1, help="frame (Frame uniform, >= 1) whose rays are counted (default 1)")
     a = ap.parse_args()
+    if a.cost_png and a.cost_scale is None:
+        ap.error("--cost-png needs --cost-scale")
     pkg = g.load_package()
 
     def mesh_spec(text):
@@ -70,6 +81,13 @@ def main():
     if a.png: disp.save_png(a.png)
     if a.pfm: disp.save_pfm(a.pfm)
     if a.checkpoint: pkg.display.save_checkpoint(a.checkpoint, mgr)
+    if a.cost_png:
+        cost = tr.render_cost(a.cost_frame)
+        heat = pkg.display.cost_heatmap_srgb8(cost, a.cost_field, a.cost_scale)
+        pkg.display.write_png(a.cost_png, heat)
+        sums = {f: int(cost[..., i].sum(dtype="u8")) for i, f in enumerate(pkg.hip.COST_FIELDS[:7])}
+        print(json.dumps({"cost_frame": a.cost_frame, "cost_field": a.cost_field, "cost_scale": a.cost_scale, "cost_sums": sums,
+                          "pixels_over_scale": int(((heat[..., 0] == 255) & (heat[..., 1] == 0)).sum())}))
 
 
 if __name__ == "__main__":
