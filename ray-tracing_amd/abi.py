@@ -71,6 +71,21 @@ class RtCounters(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtPixelAov(C.Structure):
+    """include/rt_aov.h: what camera ray 0 of a frame finds in its first segment, one 64-byte record per pixel."""
+    _fields_ = [
+        ("dst", C.c_float), ("normal", C.c_float * 3), ("pos", C.c_float * 3), ("hit", C.c_uint32),
+        ("albedo", C.c_float * 3), ("object", C.c_int32), ("emission", C.c_float * 3), ("triangle", C.c_int32)]
+
+
+# the same 64 bytes as a numpy structured dtype: HipTracer.render_aov returns a (rows, W) array of it
+AOV_DTYPE = np.dtype([
+    ("dst", "<f4"), ("normal", "<f4", (3,)), ("pos", "<f4", (3,)), ("hit", "<u4"),
+    ("albedo", "<f4", (3,)), ("object", "<i4"), ("emission", "<f4", (3,)), ("triangle", "<i4")])
+AOV_HIT_CLASS_MASK = 3   # RtPixelAov.hit bits 0-1: 0 miss, 1 opaque, 2 glass
+AOV_HIT_BACKFACE = 0x100  # bit 8: HitInfo.isBackface
+
+
 class RtBvhStats(C.Structure):
     _fields_ = [
         ("triangleCount", C.c_int32), ("totalNodeCount", C.c_int32), ("leafNodeCount", C.c_int32),

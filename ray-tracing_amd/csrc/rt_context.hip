@@ -29,6 +29,7 @@
 
 #include "rt_kernels.h"
 #include "../../include/rt_cost.h"
+#include "../../include/rt_aov.h"
 
 #include "rt_layout.h"
 #include "rt_launch_order.h"
@@ -83,6 +84,7 @@ struct RtContext {
     unsigned char* dPairs = nullptr; /* pair space */
     unsigned char* dTris = nullptr;  /* triangle space; null when the layout keeps the triangles in the pair space (arena) */
     unsigned char* dNorms = nullptr; /* 12 bytes per unit of the triangle space */
+    uint32_t* dUnitTri = nullptr;    /* uploaded triangle index by the unit its record starts at (rt_layout.h, unitTri); null: the dense layout */
     bool arenaLayout = false;
     RtLayout layout;                 /* RT_LAYOUT at rt_create */
     std::string layoutUsed = "dense";
@@ -173,6 +175,12 @@ struct RtContext {
     HipOrder backend;
     int lastLaunched = 0;            /* frames the last launch_frames call really enqueued (flush_pending rolls back the rest) */
     void* dDisplay = nullptr;  /* scratch of the display pass, kept between calls (grows on demand) */
+    /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand); the pass's own counter
+     * slot (only its watchdog word is ever written); a device pass whose watchdog word has not been read back yet */
+    void* dAovOut = nullptr;
+    size_t aovOutBytes = 0;
+    unsigned long long* dAovWords = nullptr;
+    bool aovUnreported = false;
     size_t displayBytes = 0;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     double gpuMs = 0;
@@ -381,6 +389,7 @@ static void free_scene(RtContext* ctx)
     hipFree(ctx->dPairs); ctx->dPairs = nullptr;
     hipFree(ctx->dTris); ctx->dTris = nullptr;
     hipFree(ctx->dNorms); ctx->dNorms = nullptr;
+    hipFree(ctx->dUnitTri); ctx->dUnitTri = nullptr;
     hipFree(ctx->dBigLeaves); ctx->dBigLeaves = nullptr;
     hipFree(ctx->dFilters); ctx->dFilters = nullptr;
     hipFree(ctx->dChunks); ctx->dChunks = nullptr;
@@ -405,6 +414,8 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dTileOrder[1]);
     hipFree(ctx->dTileKey);
     hipFree(ctx->dDisplay);
+    hipFree(ctx->dAovOut);
+    hipFree(ctx->dAovWords);
     hipFree(ctx->dStaging[0]);
     hipFree(ctx->dStaging[1]);
     hipFree(ctx->dPxCold);
@@ -1217,6 +1228,7 @@ static int commit_scene(RtContext* ctx, const PreparedScene& ps, const RtContext
     if ((rc = commit_vec(ctx, &ctx->dPairs, ps.lay.pairBuf, peer ? &peer->dPairs : nullptr, peer))) return rc;
     if (!ps.lay.arena && (rc = commit_vec(ctx, &ctx->dTris, ps.lay.triBuf, peer ? &peer->dTris : nullptr, peer))) return rc;
     if ((rc = commit_vec(ctx, &ctx->dNorms, ps.lay.normBuf, peer ? &peer->dNorms : nullptr, peer))) return rc;
+    if (ps.lay.unitTri.size() && (rc = commit_vec(ctx, &ctx->dUnitTri, ps.lay.unitTri, peer ? &peer->dUnitTri : nullptr, peer))) return rc;
     if ((rc = commit_vec(ctx, &ctx->dBigLeaves, ps.lay.bigLeaves, peer ? &peer->dBigLeaves : nullptr, peer))) return rc;
     ctx->arenaLayout = ps.lay.arena;
     ctx->layoutUsed = ps.lay.used.name();
@@ -1896,6 +1908,8 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
 
 extern "C" {
 
+static int aov_report(RtContext* ctx, const char* call);
+
 static int check_renderable(RtContext* ctx)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
@@ -1984,7 +1998,7 @@ int rt_synchronize(RtContext* ctx)
     RT_FLUSH(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
-    return RT_OK;
+    return aov_report(ctx, "rt_synchronize"); /* a device AOV pass completes here: so does its watchdog report (no-op otherwise) */
 }
 
 int rt_get_frame(const RtContext* ctx) { return ctx ? ctx->frame : RT_ERR_INVALID_ARG; }
@@ -2329,6 +2343,132 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     HIP_TRY(ctx, hipMemcpy(&fired, words + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
     if (fired) return watchdog_failure(ctx, "rt_render_cost", fired);
     HIP_TRY(ctx, hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* ---- rt_render_aov / rt_render_aov_to_device (include/rt_aov.h): what camera ray 0 of a frame finds, per pixel -------------
+ * One launch of rt_aov_kernel (rt_kernels.h) on the joined main stream — behind every frame already requested, like every use of the
+ * stream that is not a render launch.  The pass is the context's in nothing but the scene, the parameters and the stream: KArgs as for
+ * frame `frame`, a counter slot of its own (ctx->dAovWords; traverse() only ever writes its watchdog word), no render target, no tile
+ * queue, no pixel records.  So RtCounters and the context's watchdog word stay as they are, and a watchdog that fires here fails this
+ * pass only. */
+static int aov_enqueue(RtContext* ctx, int frame, void* dOut, size_t bytes)
+{
+    KArgs a;
+    fill_args(ctx, frame, 1, a);
+    const int tiles = a.tilesX * a.tilesY;
+    if (tiles == 0) return RT_OK;
+    const bool many = ctx->nChunks > 0 && !ctx->flatScene; /* rt_plan::launch_shape's rule */
+    void (*kern)(const KArgs, float4*, const uint32_t*) = many ? rtk::rt_aov_kernel<false, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false> : rtk::rt_aov_kernel<false, false>;
+    /* a wave region of the trace kernel, single waves, no cache, no pool */
+    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
+    a.wavesPerGroup = 1;
+    a.hotUnits = 0;
+    a.poolCells = 0;
+    a.waveLdsDwords = (int)(ldsBytes / sizeof(uint32_t));
+    a.stackEntries = ctx->stackEntries;
+    a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
+    a.frameRender = nullptr;
+    a.accumulated = nullptr;
+    a.tileQueue = nullptr;
+    a.tileOrder = nullptr;
+    a.tileCost = nullptr;
+    a.pxCold = nullptr;
+    a.staging = nullptr;
+    if (!ctx->dAovWords) HIP_TRY(ctx, hipMalloc(&ctx->dAovWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
+    a.counters = ctx->dAovWords;
+    if (ldsBytes > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
+    int perCU = 0;
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, RT_WAVE, ldsBytes));
+    long long grid = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs; /* every wave the device keeps resident; the tiles are strided over them */
+    if (grid > tiles) grid = tiles;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dAovWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (float4*)dOut, (const uint32_t*)ctx->dUnitTri);
+    HIP_TRY(ctx, hipGetLastError());
+    (void)bytes;
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the watchdog word of a device pass that has not been reported yet (8 bytes read back) */
+static int aov_report(RtContext* ctx, const char* call)
+{
+    if (!ctx->aovUnreported) return RT_OK;
+    ctx->aovUnreported = false;
+    unsigned long long fired = 0;
+    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in an rt_render_aov_to_device pass: walks were cut short, its records are not valid "
+                           "(the context's images are not affected)", call, fired);
+    return RT_OK;
+}
+
+static int aov_check_args(RtContext* ctx, const char* call, int frame, const void* out, size_t bytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame %d < 1 (the first frame after a reset is 1)", call, frame);
+    int rc = check_renderable(ctx);
+    if (rc) return rc;
+    const size_t nPix = (size_t)ctx->localRows * ctx->W;
+    if (bytes != nPix * sizeof(RtPixelAov) || (bytes && !out))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x %zu), got %zu%s", call, nPix * sizeof(RtPixelAov), ctx->localRows, ctx->W,
+                    sizeof(RtPixelAov), bytes, out ? "" : " and a null pointer");
+    return RT_OK;
+}
+
+/* a device pass still unreported: synchronise and report it before this call's own pass clears the word */
+static int aov_settle(RtContext* ctx, const char* call)
+{
+    if (!ctx->aovUnreported) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    return aov_report(ctx, call);
+}
+
+int rt_render_aov(RtContext* ctx, int frame, RtPixelAov* out, size_t bytes)
+{
+    int rc = aov_check_args(ctx, "rt_render_aov", frame, out, bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, "rt_render_aov"))) return rc;
+    if (!bytes) return RT_OK;
+    if (ctx->aovOutBytes < bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+        hipFree(ctx->dAovOut);
+        ctx->dAovOut = nullptr;
+        ctx->aovOutBytes = 0;
+        HIP_TRY(ctx, hipMalloc(&ctx->dAovOut, bytes));
+        ctx->aovOutBytes = bytes;
+    }
+    if ((rc = aov_enqueue(ctx, frame, ctx->dAovOut, bytes))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    unsigned long long fired = 0;
+    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if (fired) return watchdog_failure(ctx, "rt_render_aov", fired);
+    HIP_TRY(ctx, hipMemcpy(out, ctx->dAovOut, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes)
+{
+    int rc = aov_check_args(ctx, "rt_render_aov_to_device", frame, d_out, bytes);
+    if (rc) return rc;
+    if ((uintptr_t)d_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_aov_to_device: the records must be 16-byte aligned");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (bytes) { /* the kernel writes through this pointer: it must be device memory of this context's device that holds `bytes` bytes */
+        hipPointerAttribute_t at;
+        void* base = nullptr;
+        size_t size = 0;
+        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device ||
+            hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)d_out) != hipSuccess || (const char*)d_out + bytes > (const char*)base + size) {
+            (void)hipGetLastError();
+            return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_aov_to_device: d_out is not %zu bytes of device memory on device %d", bytes, ctx->device);
+        }
+    }
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, "rt_render_aov_to_device"))) return rc;
+    if (!bytes) return RT_OK;
+    if ((rc = aov_enqueue(ctx, frame, d_out, bytes))) return rc;
+    ctx->aovUnreported = true;
     return RT_OK;
 }
 

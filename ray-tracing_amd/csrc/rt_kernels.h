@@ -1346,6 +1346,99 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     trace_body<true, FLAT, MANY, false, true>(a, cost);
 }
 
+/* rt_render_aov (include/rt_aov.h): what camera ray 0 of frame a.frame0 finds in its first segment, one RtPixelAov (four float4) per pixel
+ * of this context's rows in rt_read_frame order.  Not a flag of trace_body: one segment per pixel has no chain state, no pool and no phases.
+ * One pixel per lane; a wave takes an 8 x 8 tile (lane & 7, lane >> 3, as the refill of trace_body does), so its 64 rays are coherent, and
+ * strides over the context's tiles by the grid.  Single-wave workgroups without the top-of-tree cache; LDS as a wave region of the trace
+ * kernel ([stackEntries][64] traversal stack, the pixel fields' rows unused, then the MANY variant's mask extension), so the host sizes it
+ * with the same rule.  The traversal runs to completion (no suspension).  `unitTri`: uploaded triangle index by the 16-byte unit a
+ * triangle record starts at (rt_layout.h moves the records), null = the dense layout (unit = 3 x index).  Only a.counters + 7 (the
+ * watchdog word of traverse()) is ever written besides `out`: the host points it at a word of this pass's own. */
+template <bool FLAT, bool MANY>
+__global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_aov_kernel(const KArgs a, float4* __restrict__ out, const uint32_t* __restrict__ unitTri)
+{
+    extern __shared__ uint32_t s_lds[];
+    const int lane = (int)threadIdx.x;
+    uint32_t* const stackBase = &s_lds[lane];
+    uint32_t* const extBase = &s_lds[(size_t)(a.stackEntries + RT_PIXEL_FIELDS) * RT_WAVE + lane];
+    const int tiles = a.tilesX * a.tilesY;
+    for (int tile = (int)blockIdx.x; tile < tiles; tile += (int)gridDim.x) {
+        /* wave-uniform: every row of an 8-row tile lies in one strip (stripRows % 8 == 0); cyclic strips: local strip ls is global strip
+         * ls * partCount + partIndex (RT_SET_POOL of trace_body) */
+        const int ty = tile / a.tilesX;
+        const int row0 = ty * 8;
+        const int ls = row0 / a.stripRows;
+        const int x = (tile - ty * a.tilesX) * 8 + (lane & 7);
+        const int lrow = row0 + (lane >> 3);
+        const int y = (ls * a.partCount + a.partIndex) * a.stripRows + (row0 - ls * a.stripRows) + (lane >> 3);
+        if (x < (int)a.W && lrow < a.localRows) {
+            /* RCC:15: id.xy / (Resolution - 1.0) */
+            const float uvx = (float)(uint32_t)x * a.rcpWm1;
+            const float uvy = (float)(uint32_t)y * a.rcpHm1;
+            /* RC:550-556 */
+            const uint32_t pixelCoordX = (uint32_t)(uvx * (float)a.W);
+            const uint32_t pixelCoordY = (uint32_t)(uvy * (float)a.H);
+            const uint32_t pixelIndex = pixelCoordY * a.W + pixelCoordX;
+            uint32_t rng = pixelIndex + (uint32_t)a.frame0 * 719393u + (uint32_t)a.seed; /* RC:552 */
+            const rt_f3 fpl = rt_v3(uvx - 0.5f, uvy - 0.5f, 1.0f) * rt_v3(a.viewParams[0], a.viewParams[1], a.viewParams[2]);
+            float cam[16];
+            for (int k = 0; k < 16; k++) cam[k] = a.cam[k];
+            const rt_f3 focusPoint = rt_mul_point(cam, fpl, 1.0f);
+            /* camera constants — RC:547,557-558 */
+            const rt_f3 camOrigin = rt_mul_point(cam, rt_v3(0.0f, 0.0f, 0.0f), 1.0f);
+            const rt_f3 camRight = rt_v3(cam[0], cam[1], cam[2]);
+            const rt_f3 camUp = rt_v3(cam[4], cam[5], cam[6]);
+            const float invNumPixelsX = a.rcpW; /* x / numPixels.x */
+            /* RC:565-576, rayIndex 0 */
+            rt_f3 rayOrigin;
+            if (a.raygenNoDefocus) { /* defocusStrength == 0: only the two draws of RandomPointInCircle remain (trace_body, PH_RAYGEN) */
+                rt_next_random(&rng);
+                rt_next_random(&rng);
+                rayOrigin = camOrigin;
+            } else {
+                rt_f2 dj = rand_circle(&rng);
+                rayOrigin = camOrigin + camRight * (dj.x * a.defocus * invNumPixelsX) + camUp * (dj.y * a.defocus * invNumPixelsX);
+            }
+            rt_f2 jj = rand_circle(&rng);
+            const rt_f3 jfp = focusPoint + camRight * (jj.x * a.diverge * invNumPixelsX) + camUp * (jj.y * a.diverge * invNumPixelsX);
+            const rt_f3 rpos = rayOrigin;
+            const rt_f3 rdir = rt_normalize(jfp - rayOrigin);
+
+            /* CalculateRayCollision — RC:335-374 */
+            SceneHit h;
+            Trav t;
+            Stats st = {};
+            begin_intersect<false, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
+            if (FLAT) traverse_flat<false>(a, rpos, rdir, h, st);
+            else traverse<false, false, MANY>(a, rpos, rdir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u);
+
+            float4 q0 = make_float4(h.dst, 0.0f, 0.0f, 0.0f), q1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+            float4 q2 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0xffffffffu)), q3 = q2; /* object = triangle = -1 */
+            if (h.obj >= 0) {
+                rt_f3 hpos, normal;
+                resolve_hit(a, rpos, rdir, h, hpos, normal);
+                const DMaterial mat = a.materials[h.obj];
+                const rt_f3 albedo = material_colour(mat, hpos, normal, false);
+                const rt_f3 emitted = rt_v3(mat.emissionCol[0], mat.emissionCol[1], mat.emissionCol[2]) * mat.emissionStrength; /* RC:530 */
+                int tri = -1;
+                if (h.obj >= a.nSpheres) tri = unitTri ? (int)unitTri[h.tri] : h.tri / 3;
+                q0 = make_float4(h.dst, normal.x, normal.y, normal.z);
+                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float((mat.flag == RT_MATERIAL_GLASS ? 2u : 1u) | (h.backface ? 0x100u : 0u)));
+                q2 = make_float4(albedo.x, albedo.y, albedo.z, __uint_as_float((uint32_t)h.obj));
+                q3 = make_float4(emitted.x, emitted.y, emitted.z, __uint_as_float((uint32_t)tri));
+            } else if (a.useSky) {
+                const rt_f3 sky = environment_light(a, rdir); /* RC:490-493 */
+                q2 = make_float4(sky.x, sky.y, sky.z, __uint_as_float(0xffffffffu));
+            }
+            float4* const o = out + 4 * ((size_t)lrow * a.W + (size_t)x); /* lrow < localRows, x < W: inside the rows * W * 64 bytes the host checked */
+            o[0] = q0;
+            o[1] = q1;
+            o[2] = q2;
+            o[3] = q3;
+        }
+    }
+}
+
 /* ---- test hooks (rt_debug_*): the same device functions, one ray / value per lane */
 __global__ void __launch_bounds__(RT_WAVE) rt_debug_intersect_kernel(const KArgs a, const float* origins, const float* dirs, int n, float* out)
 {

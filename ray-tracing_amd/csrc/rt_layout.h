@@ -176,6 +176,9 @@ static inline void make_dtri(const RtTriangle& t, DTri& d, float* n9)
 struct LaidOutScene {
     /* pair space (arena: pairs AND triangles), triangle space (arena: empty — the kernels get the pair space twice), normals */
     PodVec<unsigned char> pairBuf, triBuf, normBuf;
+    /* index of the caller's triangle by the unit its record starts at in the triangle space (other units: unspecified) — what
+     * rt_render_aov reports (include/rt_aov.h).  Empty for the dense layout, where nothing moves: unit = RT_TRI_UNITS x index */
+    PodVec<uint32_t> unitTri;
     bool arena = false;
     std::vector<uint32_t> bigLeaves;
     std::vector<uint32_t> rootCodes; /* per model, final */
@@ -589,7 +592,7 @@ struct LayoutEngine {
         const size_t pairBytes = (size_t)pairCur * RT_UNIT_BYTES, triBytes = (size_t)triCur * RT_UNIT_BYTES;
         const size_t normBytes = (size_t)(arena ? pairCur : triCur) * RT_NORM_BYTES_PER_UNIT;
         if (!out.pairBuf.resize_uninit(pairBytes ? pairBytes : 64) || !out.triBuf.resize_uninit(arena ? 0 : (triBytes ? triBytes : 48)) ||
-            !out.normBuf.resize_uninit(normBytes ? normBytes : 36)) { out.error = "out of host memory"; return false; }
+            !out.normBuf.resize_uninit(normBytes ? normBytes : 36) || !out.unitTri.resize_uninit((size_t)(arena ? pairCur : triCur) + 1)) { out.error = "out of host memory"; return false; }
         auto par_zero = [&](unsigned char* p, size_t n) {
             const size_t blk = (size_t)4 << 20;
             par((int)((n + blk - 1) / blk), [&](int b) { memset(p + (size_t)b * blk, 0, (size_t)(b + 1) * blk < n ? blk : n - (size_t)b * blk); });
@@ -630,6 +633,7 @@ struct LayoutEngine {
                         make_dtri(tris[(size_t)I.triOffset + q.start + t], d, n9);
                         memcpy(triSpace + unit * RT_UNIT_BYTES, &d, sizeof(d));
                         memcpy(out.normBuf.data() + unit * RT_NORM_BYTES_PER_UNIT, n9, sizeof(n9));
+                        out.unitTri.data()[unit] = (uint32_t)((size_t)I.triOffset + q.start + t);
                     }
                 }
             }

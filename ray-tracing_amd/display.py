@@ -96,6 +96,66 @@ def cost_heatmap_srgb8(cost, field, scale, flip_y=True):
     return out[::-1].copy() if flip_y else out
 
 
+# ---------------------------------------------------------------- first-hit feature buffers (AOVs)
+AOV_CHANNELS = ("normal", "albedo", "emission", "depth", "object")
+
+
+def aov_object_colour(obj):
+    """The fixed colour of an object index (int array, >= 0) as three uint8 planes: h = (obj + 1) * 2654435761 mod 2^32
+    (Knuth's multiplicative hash), r, g, b = 64 + (bits 0-7, 8-15, 16-23 of h) * 3 // 4 — never darker than 64, so that no
+    object is taken for a miss."""
+    h = ((np.asarray(obj).astype(np.uint64) + 1) * 2654435761) & 0xffffffff
+    return [(64 + ((h >> s) & 0xff) * 3 // 4).astype(np.uint8) for s in (0, 8, 16)]
+
+
+def aov_srgb8(aov, channel, flip_y=True, depth_range=None):
+    """RGBA8 picture of one channel of an AOV image (HipTracer.render_aov / MultiTracer.render_aov: (rows, W) records of
+    abi.AOV_DTYPE, rows bottom-up).  With q(t) = uint8(clip(t, 0, 1) * 255 + 0.5) in fp32 (NaN counts as 0):
+      normal    q(n * 0.5 + 0.5) per component (a miss, n = 0, is mid grey)
+      albedo    q(albedo)        (a miss shows the sky colour, or black without a sky)
+      emission  q(emission)
+      depth     grey q((dst - lo) / (hi - lo)), lo / hi = depth_range or the least / greatest finite dst among the hits;
+                hi == lo (a constant-depth image) draws every hit as 0; misses are black
+      object    aov_object_colour(object); misses are black
+    Alpha is 255.  flip_y: top row first (what write_png expects)."""
+    aov = np.asarray(aov)
+    if aov.ndim != 2 or aov.dtype.names is None or any(f not in aov.dtype.names for f in ("dst", "normal", "albedo", "emission", "object", "hit")):
+        raise ValueError("aov image must be a (rows, W) array of abi.AOV_DTYPE records")
+    if channel not in AOV_CHANNELS:
+        raise ValueError(f"unknown AOV channel {channel!r}: one of {', '.join(AOV_CHANNELS)}")
+
+    def q(t):
+        t = np.where(np.isnan(t), np.float32(0), t).astype(np.float32)
+        return (np.clip(t, np.float32(0), np.float32(1)) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+    out = np.zeros(aov.shape + (4,), dtype=np.uint8)
+    out[..., 3] = 255
+    hit = (aov["hit"] & 3) != 0
+    if channel == "normal":
+        out[..., :3] = q(aov["normal"] * np.float32(0.5) + np.float32(0.5))
+    elif channel in ("albedo", "emission"):
+        out[..., :3] = q(aov[channel])
+    elif channel == "depth":
+        dst = aov["dst"].astype(np.float32)
+        finite = hit & np.isfinite(dst)
+        if depth_range is not None:
+            lo, hi = np.float32(depth_range[0]), np.float32(depth_range[1])
+        elif finite.any():
+            lo, hi = dst[finite].min(), dst[finite].max()
+        else:
+            lo = hi = np.float32(0)
+        span = hi - lo
+        with np.errstate(invalid="ignore", over="ignore"):
+            t = (np.where(finite, dst, lo) - lo) / span if span > 0 else np.zeros(dst.shape, dtype=np.float32)
+        g = np.where(finite, q(t), 0).astype(np.uint8)
+        out[..., 0] = out[..., 1] = out[..., 2] = g
+    else:
+        obj = aov["object"]
+        r, g, b = aov_object_colour(np.where(obj >= 0, obj, 0))
+        for k, plane in enumerate((r, g, b)):
+            out[..., k] = np.where(obj >= 0, plane, 0)
+    return out[::-1].copy() if flip_y else out
+
+
 # ---------------------------------------------------------------- checkpoint / resume
 def save_checkpoint(path, manager):
     """Everything a progressive render needs to continue bit-identically: the accumulation sum,

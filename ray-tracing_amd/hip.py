@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
 ]
 # every symbol include/rt_cost.h declares (kept apart: ABI_SYMBOLS mirrors rt_abi.h alone)
 COST_SYMBOLS = ["rt_render_cost"]
+# every symbol include/rt_aov.h declares
+AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -85,6 +87,8 @@ class HipApi(abi.CApi):
         "gather_frame_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
         "gather_rccl": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
         "render_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+        "render_aov": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+        "render_aov_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -313,6 +317,15 @@ class MultiTracer:
             out = part if out is None else out + part  # (the contexts' rows are disjoint: elsewhere each part is 0)
         return out
 
+    def render_aov(self, frame):
+        """rt_render_aov on every context, assembled into the whole image: (H, W) records of abi.AOV_DTYPE, rows bottom-up."""
+        w, h = self.size
+        out = np.zeros((h, w), dtype=abi.AOV_DTYPE)
+        for i in range(self.api.multi_count(self.h)):
+            ctx = self.context(i)
+            out[ctx.local_to_global_rows()] = ctx.render_aov(frame)  # (the contexts' rows are disjoint)
+        return out
+
 
 class HipTracer(abi.Tracer):
     """An RtContext on one MI355X."""
@@ -389,6 +402,19 @@ class HipTracer(abi.Tracer):
         out = np.zeros((max(self.local_rows(), 0), self.width, len(COST_FIELDS)), dtype=np.uint32)
         self._check(self.api.render_cost(self.h, int(frame), out.ctypes.data if out.size else None, out.nbytes))
         return out
+
+    def render_aov(self, frame):
+        """rt_render_aov (include/rt_aov.h): what camera ray 0 of frame `frame` (>= 1) hits first, per pixel of this context's rows:
+        a (local_rows, W) array of abi.AOV_DTYPE (dst, normal, pos, hit, albedo, object, emission, triangle) in rt_read_frame's
+        order.  A picked pixel is aov[y, x]["object"].  Changes no state of the context."""
+        out = np.zeros((max(self.local_rows(), 0), self.width), dtype=abi.AOV_DTYPE)
+        self._check(self.api.render_aov(self.h, int(frame), out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def render_aov_to_device(self, frame, ptr, nbytes):
+        """rt_render_aov_to_device: the same records into device memory (e.g. a torch tensor's data_ptr(), local_rows * W * 64 bytes),
+        enqueued on the stream the context renders on; complete after synchronize()."""
+        self._check(self.api.render_aov_to_device(self.h, int(frame), ptr, int(nbytes)))
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -10,6 +10,11 @@
 --cost-png writes a heatmap of the work the rays of one frame (--cost-frame, default 1) do per pixel (rt_render_cost,
 include/rt_cost.h): --cost-field is a column of RtPixelCost or boxTests (= 2 x innerSteps, RC:271); a pixel is grey
 value / --cost-scale, or pure red above the scale.
+    python tools/rt_render.py 3 --frames 1 --aov-png aov --aov-npy aov.npy
+
+--aov-png PREFIX writes PREFIX_normal.png, PREFIX_albedo.png, PREFIX_depth.png and PREFIX_object.png: what camera ray 0 of
+frame --aov-frame (default 1) hits first in every pixel (rt_render_aov, include/rt_aov.h); --aov-npy FILE saves the raw
+records (numpy, abi.AOV_DTYPE, rows bottom-up).
 
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
@@ -35,6 +40,9 @@ def main():
     ap.add_argument("--cost-field", default="boxTests", help="RtPixelCost column, or boxTests = 2 x innerSteps (default)")
     ap.add_argument("--cost-scale", type=float, help="value drawn white; above it a pixel is red (required with --cost-png)")
     ap.add_argument("--cost-frame", type=int, default=1, help="frame (Frame uniform, >= 1) whose rays are counted (default 1)")
+    ap.add_argument("--aov-png", metavar="PREFIX", help="first-hit feature buffers of one frame as PREFIX_{normal,albedo,depth,object}.png (rt_render_aov)")
+    ap.add_argument("--aov-npy", metavar="FILE", help="the raw RtPixelAov records of that frame as a numpy file")
+    ap.add_argument("--aov-frame", type=int, default=1, help="frame (Frame uniform, >= 1) whose camera rays are reported (default 1)")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
@@ -88,6 +96,17 @@ def main():
         sums = {f: int(cost[..., i].sum(dtype="u8")) for i, f in enumerate(pkg.hip.COST_FIELDS[:7])}
         print(json.dumps({"cost_frame": a.cost_frame, "cost_field": a.cost_field, "cost_scale": a.cost_scale, "cost_sums": sums,
                           "pixels_over_scale": int(((heat[..., 0] == 255) & (heat[..., 1] == 0)).sum())}))
+    if a.aov_png or a.aov_npy:
+        aov = tr.render_aov(a.aov_frame)
+        if a.aov_npy:
+            import numpy as np
+            np.save(a.aov_npy, aov)
+        if a.aov_png:
+            for ch in ("normal", "albedo", "depth", "object"):
+                pkg.display.write_png(f"{a.aov_png}_{ch}.png", pkg.display.aov_srgb8(aov, ch))
+        hit = aov["hit"] & 3
+        print(json.dumps({"aov_frame": a.aov_frame, "pixels": int(aov.size), "miss": int((hit == 0).sum()), "opaque": int((hit == 1).sum()),
+                          "glass": int((hit == 2).sum()), "objects_seen": int(len(set(aov["object"][hit != 0].tolist())))}))
 
 
 if __name__ == "__main__":
