@@ -86,6 +86,20 @@ AOV_HIT_CLASS_MASK = 3   # RtPixelAov.hit bits 0-1: 0 miss, 1 opaque, 2 glass
 AOV_HIT_BACKFACE = 0x100  # bit 8: HitInfo.isBackface
 
 
+class RtDenoiseParams(C.Structure):
+    """include/rt_denoise.h: the parameters of the a-trous filter (32 bytes; struct_size is the handshake)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigmaColour", C.c_float), ("sigmaNormal", C.c_float),
+        ("sigmaPlane", C.c_float), ("demodulate", C.c_int32), ("scale", C.c_float), ("reserved", C.c_int32)]
+
+
+# the same 32 bytes as a numpy record
+DENOISE_PARAMS_DTYPE = np.dtype([
+    ("struct_size", "<u4"), ("iterations", "<i4"), ("sigmaColour", "<f4"), ("sigmaNormal", "<f4"),
+    ("sigmaPlane", "<f4"), ("demodulate", "<i4"), ("scale", "<f4"), ("reserved", "<i4")])
+DENOISE_MAX_ITERATIONS = 8
+
+
 class RtBvhStats(C.Structure):
     _fields_ = [
         ("triangleCount", C.c_int32), ("totalNodeCount", C.c_int32), ("leafNodeCount", C.c_int32),

@@ -30,7 +30,10 @@
 #include "rt_kernels.h"
 #include "../../include/rt_cost.h"
 #include "../../include/rt_aov.h"
+#include "../../include/rt_denoise.h"
 
+#include "rt_denoise_launch.h"
+#include "rt_denoise_math.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -181,6 +184,12 @@ struct RtContext {
     size_t aovOutBytes = 0;
     unsigned long long* dAovWords = nullptr;
     bool aovUnreported = false;
+    /* rt_denoise (include/rt_denoise.h): the filter's two colour images and packed guide image, and the AOV records of the two context
+     * calls' internal pass; kept between calls (grow on demand) */
+    void* dDnScratch = nullptr;
+    size_t dnScratchBytes = 0;
+    void* dDnAov = nullptr;
+    size_t dnAovBytes = 0;
     size_t displayBytes = 0;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     double gpuMs = 0;
@@ -416,6 +425,8 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dDisplay);
     hipFree(ctx->dAovOut);
     hipFree(ctx->dAovWords);
+    hipFree(ctx->dDnScratch);
+    hipFree(ctx->dDnAov);
     hipFree(ctx->dStaging[0]);
     hipFree(ctx->dStaging[1]);
     hipFree(ctx->dPxCold);
@@ -2397,8 +2408,8 @@ static int aov_report(RtContext* ctx, const char* call)
     ctx->aovUnreported = false;
     unsigned long long fired = 0;
     HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in an rt_render_aov_to_device pass: walks were cut short, its records are not valid "
-                           "(the context's images are not affected)", call, fired);
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device or rt_denoise_to_device call: walks were "
+                           "cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
     return RT_OK;
 }
 
@@ -2468,6 +2479,192 @@ int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes
     if ((rc = aov_settle(ctx, "rt_render_aov_to_device"))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = aov_enqueue(ctx, frame, d_out, bytes))) return rc;
+    ctx->aovUnreported = true;
+    return RT_OK;
+}
+
+/* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
+ * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main
+ * stream.  The two context calls run the AOV pass of rt_render_aov_to_device into library-owned records first, with that pass's own
+ * watchdog word and its reporting. */
+static int dn_check_params(RtContext* ctx, const char* call, const RtDenoiseParams* p, rt_dn::Job* job)
+{
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: null parameters", call);
+    if (p->struct_size != sizeof(RtDenoiseParams))
+        return fail(ctx, RT_ERR_ABI_MISMATCH, "%s: RtDenoiseParams.struct_size is %u, this library's is %zu", call, p->struct_size, sizeof(RtDenoiseParams));
+    if (p->iterations < 0 || p->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: iterations %d outside 0..%d", call, p->iterations, RT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {p->sigmaColour, p->sigmaNormal, p->sigmaPlane};
+    for (float s : sig)
+        if (!(s > 0.0f) || !rt_dn_finite(s)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: every sigma must be finite and > 0", call);
+    if (!rt_dn_finite(p->scale)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: scale is not finite", call);
+    if (p->reserved != 0) return fail(ctx, RT_ERR_INVALID_ARG, "%s: reserved must be 0", call);
+    job->iterations = p->iterations;
+    job->demodulate = p->demodulate != 0;
+    job->scale = p->scale;
+    job->aC = rt_dn_inv_sq(p->sigmaColour);
+    job->aN = rt_dn_inv_sq(p->sigmaNormal);
+    job->aP = rt_dn_inv_sq(p->sigmaPlane);
+    /* a sigma so small that 1 / sigma^2 (for the colour: times 4^i in the last pass) is infinite would turn the centre tap's e = 0 * inf into NaN */
+    if (!rt_dn_finite(job->aN) || !rt_dn_finite(job->aP) || !rt_dn_finite(rt_dn_colour_scale(job->aC, p->iterations > 0 ? p->iterations - 1 : 0)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: a sigma is too small: 1 / sigma^2 is not finite in fp32", call);
+    return RT_OK;
+}
+
+static int dn_check_whole_image(RtContext* ctx, const char* call)
+{
+    if (ctx->partCount > 1)
+        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; the filter needs the whole image (gather, then rt_denoise_buffers)",
+                    call, ctx->partIndex, ctx->partCount);
+    return RT_OK;
+}
+
+/* `bytes` bytes of 16-byte aligned device memory of the context's device */
+static int dn_check_device_range(RtContext* ctx, const char* call, const char* what, const void* p, size_t bytes)
+{
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is null", call, what);
+    if ((uintptr_t)p & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", call, what);
+    hipPointerAttribute_t at;
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device ||
+        hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess || (const char*)p + bytes > (const char*)base + size) {
+        (void)hipGetLastError();
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is not %zu bytes of device memory on device %d", call, what, bytes, ctx->device);
+    }
+    return RT_OK;
+}
+
+/* the image the two context calls filter */
+static const float* dn_source(const RtContext* ctx, int use_accumulated)
+{
+    return use_accumulated ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame);
+}
+
+static bool dn_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
+
+static int dn_grow(RtContext* ctx, void** buf, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx))); /* a filter still running reads the old allocation */
+    hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    HIP_TRY(ctx, hipMalloc(buf, bytes));
+    *have = bytes;
+    return RT_OK;
+}
+
+int rt_denoise_default_params(RtDenoiseParams* out)
+{
+    if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_denoise_default_params: out is null");
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(RtDenoiseParams);
+    out->iterations = 5;
+    out->sigmaColour = 4.0f;
+    out->sigmaNormal = 0.25f;
+    out->sigmaPlane = 0.1f;
+    out->demodulate = 1;
+    out->scale = 1.0f;
+    return RT_OK;
+}
+
+int rt_denoise_buffers(RtContext* ctx, const RtDenoiseParams* p, int width, int height, const void* d_rgba_in, const void* d_aov, void* d_rgba_out)
+{
+    static const char* call = "rt_denoise_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    rt_dn::Job job;
+    int rc = dn_check_params(ctx, call, p, &job);
+    if (rc) return rc;
+    if (width < 1 || height < 1 || (long long)width * height > (long long)INT32_MAX / 2)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d x %d is not an image size (at least 1 x 1, at most 2^30 pixels)", call, width, height);
+    if ((rc = dn_check_whole_image(ctx, call))) return rc;
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = dn_check_device_range(ctx, call, "d_rgba_in", d_rgba_in, n * 16))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_aov", d_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
+    if (dn_overlap(d_rgba_out, n * 16, d_rgba_in, n * 16) || dn_overlap(d_rgba_out, n * 16, d_aov, n * sizeof(RtPixelAov)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba_out overlaps an input", call);
+    RT_FLUSH(ctx);
+    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
+    job.W = width;
+    job.H = height;
+    HIP_TRY(ctx, rt_dn::enqueue(joined(ctx), job, d_rgba_in, d_aov, d_rgba_out, ctx->dDnScratch));
+    return RT_OK;
+}
+
+/* what rt_denoise and rt_denoise_to_device share: checks, the AOV pass, the filter from the context's image into dOut (device) */
+static int dn_check_context_call(RtContext* ctx, const char* call, const RtDenoiseParams* p, int aov_frame, const void* out, size_t bytes, rt_dn::Job* job)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    int rc = dn_check_params(ctx, call, p, job);
+    if (rc) return rc;
+    if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
+    if ((rc = check_renderable(ctx))) return rc;
+    if ((rc = dn_check_whole_image(ctx, call))) return rc;
+    const size_t want = (size_t)ctx->localRows * ctx->W * 16;
+    if (bytes != want || (bytes && !out))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x 16), got %zu%s", call, want, ctx->localRows, ctx->W, bytes, out ? "" : " and a null pointer");
+    job->W = ctx->W;
+    job->H = ctx->localRows;
+    return RT_OK;
+}
+
+static int dn_enqueue_context_call(RtContext* ctx, const rt_dn::Job& job, int use_accumulated, int aov_frame, void* dOut)
+{
+    const size_t n = (size_t)job.W * job.H;
+    int rc;
+    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
+    if ((rc = dn_grow(ctx, &ctx->dDnAov, &ctx->dnAovBytes, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov, n * sizeof(RtPixelAov)))) return rc;
+    HIP_TRY(ctx, rt_dn::enqueue(joined(ctx), job, dn_source(ctx, use_accumulated), ctx->dDnAov, dOut, ctx->dDnScratch));
+    return RT_OK;
+}
+
+int rt_denoise(RtContext* ctx, const RtDenoiseParams* p, int use_accumulated, int aov_frame, float* rgba, size_t bytes)
+{
+    static const char* call = "rt_denoise";
+    rt_dn::Job job;
+    int rc = dn_check_context_call(ctx, call, p, aov_frame, rgba, bytes, &job);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, call))) return rc;
+    if (!bytes) return RT_OK;
+    void* dOut = nullptr;
+    if ((rc = display_scratch(ctx, bytes, &dOut))) return rc;
+    if ((rc = dn_enqueue_context_call(ctx, job, use_accumulated, aov_frame, dOut))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    unsigned long long fired = 0;
+    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if (fired) return watchdog_failure(ctx, call, fired);
+    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgba, dOut, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accumulated, int aov_frame, void* d_rgba, size_t bytes)
+{
+    static const char* call = "rt_denoise_to_device";
+    rt_dn::Job job;
+    int rc = dn_check_context_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (bytes) {
+        if ((rc = dn_check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+        if (dn_overlap(d_rgba, bytes, dn_source(ctx, use_accumulated), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the source image", call);
+    } else if ((uintptr_t)d_rgba & 15) {
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
+    }
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, call))) return rc;
+    if (!bytes) return RT_OK;
+    if ((rc = dn_enqueue_context_call(ctx, job, use_accumulated, aov_frame, d_rgba))) return rc;
     ctx->aovUnreported = true;
     return RT_OK;
 }

@@ -156,6 +156,22 @@ def aov_srgb8(aov, channel, flip_y=True, depth_range=None):
     return out[::-1].copy() if flip_y else out
 
 
+# ---------------------------------------------------------------- a host image as a picture (the denoised image of HipTracer.denoise)
+def linear_srgb8(rgb, flip_y=True):
+    """RGBA8 picture of a linear (rows, W, 3 or 4) float image, rows bottom-up: the Display pass's transfer on the host — per channel
+    c = clip(c, 0, 1) (NaN counts as 0), then 12.92 c below 0.0031308 and 1.055 c^(1/2.4) - 0.055 above, then uint8(255 t + 0.5).
+    Alpha is 255.  flip_y: top row first (what write_png expects).  fp32 with numpy's pow: a picture, not part of the bit contract."""
+    rgb = np.asarray(rgb)
+    if rgb.ndim != 3 or rgb.shape[2] not in (3, 4):
+        raise ValueError("image must be (rows, W, 3) or (rows, W, 4)")
+    c = rgb[..., :3].astype(np.float32)
+    c = np.clip(np.where(np.isnan(c), np.float32(0), c), np.float32(0), np.float32(1))
+    t = np.where(c <= np.float32(0.0031308), np.float32(12.92) * c, np.float32(1.055) * np.power(c, np.float32(1 / 2.4)) - np.float32(0.055))
+    out = np.full(rgb.shape[:2] + (4,), 255, dtype=np.uint8)
+    out[..., :3] = (t.astype(np.float32) * np.float32(255) + np.float32(0.5)).astype(np.uint8)
+    return out[::-1].copy() if flip_y else out
+
+
 # ---------------------------------------------------------------- checkpoint / resume
 def save_checkpoint(path, manager):
     """Everything a progressive render needs to continue bit-identically: the accumulation sum,

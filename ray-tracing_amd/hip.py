@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
 COST_SYMBOLS = ["rt_render_cost"]
 # every symbol include/rt_aov.h declares
 AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
+# every symbol include/rt_denoise.h declares
+DENOISE_SYMBOLS = ["rt_denoise_default_params", "rt_denoise_buffers", "rt_denoise", "rt_denoise_to_device"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -89,6 +91,10 @@ class HipApi(abi.CApi):
         "render_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
         "render_aov": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
         "render_aov_to_device": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
+        "denoise_default_params": (C.c_int, [C.POINTER(abi.RtDenoiseParams)]),
+        "denoise_buffers": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "denoise": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+        "denoise_to_device": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -197,6 +203,18 @@ class HipApi(abi.CApi):
             raise abi.RtError(rc, "build_bvh_gpu_batch failed")
         total = (node_off[n - 1] + n_nodes[n - 1]) if n else 0
         return nodes[:total], tris, [(node_off[k], tri_off[k], stats[k].as_dict()) for k in range(n)]
+
+    def denoise_params(self, **fields):
+        """rt_denoise_default_params, with `fields` (iterations, sigmaColour, sigmaNormal, sigmaPlane, demodulate, scale) set on top."""
+        p = abi.RtDenoiseParams()
+        rc = self.denoise_default_params(C.byref(p))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, "rt_denoise_default_params failed")
+        for k, v in fields.items():
+            if k not in dict(abi.RtDenoiseParams._fields_):
+                raise TypeError(f"RtDenoiseParams has no field {k!r}")
+            setattr(p, k, v)
+        return p
 
     def create_tracer(self, device_id=0):
         h = C.c_void_p()
@@ -415,6 +433,28 @@ class HipTracer(abi.Tracer):
         """rt_render_aov_to_device: the same records into device memory (e.g. a torch tensor's data_ptr(), local_rows * W * 64 bytes),
         enqueued on the stream the context renders on; complete after synchronize()."""
         self._check(self.api.render_aov_to_device(self.h, int(frame), ptr, int(nbytes)))
+
+    def denoise(self, params=None, use_accumulated=True, aov_frame=1):
+        """rt_denoise (include/rt_denoise.h): the context's accumulated image (or its last frame) through the edge-avoiding a-trous
+        filter, guided by the AOV pass of frame `aov_frame`: a (rows, W, 4) float32 array, rows bottom-up.  `params`: an
+        abi.RtDenoiseParams (default: api.denoise_params()); the accumulated image is a sum, so scale = 1 / frames.  Changes no state
+        of the context."""
+        p = params if params is not None else self.api.denoise_params()
+        out = np.zeros((max(self.local_rows(), 0), self.width, 4), dtype=np.float32)
+        self._check(self.api.denoise(self.h, C.byref(p), 1 if use_accumulated else 0, int(aov_frame), out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def denoise_to_device(self, ptr, nbytes, params=None, use_accumulated=True, aov_frame=1):
+        """rt_denoise_to_device: the same image into device memory (e.g. a torch tensor's data_ptr(), rows * W * 16 bytes), enqueued on
+        the stream the context renders on; complete after synchronize()."""
+        p = params if params is not None else self.api.denoise_params()
+        self._check(self.api.denoise_to_device(self.h, C.byref(p), 1 if use_accumulated else 0, int(aov_frame), ptr, int(nbytes)))
+
+    def denoise_buffers(self, width, height, rgba_in_ptr, aov_ptr, rgba_out_ptr, params=None):
+        """rt_denoise_buffers: the filter alone on caller-owned device memory (width x height RGBA32F in and out, width x height
+        RtPixelAov records), enqueued on the stream the context renders on.  Needs no scene and no resize."""
+        p = params if params is not None else self.api.denoise_params()
+        self._check(self.api.denoise_buffers(self.h, C.byref(p), int(width), int(height), rgba_in_ptr, aov_ptr, rgba_out_ptr))
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

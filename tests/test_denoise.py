@@ -1,0 +1,186 @@
+"""rt_denoise (include/rt_denoise.h) without a GPU: the header is plain C (C99 and C++17) and RtDenoiseParams is the same 32 bytes in C,
+in ctypes and through a numpy view; the library exports the header's four calls and each refuses a null context; the default
+parameters are valid; and the arithmetic of ray-tracing_amd/csrc/rt_denoise_math.h — the functions the kernels call, here run by the
+host driver tests/denoise_math_driver.cpp — equals the NumPy restatement of the header's prose (tests/denoise_reference.py) bit for
+bit, every pixel, every channel."""
+import ctypes as C
+import os
+import re
+import shutil
+import struct
+import subprocess
+
+import numpy as np
+import pytest
+
+import denoise_reference as ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+OFFSETS = {"struct_size": 0, "iterations": 4, "sigmaColour": 8, "sigmaNormal": 12, "sigmaPlane": 16, "demodulate": 20, "scale": 24, "reserved": 28}
+FUNCTIONS = ["rt_denoise", "rt_denoise_buffers", "rt_denoise_default_params", "rt_denoise_to_device"]
+
+
+def header_functions():
+    text = open(os.path.join(INCLUDE, "rt_denoise.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(rt_[a-z_0-9]+)\s*\(", text)))
+
+
+# ---------------------------------------------------------------- 1. the header and the three layouts
+@pytest.mark.parametrize("lang", ["c99", "c++17"])
+def test_header_compiles_and_has_the_documented_layout(lang, tmp_path):
+    cxx = lang.startswith("c++")
+    src = tmp_path / ("dn.cpp" if cxx else "dn.c")
+    checks = "\n".join(f"typedef char at_{f}[offsetof(RtDenoiseParams, {f}) == {o} ? 1 : -1];" for f, o in OFFSETS.items())
+    src.write_text('#include <stddef.h>\n#include "rt_denoise.h"\ntypedef char size_is_32[sizeof(RtDenoiseParams) == 32 ? 1 : -1];\n' + checks +
+                   "\nint use(RtContext* c, RtDenoiseParams* p, float* f, RtPixelAov* a) { return rt_denoise_default_params(p) + rt_denoise_buffers(c, p, 1, 1, f, a, f)"
+                   " + rt_denoise(c, p, 1, 1, f, 16) + rt_denoise_to_device(c, p, 1, 1, f, 16); }\n")
+    cmd = ["g++", "-x", "c++"] if cxx else ["gcc", "-x", "c"]
+    subprocess.check_call(cmd + [f"-std={lang}", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I", INCLUDE, str(src)])
+
+
+def test_ctypes_struct_and_numpy_view_are_the_same_32_bytes(pkg):
+    abi = pkg.abi
+    assert C.sizeof(abi.RtDenoiseParams) == 32 and abi.DENOISE_PARAMS_DTYPE.itemsize == 32
+    assert tuple(n for n, _ in abi.RtDenoiseParams._fields_) == tuple(OFFSETS) == abi.DENOISE_PARAMS_DTYPE.names
+    for f, off in OFFSETS.items():
+        assert getattr(abi.RtDenoiseParams, f).offset == off and getattr(abi.RtDenoiseParams, f).size == 4, f
+        assert abi.DENOISE_PARAMS_DTYPE.fields[f][1] == off, f
+    p = abi.RtDenoiseParams(struct_size=32, iterations=3, sigmaColour=0.5, sigmaNormal=0.25, sigmaPlane=2.0, demodulate=1, scale=0.125, reserved=0)
+    a = np.frombuffer(bytes(p), dtype=abi.DENOISE_PARAMS_DTYPE)[0]
+    assert a.tolist() == (32, 3, 0.5, 0.25, 2.0, 1, 0.125, 0)
+    assert struct.unpack("<Iifffifi", bytes(p)) == (32, 3, 0.5, 0.25, 2.0, 1, 0.125, 0)
+
+
+# ---------------------------------------------------------------- 2. symbols  3. null context  4. default parameters
+def test_header_symbols_are_exported_and_listed(pkg, api):
+    names = header_functions()
+    assert names == FUNCTIONS
+    assert sorted(pkg.hip.DENOISE_SYMBOLS) == names, "hip.DENOISE_SYMBOLS is out of sync with include/rt_denoise.h"
+    for other in (pkg.hip.ABI_SYMBOLS, pkg.hip.COST_SYMBOLS, pkg.hip.AOV_SYMBOLS):
+        assert not set(names) & set(other)
+    for n in names:
+        assert hasattr(api.lib, n), f"libraytrace_hip.so does not export {n}"
+
+
+def test_every_call_refuses_a_null_context(pkg, api):
+    abi = pkg.abi
+    p = api.denoise_params()
+    buf = np.zeros(64, dtype=np.float32)
+    d = buf.ctypes.data
+    assert api.denoise_buffers(None, C.byref(p), 1, 1, d, d, d) == abi.RT_ERR_INVALID_ARG
+    assert b"null context" in api.last_error(None)
+    assert api.denoise(None, C.byref(p), 1, 1, d, 16) == abi.RT_ERR_INVALID_ARG
+    assert api.denoise_to_device(None, C.byref(p), 1, 1, d, 16) == abi.RT_ERR_INVALID_ARG
+    assert api.denoise(None, None, 1, 1, None, 0) == abi.RT_ERR_INVALID_ARG
+    assert api.denoise_default_params(None) == abi.RT_ERR_INVALID_ARG
+
+
+def test_default_params_are_valid(pkg, api):
+    raw = (C.c_uint8 * 32)(*([0xff] * 32))
+    p = pkg.abi.RtDenoiseParams.from_buffer(raw)
+    assert api.denoise_default_params(C.byref(p)) == pkg.abi.RT_OK
+    assert p.struct_size == 32 and p.reserved == 0
+    assert 1 <= p.iterations <= pkg.abi.DENOISE_MAX_ITERATIONS
+    for s in (p.sigmaColour, p.sigmaNormal, p.sigmaPlane):
+        assert np.isfinite(s) and s > 0
+    assert p.demodulate == 1 and p.scale == 1.0
+    q = api.denoise_params(iterations=2, scale=0.25)
+    assert (q.iterations, q.scale, q.sigmaColour) == (2, 0.25, p.sigmaColour)
+    with pytest.raises(TypeError):
+        api.denoise_params(sigma=1.0)
+
+
+# ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
+@pytest.fixture(scope="module")
+def driver(tmp_path_factory):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    exe = str(tmp_path_factory.mktemp("denoise_math") / "driver")
+    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
+                           os.path.join(ROOT, "tests", "denoise_math_driver.cpp"), "-o", exe])
+
+    def run(rgba, aov, iterations, sc, sn, sp, demodulate, scale, via_file=None):
+        h, w = rgba.shape[:2]
+        blob = struct.pack("<4i4f", w, h, iterations, int(demodulate), scale, sc, sn, sp) + rgba.tobytes() + aov.tobytes()
+        if via_file:
+            with open(via_file, "wb") as f:
+                f.write(blob)
+            out = subprocess.run([exe, str(via_file)], capture_output=True, timeout=600, check=True).stdout
+        else:
+            out = subprocess.run([exe], input=blob, capture_output=True, timeout=600, check=True).stdout
+        return np.frombuffer(out, dtype=np.float32).reshape(h, w, 4)
+    return run
+
+
+def assert_same_bits(got, want, what):
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+    if len(bad):
+        y, x, k = bad[0]
+        raise AssertionError(f"{what}: {len(set(map(tuple, bad[:, :2])))} pixels differ; first at row {y}, column {x}, channel {k}: "
+                             f"got {got[y, x]}, want {want[y, x]}")
+
+
+def test_the_synthetic_image_covers_what_it_is_there_for(pkg):
+    rgba, aov = ref.synthetic(pkg, 23, 17)
+    assert set(np.unique(aov["object"]).tolist()) == {-1, 0, 1, 2}
+    assert ((aov["hit"] & 3) == 2).any() and ((aov["hit"] & 3) == 1).any() and ((aov["hit"] & 3) == 0).any()
+    c = rgba[..., :3]
+    assert np.isnan(c).any() and np.isposinf(c).any()
+    assert (aov["albedo"][aov["object"] == 1][:, 2] < 1 / 256).all() and (aov["albedo"][aov["object"] == 1][:, 0] > 1 / 256).all()
+    hit = aov["object"] >= 0
+    assert hit[0].any() and hit[-1].any() and hit[:, 0].any() and hit[:, -1].any()  # filtered pixels on every border
+
+
+@pytest.mark.parametrize("demodulate", [0, 1])
+@pytest.mark.parametrize("iterations", [0, 1, 2, 3, 4])
+def test_math_header_equals_the_numpy_restatement(pkg, orc, driver, iterations, demodulate, tmp_path):
+    """Passes 0 ... 3 (spacings 1, 2, 4, 8) on a 23 x 17 image: at spacing 8 most taps fall outside."""
+    rgba, aov = ref.synthetic(pkg, 23, 17)
+    args = (iterations, 0.75, 0.3, 0.2, demodulate, 0.25)
+    got = driver(rgba, aov, *args, via_file=(tmp_path / "in.bin") if iterations == 2 else None)
+    want = ref.denoise(orc, rgba, aov, *args)
+    assert_same_bits(got, want, f"{iterations} iterations, demodulate {demodulate}")
+    # exact properties of the definition itself
+    unfiltered = (aov["object"] < 0) | ~np.isfinite(rgba[..., :3]).all(axis=-1)
+    assert unfiltered.any()
+    scaled = rgba[..., :3] * np.float32(0.25)
+    assert np.array_equal(got[..., :3].view(np.uint32)[unfiltered], scaled.view(np.uint32)[unfiltered])
+    assert np.array_equal(got[..., 3].view(np.uint32), rgba[..., 3].view(np.uint32))
+    if iterations == 0:
+        assert np.array_equal(got[..., :3].view(np.uint32), scaled.view(np.uint32))
+    else:
+        changed = (got[..., :3].view(np.uint32) != scaled.view(np.uint32)).any(axis=-1)
+        assert changed[~unfiltered].mean() > 0.9  # it is a filter
+
+
+def test_nothing_crosses_an_object_edge(pkg, orc, driver):
+    rgba, aov = ref.synthetic(pkg, 23, 17, seed=2)
+    hit = aov["object"] >= 0
+    a = aov["object"] == 0
+    rgba[..., :3] = np.where(a[..., None], np.float32([1, 0, 0]), np.float32([0, 1, 0]))
+    got = driver(rgba, aov, 4, 10.0, 10.0, 10.0, 1, 1.0)
+    assert a.any() and (hit & ~a).any()
+    assert (got[..., 1][a] == 0).all() and (got[..., 0][hit & ~a] == 0).all()
+    assert (got[..., 0][a] > 0).all()
+
+
+# ---------------------------------------------------------------- the picture of a denoised image
+def test_linear_srgb8(pkg):
+    d = pkg.display
+    img = np.zeros((2, 3, 4), dtype=np.float32)
+    img[0, 0, :3] = (0.0, 1.0, 2.0)
+    img[0, 1, :3] = (np.nan, -1.0, 0.002)
+    img[1, 2, :3] = (0.5, 0.2140, 0.0031308)
+    out = d.linear_srgb8(img, flip_y=False)
+    assert out.shape == (2, 3, 4) and out.dtype == np.uint8 and (out[..., 3] == 255).all()
+    assert out[0, 0, :3].tolist() == [0, 255, 255]
+    assert out[0, 1, :3].tolist() == [0, 0, int(12.92 * 0.002 * 255 + 0.5)]
+    assert out[1, 2, :3].tolist() == [188, 127, 10]  # 0.5 -> 0.7354, 0.2140 -> 0.5, the knee -> 0.04045
+    assert np.array_equal(d.linear_srgb8(img), out[::-1])
+    assert np.array_equal(d.linear_srgb8(img[..., :3]), out[::-1])
+    with pytest.raises(ValueError):
+        d.linear_srgb8(np.zeros((2, 3)))

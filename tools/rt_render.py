@@ -15,6 +15,11 @@ value / --cost-scale, or pure red above the scale.
 --aov-png PREFIX writes PREFIX_normal.png, PREFIX_albedo.png, PREFIX_depth.png and PREFIX_object.png: what camera ray 0 of
 frame --aov-frame (default 1) hits first in every pixel (rt_render_aov, include/rt_aov.h); --aov-npy FILE saves the raw
 records (numpy, abi.AOV_DTYPE, rows bottom-up).
+    python tools/rt_render.py 3 --frames 4 --png noisy.png --denoise-png denoised.png
+
+--denoise-png FILE writes the accumulated image through the edge-avoiding a-trous filter (rt_denoise, include/rt_denoise.h) with
+scale = 1 / frames accumulated, guided by the AOV pass of frame --aov-frame, as an sRGB picture (display.linear_srgb8);
+--denoise-iterations N (0..8) and --denoise-sigma COLOUR,NORMAL,PLANE override the library's default parameters.
 
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
@@ -43,6 +48,9 @@ def main():
     ap.add_argument("--aov-png", metavar="PREFIX", help="first-hit feature buffers of one frame as PREFIX_{normal,albedo,depth,object}.png (rt_render_aov)")
     ap.add_argument("--aov-npy", metavar="FILE", help="the raw RtPixelAov records of that frame as a numpy file")
     ap.add_argument("--aov-frame", type=int, default=1, help="frame (Frame uniform, >= 1) whose camera rays are reported (default 1)")
+    ap.add_argument("--denoise-png", metavar="FILE", help="the accumulated image through rt_denoise, as an sRGB picture")
+    ap.add_argument("--denoise-iterations", type=int, help="passes of the filter, 0..8 (default: the library's)")
+    ap.add_argument("--denoise-sigma", metavar="C,N,P", help="sigmaColour,sigmaNormal,sigmaPlane (default: the library's)")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
@@ -107,6 +115,18 @@ def main():
         hit = aov["hit"] & 3
         print(json.dumps({"aov_frame": a.aov_frame, "pixels": int(aov.size), "miss": int((hit == 0).sum()), "opaque": int((hit == 1).sum()),
                           "glass": int((hit == 2).sum()), "objects_seen": int(len(set(aov["object"][hit != 0].tolist())))}))
+    if a.denoise_png:
+        n = max(mgr.numAccumulatedFrames - 1, 1)  # frames in the accumulated sum
+        fields = {"scale": 1.0 / n}
+        if a.denoise_iterations is not None:
+            fields["iterations"] = a.denoise_iterations
+        if a.denoise_sigma:
+            fields["sigmaColour"], fields["sigmaNormal"], fields["sigmaPlane"] = (float(x) for x in a.denoise_sigma.split(","))
+        p = api.denoise_params(**fields)
+        img = tr.denoise(p, use_accumulated=True, aov_frame=a.aov_frame)
+        pkg.display.write_png(a.denoise_png, pkg.display.linear_srgb8(img))
+        print(json.dumps({"denoise_png": a.denoise_png, "iterations": p.iterations, "sigma": [p.sigmaColour, p.sigmaNormal, p.sigmaPlane],
+                          "demodulate": p.demodulate, "scale": p.scale, "aov_frame": a.aov_frame}))
 
 
 if __name__ == "__main__":
