@@ -100,6 +100,20 @@ DENOISE_PARAMS_DTYPE = np.dtype([
 DENOISE_MAX_ITERATIONS = 8
 
 
+class RtReprojectParams(C.Structure):
+    """include/rt_reproject.h: the previous camera and the thresholds of a reprojection (100 bytes; struct_size is the handshake)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("prevViewParams", C.c_float * 3), ("prevCamLocalToWorld", C.c_float * 16),
+        ("maxPlaneDistance", C.c_float), ("minNormalDot", C.c_float), ("maxHistory", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_int32)]
+
+
+# the same 100 bytes as a numpy record
+REPROJECT_PARAMS_DTYPE = np.dtype([
+    ("struct_size", "<u4"), ("prevViewParams", "<f4", (3,)), ("prevCamLocalToWorld", "<f4", (16,)),
+    ("maxPlaneDistance", "<f4"), ("minNormalDot", "<f4"), ("maxHistory", "<f4"), ("flags", "<u4"), ("reserved", "<i4")])
+REPROJECT_FLAG_GLASS = 1  # bit 0 of flags: carry history onto glass first hits too
+
+
 class RtBvhStats(C.Structure):
     _fields_ = [
         ("triangleCount", C.c_int32), ("totalNodeCount", C.c_int32), ("leafNodeCount", C.c_int32),

@@ -31,9 +31,11 @@
 #include "../../include/rt_cost.h"
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
+#include "../../include/rt_reproject.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
+#include "rt_reproject_launch.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -2408,8 +2410,8 @@ static int aov_report(RtContext* ctx, const char* call)
     ctx->aovUnreported = false;
     unsigned long long fired = 0;
     HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device or rt_denoise_to_device call: walks were "
-                           "cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call: "
+                           "walks were cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
     return RT_OK;
 }
 
@@ -2666,6 +2668,197 @@ int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accum
     if (!bytes) return RT_OK;
     if ((rc = dn_enqueue_context_call(ctx, job, use_accumulated, aov_frame, d_rgba))) return rc;
     ctx->aovUnreported = true;
+    return RT_OK;
+}
+
+/* ---- rt_reproject_buffers / rt_reproject_accumulated / rt_resolve* (include/rt_reproject.h) -----------------------------------
+ * The kernels are rt_reproject.hip's (rt_rp::enqueue*); here are the argument checks, the scratch and the order.  Everything runs on the
+ * joined main stream (rt_launch_order.h, join): behind every frame either render stream holds, and — join() re-arms the fork — in front
+ * of every frame requested later, which is how rt_reset_accumulation and rt_write_accumulated order their write of the accumulator.
+ * The scratch is the denoiser's: its colour images hold the reprojected image, its records the current view's; both are only ever used
+ * by work on this one stream. */
+static int rp_check_params(RtContext* ctx, const char* call, const RtReprojectParams* p, rt_rp_job* job)
+{
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: null parameters", call);
+    if (p->struct_size != sizeof(RtReprojectParams))
+        return fail(ctx, RT_ERR_ABI_MISMATCH, "%s: RtReprojectParams.struct_size is %u, this library's is %zu", call, p->struct_size, sizeof(RtReprojectParams));
+    if (!(p->maxPlaneDistance >= 0.0f) || !rt_rp_finite(p->maxPlaneDistance)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: maxPlaneDistance must be finite and >= 0", call);
+    if (!rt_rp_finite(p->minNormalDot)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: minNormalDot is not finite", call);
+    if (!(p->maxHistory > 0.0f) || !rt_rp_finite(p->maxHistory)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: maxHistory must be finite and > 0", call);
+    if (p->flags & ~RT_REPROJECT_FLAG_GLASS) return fail(ctx, RT_ERR_INVALID_ARG, "%s: flags 0x%x: only bit 0 is defined", call, p->flags);
+    if (p->reserved != 0) return fail(ctx, RT_ERR_INVALID_ARG, "%s: reserved must be 0", call);
+    for (int r = 0; r < 3; r++) {
+        job->R[r] = p->prevCamLocalToWorld[r];
+        job->U[r] = p->prevCamLocalToWorld[4 + r];
+        job->F[r] = p->prevCamLocalToWorld[8 + r];
+        job->O[r] = p->prevCamLocalToWorld[12 + r];
+    }
+    job->pw = p->prevViewParams[0];
+    job->ph = p->prevViewParams[1];
+    job->fd = p->prevViewParams[2];
+    job->maxPlaneDistance = p->maxPlaneDistance;
+    job->minNormalDot = p->minNormalDot;
+    job->maxHistory = p->maxHistory;
+    job->glass = (int)(p->flags & RT_REPROJECT_FLAG_GLASS);
+    return RT_OK;
+}
+
+static int rp_check_size(RtContext* ctx, const char* call, int width, int height)
+{
+    if (width < 1 || height < 1 || (long long)width * height > (1ll << 30))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d x %d is not an image size (at least 1 x 1, at most 2^30 pixels)", call, width, height);
+    return RT_OK;
+}
+
+static float* rp_accum(const RtContext* ctx) { return ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum; }
+
+int rt_reproject_default_params(RtReprojectParams* out)
+{
+    if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_reproject_default_params: out is null");
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(RtReprojectParams);
+    out->maxPlaneDistance = 0.1f;
+    out->minNormalDot = 0.9f;
+    out->maxHistory = 256.0f;
+    return RT_OK;
+}
+
+int rt_reproject_buffers(RtContext* ctx, const RtReprojectParams* p, int width, int height, const void* d_prev_rgba, const void* d_prev_aov, const void* d_cur_aov,
+                         void* d_out_rgba)
+{
+    static const char* call = "rt_reproject_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    rt_rp_job job;
+    int rc = rp_check_params(ctx, call, p, &job);
+    if (rc) return rc;
+    if ((rc = rp_check_size(ctx, call, width, height))) return rc;
+    if (ctx->partCount > 1)
+        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; reprojection needs the whole image (gather first)", call, ctx->partIndex,
+                    ctx->partCount);
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = dn_check_device_range(ctx, call, "d_prev_rgba", d_prev_rgba, n * 16))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_prev_aov", d_prev_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_cur_aov", d_cur_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_out_rgba", d_out_rgba, n * 16))) return rc;
+    if (dn_overlap(d_out_rgba, n * 16, d_prev_rgba, n * 16) || dn_overlap(d_out_rgba, n * 16, d_prev_aov, n * sizeof(RtPixelAov)) ||
+        dn_overlap(d_out_rgba, n * 16, d_cur_aov, n * sizeof(RtPixelAov)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_out_rgba overlaps an input", call);
+    RT_FLUSH(ctx);
+    job.W = width;
+    job.H = height;
+    HIP_TRY(ctx, rt_rp::enqueue(joined(ctx), job, d_prev_rgba, d_prev_aov, d_cur_aov, d_out_rgba));
+    return RT_OK;
+}
+
+int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const void* d_prev_aov, int aov_frame, void* d_cur_aov_out)
+{
+    static const char* call = "rt_reproject_accumulated";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    rt_rp_job job;
+    int rc = rp_check_params(ctx, call, p, &job);
+    if (rc) return rc;
+    if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
+    if ((rc = check_renderable(ctx))) return rc;
+    if (ctx->partCount > 1)
+        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; reprojection needs the whole image (gather, then rt_reproject_buffers)", call,
+                    ctx->partIndex, ctx->partCount);
+    job.W = ctx->W;
+    job.H = ctx->localRows;
+    const size_t n = (size_t)job.W * job.H, recBytes = n * sizeof(RtPixelAov);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    float* const accum = rp_accum(ctx);
+    if (!d_prev_aov) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov is null", call);
+    if ((uintptr_t)d_prev_aov & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov must be 16-byte aligned", call);
+    if ((uintptr_t)d_cur_aov_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_cur_aov_out must be 16-byte aligned", call);
+    if (n) {
+        if ((rc = dn_check_device_range(ctx, call, "d_prev_aov", d_prev_aov, recBytes))) return rc;
+        if (dn_overlap(d_prev_aov, recBytes, accum, n * 16)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov overlaps AccumulatedRender", call);
+        if (d_cur_aov_out) {
+            if ((rc = dn_check_device_range(ctx, call, "d_cur_aov_out", d_cur_aov_out, recBytes))) return rc;
+            if (dn_overlap(d_cur_aov_out, recBytes, d_prev_aov, recBytes) || dn_overlap(d_cur_aov_out, recBytes, accum, n * 16))
+                return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_cur_aov_out overlaps d_prev_aov or AccumulatedRender", call);
+        }
+    }
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, call))) return rc;
+    if (!n) return RT_OK;
+    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, n * 16))) return rc;
+    if ((rc = dn_grow(ctx, &ctx->dDnAov, &ctx->dnAovBytes, recBytes))) return rc;
+    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov, recBytes))) return rc;
+    ctx->aovUnreported = true;
+    hipStream_t st = joined(ctx);
+    if (d_cur_aov_out) HIP_TRY(ctx, hipMemcpyAsync(d_cur_aov_out, ctx->dDnAov, recBytes, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, rt_rp::enqueue(st, job, accum, d_prev_aov, ctx->dDnAov, ctx->dDnScratch));
+    /* over the accumulator, unless the pass's watchdog fired: the device reads the pass's own word, the host reports it later */
+    HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, accum, n, ctx->dAovWords + kWatchdogWord));
+    return RT_OK;
+}
+
+int rt_resolve_buffers(RtContext* ctx, int width, int height, const void* d_rgba_sum, void* d_rgba_out)
+{
+    static const char* call = "rt_resolve_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    int rc = rp_check_size(ctx, call, width, height);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = dn_check_device_range(ctx, call, "d_rgba_sum", d_rgba_sum, n * 16))) return rc;
+    if ((rc = dn_check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
+    if (d_rgba_out != d_rgba_sum && dn_overlap(d_rgba_out, n * 16, d_rgba_sum, n * 16))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba_out overlaps d_rgba_sum without being it (in place means the same pointer)", call);
+    RT_FLUSH(ctx);
+    HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), d_rgba_sum, d_rgba_out, n));
+    return RT_OK;
+}
+
+static int rp_check_resolve_call(RtContext* ctx, const char* call, const void* out, size_t bytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "%s before rt_resize", call);
+    const size_t want = (size_t)ctx->localRows * ctx->W * 16;
+    if (bytes != want || (bytes && !out))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x 16), got %zu%s", call, want, ctx->localRows, ctx->W, bytes, out ? "" : " and a null pointer");
+    return RT_OK;
+}
+
+int rt_resolve(RtContext* ctx, float* rgba, size_t bytes)
+{
+    static const char* call = "rt_resolve";
+    int rc = rp_check_resolve_call(ctx, call, rgba, bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    void* dOut = nullptr;
+    if (bytes) {
+        if ((rc = display_scratch(ctx, bytes, &dOut))) return rc;
+        HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), rp_accum(ctx), dOut, bytes / 16));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    /* a device AOV pass completes here: a watchdog that fired in rt_reproject_accumulated's pass left the accumulator as it was, and the
+     * caller of this host read must not take its resolve for the reprojected image */
+    if ((rc = aov_report(ctx, call))) return rc;
+    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
+    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, dOut, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_resolve_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
+{
+    static const char* call = "rt_resolve_to_device";
+    int rc = rp_check_resolve_call(ctx, call, d_rgba, bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (bytes) {
+        if ((rc = dn_check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+        if (dn_overlap(d_rgba, bytes, rp_accum(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
+    } else if ((uintptr_t)d_rgba & 15) {
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
+    }
+    RT_FLUSH(ctx);
+    if (!bytes) return RT_OK;
+    HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), rp_accum(ctx), d_rgba, bytes / 16));
     return RT_OK;
 }
 

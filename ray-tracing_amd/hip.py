@@ -35,6 +35,9 @@ COST_SYMBOLS = ["rt_render_cost"]
 AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
 # every symbol include/rt_denoise.h declares
 DENOISE_SYMBOLS = ["rt_denoise_default_params", "rt_denoise_buffers", "rt_denoise", "rt_denoise_to_device"]
+# every symbol include/rt_reproject.h declares
+REPROJECT_SYMBOLS = ["rt_reproject_default_params", "rt_reproject_buffers", "rt_reproject_accumulated", "rt_resolve_buffers", "rt_resolve",
+                     "rt_resolve_to_device"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -95,6 +98,12 @@ class HipApi(abi.CApi):
         "denoise_buffers": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
         "denoise": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
         "denoise_to_device": (C.c_int, [C.c_void_p, C.POINTER(abi.RtDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_size_t]),
+        "reproject_default_params": (C.c_int, [C.POINTER(abi.RtReprojectParams)]),
+        "reproject_buffers": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "reproject_accumulated": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_void_p, C.c_int, C.c_void_p]),
+        "resolve_buffers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+        "resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "resolve_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -214,6 +223,25 @@ class HipApi(abi.CApi):
             if k not in dict(abi.RtDenoiseParams._fields_):
                 raise TypeError(f"RtDenoiseParams has no field {k!r}")
             setattr(p, k, v)
+        return p
+
+    def reproject_params(self, prev_params=None, **fields):
+        """rt_reproject_default_params, with the previous camera taken from `prev_params` (the RtParams of the view that is being left)
+        and `fields` (prevViewParams, prevCamLocalToWorld, maxPlaneDistance, minNormalDot, maxHistory, flags) set on top."""
+        p = abi.RtReprojectParams()
+        rc = self.reproject_default_params(C.byref(p))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, "rt_reproject_default_params failed")
+        if prev_params is not None:
+            p.prevViewParams[:] = list(prev_params.viewParams)
+            p.prevCamLocalToWorld[:] = list(prev_params.camLocalToWorld)
+        for k, v in fields.items():
+            if k not in dict(abi.RtReprojectParams._fields_):
+                raise TypeError(f"RtReprojectParams has no field {k!r}")
+            if k in ("prevViewParams", "prevCamLocalToWorld"):
+                getattr(p, k)[:] = [float(x) for x in v]
+            else:
+                setattr(p, k, v)
         return p
 
     def create_tracer(self, device_id=0):
@@ -345,6 +373,20 @@ class MultiTracer:
         return out
 
 
+    def _needs_whole_image(self, what):
+        raise abi.RtError(abi.RT_ERR_STATE, f"{what}: every context of a MultiTracer owns part of the image; gather the image and the AOV records "
+                                            "of all parts onto one device (gather_accumulated_to_device), then use the *_buffers call of one context")
+
+    def reproject_accumulated(self, *args, **kwargs):
+        self._needs_whole_image("reproject_accumulated")
+
+    def resolve(self, *args, **kwargs):
+        self._needs_whole_image("resolve")
+
+    def resolve_to_device(self, *args, **kwargs):
+        self._needs_whole_image("resolve_to_device")
+
+
 class HipTracer(abi.Tracer):
     """An RtContext on one MI355X."""
 
@@ -455,6 +497,32 @@ class HipTracer(abi.Tracer):
         RtPixelAov records), enqueued on the stream the context renders on.  Needs no scene and no resize."""
         p = params if params is not None else self.api.denoise_params()
         self._check(self.api.denoise_buffers(self.h, C.byref(p), int(width), int(height), rgba_in_ptr, aov_ptr, rgba_out_ptr))
+
+    def reproject_buffers(self, width, height, prev_rgba_ptr, prev_aov_ptr, cur_aov_ptr, out_rgba_ptr, params):
+        """rt_reproject_buffers (include/rt_reproject.h): the reprojection alone on caller-owned device memory, enqueued on the stream the
+        context renders on.  `params`: api.reproject_params(previous RtParams, ...).  Needs no scene and no resize."""
+        self._check(self.api.reproject_buffers(self.h, C.byref(params), int(width), int(height), prev_rgba_ptr, prev_aov_ptr, cur_aov_ptr, out_rgba_ptr))
+
+    def reproject_accumulated(self, params, prev_aov_ptr, aov_frame=1, cur_aov_out_ptr=None):
+        """rt_reproject_accumulated: after set_params with the new camera, replace the accumulated image by its reprojection into the
+        current view.  prev_aov_ptr: the device records of the view that was left (render_aov_to_device before the move);
+        cur_aov_out_ptr: optional device memory that receives the current view's records.  Only enqueues."""
+        self._check(self.api.reproject_accumulated(self.h, C.byref(params), prev_aov_ptr, int(aov_frame), cur_aov_out_ptr))
+
+    def resolve(self):
+        """rt_resolve: the accumulated image divided per pixel by its own frame count (alpha): (rows, W, 4) float32, rows bottom-up; the
+        alpha channel is the history length."""
+        out = np.zeros((max(self.local_rows(), 0), self.width, 4), dtype=np.float32)
+        self._check(self.api.resolve(self.h, out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def resolve_to_device(self, ptr, nbytes):
+        """rt_resolve_to_device: the same image into device memory (rows * W * 16 bytes), enqueued on the stream the context renders on."""
+        self._check(self.api.resolve_to_device(self.h, ptr, int(nbytes)))
+
+    def resolve_buffers(self, width, height, rgba_sum_ptr, rgba_out_ptr):
+        """rt_resolve_buffers: the per-pixel divide on caller-owned device memory (in place when both pointers are equal)."""
+        self._check(self.api.resolve_buffers(self.h, int(width), int(height), rgba_sum_ptr, rgba_out_ptr))
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

@@ -1,0 +1,62 @@
+// Host driver of ray-tracing_amd/csrc/rt_reproject_math.h for tests/test_reproject.py: rt_reproject and rt_resolve over arrays read
+// from a file (argv[1]) or stdin, with the very functions the kernels call.
+//
+// Input (binary, little endian):  int32 mode (0 reproject, 1 resolve), W, H, flags;
+//   mode 0:  float32 prevViewParams[3], prevCamLocalToWorld[16], maxPlaneDistance, minNormalDot, maxHistory;
+//            W*H x 4 float32 (the previous sums);  W*H x 16 float32 (the previous records, raw words);  W*H x 16 float32 (the current)
+//   mode 1:  W*H x 4 float32 (the sums)
+// Output (binary, to stdout):     W*H x 4 float32
+#include <cstdint>
+#include <cstdio>
+#include <vector>
+
+#include "../ray-tracing_amd/csrc/rt_reproject_math.h"
+
+struct PrevView {
+    const rt_rp4* rgba;
+    const rt_rp4* aov;
+    rt_rp4 colour(size_t i) const { return rgba[i]; }
+    rt_rp4 q0(size_t i) const { return aov[4 * i]; }
+    rt_rp4 q1(size_t i) const { return aov[4 * i + 1]; }
+    int32_t object(size_t i) const { return (int32_t)rt_f2u(aov[4 * i + 2].w); }
+};
+
+int main(int argc, char** argv)
+{
+    FILE* f = argc > 1 ? fopen(argv[1], "rb") : stdin;
+    if (!f) return 2;
+    int32_t head[4];
+    if (fread(head, 4, 4, f) != 4) return 3;
+    const int mode = head[0], W = head[1], H = head[2];
+    if (W < 1 || H < 1 || mode < 0 || mode > 1) return 4;
+    const size_t n = (size_t)W * H;
+    std::vector<rt_rp4> P(n), out(n);
+    if (mode == 1) {
+        if (fread(P.data(), 16, n, f) != n) return 5;
+        for (size_t i = 0; i < n; i++) out[i] = rt_rp_resolve(P[i]);
+        return fwrite(out.data(), 16, n, stdout) == n ? 0 : 6;
+    }
+    float par[22];
+    if (fread(par, 4, 22, f) != 22) return 3;
+    std::vector<rt_rp4> b(4 * n), a(4 * n);
+    if (fread(P.data(), 16, n, f) != n || fread(b.data(), 16, 4 * n, f) != 4 * n || fread(a.data(), 16, 4 * n, f) != 4 * n) return 5;
+    rt_rp_job job;
+    for (int r = 0; r < 3; r++) {
+        job.R[r] = par[3 + r];
+        job.U[r] = par[3 + 4 + r];
+        job.F[r] = par[3 + 8 + r];
+        job.O[r] = par[3 + 12 + r];
+    }
+    job.pw = par[0];
+    job.ph = par[1];
+    job.fd = par[2];
+    job.maxPlaneDistance = par[19];
+    job.minNormalDot = par[20];
+    job.maxHistory = par[21];
+    job.glass = head[3] & 1;
+    job.W = W;
+    job.H = H;
+    const PrevView prev = {P.data(), b.data()};
+    for (size_t i = 0; i < n; i++) out[i] = rt_rp_pixel(job, a[4 * i], a[4 * i + 1], (int32_t)rt_f2u(a[4 * i + 2].w), prev);
+    return fwrite(out.data(), 16, n, stdout) == n ? 0 : 6;
+}

@@ -20,6 +20,12 @@ records (numpy, abi.AOV_DTYPE, rows bottom-up).
 --denoise-png FILE writes the accumulated image through the edge-avoiding a-trous filter (rt_denoise, include/rt_denoise.h) with
 scale = 1 / frames accumulated, guided by the AOV pass of frame --aov-frame, as an sRGB picture (display.linear_srgb8);
 --denoise-iterations N (0..8) and --denoise-sigma COLOUR,NORMAL,PLANE override the library's default parameters.
+    python tools/rt_render.py 3 --frames 32 --reproject-png moved --reproject-move 0.05,0.02,0.03 --reproject-frames 4
+
+--reproject-png PREFIX: after the --frames frames, moves the camera by --reproject-move DX,DY,DZ (world units), carries the accumulated
+image into the new view (rt_reproject_accumulated, include/rt_reproject.h), renders --reproject-frames more frames and writes
+PREFIX_resolved.png (rt_resolve: every pixel divided by its own frame count) and PREFIX_history.png (that count, white =
+--frames + --reproject-frames, black = restarted).  It runs last: the other outputs show the view before the move.
 
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
@@ -51,6 +57,9 @@ def main():
     ap.add_argument("--denoise-png", metavar="FILE", help="the accumulated image through rt_denoise, as an sRGB picture")
     ap.add_argument("--denoise-iterations", type=int, help="passes of the filter, 0..8 (default: the library's)")
     ap.add_argument("--denoise-sigma", metavar="C,N,P", help="sigmaColour,sigmaNormal,sigmaPlane (default: the library's)")
+    ap.add_argument("--reproject-png", metavar="PREFIX", help="move the camera, reproject, render on; PREFIX_resolved.png and PREFIX_history.png")
+    ap.add_argument("--reproject-move", metavar="DX,DY,DZ", default="0.05,0.02,0.03", help="camera offset in world units")
+    ap.add_argument("--reproject-frames", type=int, default=4, help="frames rendered after the reprojection")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
@@ -127,6 +136,30 @@ def main():
         pkg.display.write_png(a.denoise_png, pkg.display.linear_srgb8(img))
         print(json.dumps({"denoise_png": a.denoise_png, "iterations": p.iterations, "sigma": [p.sigmaColour, p.sigmaNormal, p.sigmaPlane],
                           "demodulate": p.demodulate, "scale": p.scale, "aov_frame": a.aov_frame}))
+    if a.reproject_png:
+        import ctypes as C
+        import numpy as np
+        hip = C.CDLL("libamdhip64.so")
+        d_prev = C.c_void_p()
+        if hip.hipMalloc(C.byref(d_prev), C.c_size_t(w * h * 64)) != 0:
+            raise RuntimeError("hipMalloc failed")
+        tr.render_aov_to_device(a.aov_frame, d_prev.value, w * h * 64)
+        before = mgr.params()
+        t = mgr.camera.transform
+        offset = [float(x) for x in a.reproject_move.split(",")]
+        mgr.camera.transform = pkg.Transform(tuple(np.array(t.position) + np.array(offset)), t.euler, t.scale)
+        mgr.SetShaderParams()
+        tr.reproject_accumulated(api.reproject_params(before), d_prev.value, a.aov_frame)
+        mgr.RenderFrames(a.reproject_frames)
+        img = tr.resolve()
+        hip.hipFree(d_prev)
+        total = max(mgr.numAccumulatedFrames - 1, 1)
+        grey = np.repeat(np.clip(img[..., 3:4] / total, 0, 1) ** 2.2, 3, axis=-1).astype(np.float32)
+        pkg.display.write_png(f"{a.reproject_png}_resolved.png", pkg.display.linear_srgb8(img))
+        pkg.display.write_png(f"{a.reproject_png}_history.png", pkg.display.linear_srgb8(grey))
+        carried = img[..., 3] > a.reproject_frames
+        print(json.dumps({"reproject_png": a.reproject_png, "move": offset, "frames_after": a.reproject_frames, "pixels": int(carried.size),
+                          "carried": int(carried.sum()), "mean_history": float(img[..., 3].mean())}))
 
 
 if __name__ == "__main__":
