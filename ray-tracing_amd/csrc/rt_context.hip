@@ -179,7 +179,8 @@ struct RtContext {
     rt_order::LaunchOrder order;
     HipOrder backend;
     int lastLaunched = 0;            /* frames the last launch_frames call really enqueued (flush_pending rolls back the rest) */
-    void* dDisplay = nullptr;  /* scratch of the display pass, kept between calls (grows on demand) */
+    void* dDisplay = nullptr;  /* scratch of the display pass and of the other host reads, kept between calls (grows on demand) */
+    size_t displayBytes = 0;
     /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand); the pass's own counter
      * slot (only its watchdog word is ever written); a device pass whose watchdog word has not been read back yet */
     void* dAovOut = nullptr;
@@ -192,7 +193,6 @@ struct RtContext {
     size_t dnScratchBytes = 0;
     void* dDnAov = nullptr;
     size_t dnAovBytes = 0;
-    size_t displayBytes = 0;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     double gpuMs = 0;
     int timerState = 0; /* 0 idle, 1 begun, 2 ended (elapsed not yet read) */
@@ -273,6 +273,77 @@ static void flush_timer(RtContext* ctx)
         if (hipEventElapsedTime(&ms, ctx->evStart, ctx->evStop) == hipSuccess) ctx->gpuMs += ms;
         ctx->timerState = 0;
     }
+}
+
+/* ---- what the entry points behind the render share: targets, scratch, argument checks ------------------------------------------- */
+/* The render targets: the caller's (rt_bind_render_targets) or the context's own */
+static float* accum_target(const RtContext* ctx) { return ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum; }
+static float* frame_target(const RtContext* ctx) { return ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame; }
+static float* image_target(const RtContext* ctx, int use_accumulated) { return use_accumulated ? accum_target(ctx) : frame_target(ctx); }
+
+/* Device scratch that is kept between calls and grows on demand: *buf holds at least `bytes` bytes afterwards */
+static int grow_scratch(RtContext* ctx, void** buf, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx))); /* work still running on the stream uses the old allocation */
+    hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    HIP_TRY(ctx, hipMalloc(buf, bytes));
+    *have = bytes;
+    return RT_OK;
+}
+
+/* `p` is `bytes` bytes of 16-byte aligned device memory of the context's device (kernels write or read through it) */
+static int check_device_range(RtContext* ctx, const char* call, const char* what, const void* p, size_t bytes)
+{
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is null", call, what);
+    if ((uintptr_t)p & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", call, what);
+    hipPointerAttribute_t at;
+    void* base = nullptr;
+    size_t size = 0;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device ||
+        hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess || (const char*)p + bytes > (const char*)base + size) {
+        (void)hipGetLastError();
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is not %zu bytes of device memory on device %d", call, what, bytes, ctx->device);
+    }
+    return RT_OK;
+}
+
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
+}
+
+/* The caller's buffer for this context's rows: exactly rows x W x perPixel bytes, and a pointer where there are bytes — or always
+ * (nullIsError: the reads, the display calls and rt_write_accumulated refuse a null pointer even for a part that owns no rows) */
+static int check_rows_buffer(RtContext* ctx, const char* call, size_t perPixel, const void* p, size_t bytes, bool nullIsError = false)
+{
+    const size_t want = (size_t)ctx->localRows * ctx->W * perPixel;
+    if (bytes != want || (!p && (bytes || nullIsError)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x %zu), got %zu%s", call, want, ctx->localRows, ctx->W, perPixel, bytes,
+                    p ? "" : " and a null pointer");
+    return RT_OK;
+}
+
+/* The passes that look at a pixel's neighbours need every row.  A context that passes this one owns pixels (part 0 of 1 of an image
+ * rt_resize accepted) — unless rt_set_partition stored the whole-image partition over a part without rows and its rt_resize then failed
+ * in HIP before it recomputed localRows; for that one case the context calls behind this check still handle zero bytes. */
+static int check_whole_image(RtContext* ctx, const char* call, const char* who, const char* instead)
+{
+    if (ctx->partCount > 1)
+        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; %s needs the whole image (%s)", call, ctx->partIndex, ctx->partCount, who, instead);
+    return RT_OK;
+}
+
+/* width x height of a *_buffers call.  The limit is the caller's: rt_denoise_buffers admits one pixel less than the reprojection and resolve
+ * calls (INT32_MAX / 2 against 1 << 30).  Nothing in rt_denoise.hip's indexing (size_t throughout) asks for that; the limits are kept as they
+ * were first written. */
+static int check_image_size(RtContext* ctx, const char* call, int width, int height, long long maxPixels)
+{
+    if (width < 1 || height < 1 || (long long)width * height > maxPixels)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d x %d is not an image size (at least 1 x 1, at most 2^30 pixels)", call, width, height);
+    return RT_OK;
 }
 
 /* Stream-ordered host->device upload: the bytes are copied into a pinned staging slot now and the
@@ -540,8 +611,8 @@ int rt_get_render_targets(RtContext* ctx, void** d_frame, void** d_accum)
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     /* a host that reads the targets after its own device synchronise must find every requested frame at least launched */
     RT_FLUSH(ctx);
-    if (d_frame) *d_frame = ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame;
-    if (d_accum) *d_accum = ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum;
+    if (d_frame) *d_frame = frame_target(ctx);
+    if (d_accum) *d_accum = accum_target(ctx);
     return RT_OK;
 }
 
@@ -1463,12 +1534,11 @@ int rt_reset_accumulation(RtContext* ctx)
     RT_FLUSH(ctx);
     if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "rt_reset_accumulation before rt_resize");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float* accum = ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum;
     size_t n = (size_t)ctx->localRows * ctx->W;
     if (n) {
         int blocks = (int)((n + 255) / 256);
         if (blocks > 2048) blocks = 2048;
-        hipLaunchKernelGGL(rtk::rt_reset_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (float4*)accum, n);
+        hipLaunchKernelGGL(rtk::rt_reset_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (float4*)accum_target(ctx), n);
         HIP_TRY(ctx, hipGetLastError());
     }
     if (int rc = clear_watchdog(ctx)) return rc;
@@ -1497,8 +1567,8 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
     a.filterMaxOrigin = ctx->filterMaxOrigin;
     a.nSpheres = ctx->nSpheres;
     a.nModels = ctx->nModels;
-    a.frameRender = ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame;
-    a.accumulated = ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum;
+    a.frameRender = frame_target(ctx);
+    a.accumulated = accum_target(ctx);
     a.W = (uint32_t)ctx->W;
     a.H = (uint32_t)ctx->H;
     a.localRows = ctx->localRows;
@@ -2038,106 +2108,66 @@ int rt_timer_end(RtContext* ctx)
     return RT_OK;
 }
 
-static int read_target(RtContext* ctx, const float* src, float* rgba, size_t bytes)
+static int read_target(RtContext* ctx, int use_accumulated, float* rgba, size_t bytes)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     RT_FLUSH(ctx);
-    size_t want = (size_t)ctx->localRows * ctx->W * 16;
-    if (!rgba || bytes != want) return fail(ctx, RT_ERR_INVALID_ARG, "read: need exactly %zu bytes, got %zu", want, bytes);
+    if (int rc = check_rows_buffer(ctx, "rt_read", 16, rgba, bytes, true)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
     if (int rc = check_watchdog(ctx, ctx, "rt_read")) return rc;
-    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, src, bytes, hipMemcpyDeviceToHost));
+    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, image_target(ctx, use_accumulated), bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
-int rt_read_frame(RtContext* ctx, float* rgba, size_t bytes)
-{
-    return read_target(ctx, ctx ? (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame) : nullptr, rgba, bytes);
-}
-int rt_read_accumulated(RtContext* ctx, float* rgba, size_t bytes)
-{
-    return read_target(ctx, ctx ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : nullptr, rgba, bytes);
-}
+int rt_read_frame(RtContext* ctx, float* rgba, size_t bytes) { return read_target(ctx, 0, rgba, bytes); }
+int rt_read_accumulated(RtContext* ctx, float* rgba, size_t bytes) { return read_target(ctx, 1, rgba, bytes); }
 
 /* ---- display pass + checkpoint ------------------------------------------------ */
-static int display_common(RtContext* ctx, int frame, int use_accumulated, const float** src)
+/* rt_display (srgb8 = false: RGBA32F) and rt_display_srgb8 (RGBA8, optionally flipped): they differ in the kernel and the pixel size */
+static int display_pass(RtContext* ctx, const char* call, bool srgb8, int frame, int use_accumulated, int flip_y, void* out, size_t bytes)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     RT_FLUSH(ctx);
     if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "display before rt_resize");
     if (frame == 0) return fail(ctx, RT_ERR_INVALID_ARG, "display: Frame must not be 0");
-    *src = use_accumulated ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame);
-    return RT_OK;
-}
-
-static int display_scratch(RtContext* ctx, size_t bytes, void** out)
-{
-    if (ctx->displayBytes < bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-        hipFree(ctx->dDisplay);
-        ctx->dDisplay = nullptr;
-        ctx->displayBytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dDisplay, bytes));
-        ctx->displayBytes = bytes;
-    }
-    *out = ctx->dDisplay;
+    int rc = check_rows_buffer(ctx, call, srgb8 ? 4 : 16, out, bytes, true);
+    if (rc) return rc;
+    const size_t n = (size_t)ctx->localRows * ctx->W;
+    if (n == 0) return RT_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
+    int blocks = (int)((n + 255) / 256);
+    if (blocks > 4096) blocks = 4096;
+    const float4* src = (const float4*)image_target(ctx, use_accumulated);
+    if (srgb8) hipLaunchKernelGGL(rtk::rt_display_srgb8_kernel, dim3(blocks), dim3(256), 0, joined(ctx), src, (uint32_t*)ctx->dDisplay, ctx->W, ctx->localRows, frame, flip_y);
+    else hipLaunchKernelGGL(rtk::rt_display_kernel, dim3(blocks), dim3(256), 0, joined(ctx), src, (float4*)ctx->dDisplay, n, frame);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(joined(ctx));
+    if (e == hipSuccess && (rc = check_watchdog(ctx, ctx, call))) return rc;
+    if (e == hipSuccess) e = hipMemcpy(out, ctx->dDisplay, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "%s: %s", call, hipGetErrorString(e));
     return RT_OK;
 }
 
 int rt_display(RtContext* ctx, int frame, int use_accumulated, float* rgba, size_t bytes)
 {
-    const float* src = nullptr;
-    int rc = display_common(ctx, frame, use_accumulated, &src);
-    if (rc) return rc;
-    const size_t n = (size_t)ctx->localRows * ctx->W;
-    if (!rgba || bytes != n * 16) return fail(ctx, RT_ERR_INVALID_ARG, "rt_display: need exactly %zu bytes", n * 16);
-    if (n == 0) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float4* tmp = nullptr;
-    if ((rc = display_scratch(ctx, bytes, (void**)&tmp))) return rc;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(rtk::rt_display_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (const float4*)src, tmp, n, frame);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(joined(ctx));
-    if (e == hipSuccess && (rc = check_watchdog(ctx, ctx, "rt_display"))) return rc;
-    if (e == hipSuccess) e = hipMemcpy(rgba, tmp, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_display: %s", hipGetErrorString(e));
-    return RT_OK;
+    return display_pass(ctx, "rt_display", false, frame, use_accumulated, 0, rgba, bytes);
 }
 
 int rt_display_srgb8(RtContext* ctx, int frame, int use_accumulated, int flip_y, uint8_t* rgba8, size_t bytes)
 {
-    const float* src = nullptr;
-    int rc = display_common(ctx, frame, use_accumulated, &src);
-    if (rc) return rc;
-    const size_t n = (size_t)ctx->localRows * ctx->W;
-    if (!rgba8 || bytes != n * 4) return fail(ctx, RT_ERR_INVALID_ARG, "rt_display_srgb8: need exactly %zu bytes", n * 4);
-    if (n == 0) return RT_OK;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t* tmp = nullptr;
-    if ((rc = display_scratch(ctx, bytes, (void**)&tmp))) return rc;
-    int blocks = (int)((n + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(rtk::rt_display_srgb8_kernel, dim3(blocks), dim3(256), 0, joined(ctx), (const float4*)src, tmp, ctx->W, ctx->localRows, frame, flip_y);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(joined(ctx));
-    if (e == hipSuccess && (rc = check_watchdog(ctx, ctx, "rt_display_srgb8"))) return rc;
-    if (e == hipSuccess) e = hipMemcpy(rgba8, tmp, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(ctx, RT_ERR_HIP, "rt_display_srgb8: %s", hipGetErrorString(e));
-    return RT_OK;
+    return display_pass(ctx, "rt_display_srgb8", true, frame, use_accumulated, flip_y, rgba8, bytes);
 }
 
 int rt_write_accumulated(RtContext* ctx, const float* rgba, size_t bytes)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     RT_FLUSH(ctx);
-    const size_t want = (size_t)ctx->localRows * ctx->W * 16;
-    if (!rgba || bytes != want) return fail(ctx, RT_ERR_INVALID_ARG, "rt_write_accumulated: need exactly %zu bytes, got %zu", want, bytes);
+    if (int rc = check_rows_buffer(ctx, "rt_write_accumulated", 16, rgba, bytes, true)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    if (bytes) HIP_TRY(ctx, hipMemcpy(ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum, rgba, bytes, hipMemcpyHostToDevice));
+    if (bytes) HIP_TRY(ctx, hipMemcpy(accum_target(ctx), rgba, bytes, hipMemcpyHostToDevice));
     return clear_watchdog(ctx); /* the accumulated image is the caller's checkpoint now */
 }
 
@@ -2167,25 +2197,36 @@ int rt_reset_counters(RtContext* ctx)
     return RT_OK;
 }
 
+/* After a synchronise of the joined stream: the whole counter block on the host; sum_field adds one field up over the slots */
+static int read_counter_block(RtContext* ctx, std::vector<unsigned long long>& h)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    h.resize((size_t)RT_COUNTER_SLOTS * RT_COUNTER_FIELDS);
+    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dCounters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+static unsigned long long sum_field(const std::vector<unsigned long long>& h, int f)
+{
+    unsigned long long sum = 0;
+    for (int s = 0; s < RT_COUNTER_SLOTS; s++) sum += h[(size_t)s * RT_COUNTER_FIELDS + f];
+    return sum;
+}
+
 int rt_get_counters(RtContext* ctx, RtCounters* out)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     RT_FLUSH(ctx);
     if (!out) return fail(ctx, RT_ERR_INVALID_ARG, "rt_get_counters: null out");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    std::vector<unsigned long long> h;
+    if (int rc = read_counter_block(ctx, h)) return rc;
     flush_timer(ctx);
-    std::vector<unsigned long long> h((size_t)RT_COUNTER_SLOTS * RT_COUNTER_FIELDS);
-    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dCounters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    unsigned long long sum[RT_COUNTER_FIELDS] = {0};
-    for (int s = 0; s < RT_COUNTER_SLOTS; s++)
-        for (int f = 0; f < RT_COUNTER_FIELDS; f++) sum[f] += h[(size_t)s * RT_COUNTER_FIELDS + f];
-    out->segments = sum[0];
-    out->innerSteps = sum[1];
-    out->leafSteps = sum[2];
-    out->triTests = sum[3];
-    out->sphereTests = sum[4];
-    out->modelVisits = sum[5];
+    out->segments = sum_field(h, 0);
+    out->innerSteps = sum_field(h, 1);
+    out->leafSteps = sum_field(h, 2);
+    out->triTests = sum_field(h, 3);
+    out->sphereTests = sum_field(h, 4);
+    out->modelVisits = sum_field(h, 5);
     out->pixelFrames = ctx->pixelFrames;
     out->gpuMs = ctx->gpuMs;
     /* word 7 = the watchdogs (rt_kernels.h): traverse — a wave ended its lanes' walks because no validated scene needs that many steps; pool_exchange — a wave
@@ -2203,25 +2244,13 @@ int rt_debug_phase_profile(RtContext* ctx, uint64_t* out, int n)
 {
     if (!ctx || !out || n < 2 * RT_N_PHASES) return fail(ctx, RT_ERR_INVALID_ARG, "rt_debug_phase_profile: need %d entries", 2 * RT_N_PHASES);
     RT_FLUSH(ctx);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    std::vector<unsigned long long> h((size_t)RT_COUNTER_SLOTS * RT_COUNTER_FIELDS);
-    HIP_TRY(ctx, hipMemcpy(h.data(), ctx->dCounters, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    for (int f = 0; f < 2 * RT_N_PHASES; f++) {
-        out[f] = 0;
-        for (int s = 0; s < RT_COUNTER_SLOTS; s++) out[f] += h[(size_t)s * RT_COUNTER_FIELDS + 8 + f];
-    }
-    if (n > 2 * RT_N_PHASES) { /* audit of the conservative root filter: must be 0 */
-        out[2 * RT_N_PHASES] = 0;
-        for (int s = 0; s < RT_COUNTER_SLOTS; s++) out[2 * RT_N_PHASES] += h[(size_t)s * RT_COUNTER_FIELDS + 6];
-    }
+    std::vector<unsigned long long> h;
+    if (int rc = read_counter_block(ctx, h)) return rc;
+    for (int f = 0; f < 2 * RT_N_PHASES; f++) out[f] = sum_field(h, 8 + f);
+    if (n > 2 * RT_N_PHASES) out[2 * RT_N_PHASES] = sum_field(h, 6); /* audit of the conservative root filter: must be 0 */
     /* then: inner steps served by the LDS top-of-tree cache; inner steps (lane-steps) taken while >= 48 lanes of the wave stood on ONE node;
      * the same for >= 3/4 of >= 16 active lanes; the rest 0 */
-    for (int p = 0; p < RT_N_PHASES && 2 * RT_N_PHASES + 1 + p < n; p++) {
-        out[2 * RT_N_PHASES + 1 + p] = 0;
-        if (p < 3)
-            for (int s = 0; s < RT_COUNTER_SLOTS; s++) out[2 * RT_N_PHASES + 1 + p] += h[(size_t)s * RT_COUNTER_FIELDS + 8 + 2 * RT_N_PHASES + p];
-    }
+    for (int p = 0; p < RT_N_PHASES && 2 * RT_N_PHASES + 1 + p < n; p++) out[2 * RT_N_PHASES + 1 + p] = p < 3 ? sum_field(h, 8 + 2 * RT_N_PHASES + p) : 0;
     return RT_OK;
 }
 
@@ -2278,6 +2307,24 @@ int rt_debug_math_eval(RtContext* ctx, int op, const float* x, const float* y, f
     return RT_OK;
 }
 
+/* ---- the passes that trace as single waves (rt_render_cost, the AOV pass): no top-of-tree cache, no chain pool --------------------
+ * The KArgs fields of that form, the LDS attribute a wave region above 48 KB needs, and *residentWaves = every wave the device keeps
+ * resident.  waveLdsBytes is the caller's: the cost kernel's FLAT form keeps its pixel records in LDS (rt_plan::launch_shape adds them),
+ * the AOV kernel has none (rt_plan::wave_lds_bytes). */
+static int single_wave_pass(RtContext* ctx, const void* kern, size_t waveLdsBytes, KArgs& a, long long* residentWaves)
+{
+    a.wavesPerGroup = 1;
+    a.hotUnits = 0;
+    a.poolCells = 0;
+    a.waveLdsDwords = (int)(waveLdsBytes / sizeof(uint32_t));
+    a.stackEntries = ctx->stackEntries;
+    if (waveLdsBytes > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)waveLdsBytes));
+    int perCU = 0;
+    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, RT_WAVE, waveLdsBytes));
+    *residentWaves = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs;
+    return RT_OK;
+}
+
 /* ---- rt_render_cost (include/rt_cost.h): per-pixel work of one frame ----------------------
  * The stats build of the trace kernel in its single-wave, unpooled form without the top-of-tree cache (rt_kernels.h, rt_cost_kernel):
  * one lane owns a pixel from set-up to finish, so the lane's exact counters between the two are that pixel's.  The launch is the
@@ -2290,10 +2337,7 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     if (frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_cost: frame %d < 1 (the first frame after a reset is 1)", frame);
     int rc = check_renderable(ctx);
     if (rc) return rc;
-    const size_t nPix = (size_t)ctx->localRows * ctx->W;
-    if (bytes != nPix * sizeof(RtPixelCost) || (bytes && !out))
-        return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_cost: need exactly %zu bytes (%d rows x %d x %zu), got %zu", nPix * sizeof(RtPixelCost), ctx->localRows, ctx->W,
-                    sizeof(RtPixelCost), bytes);
+    if ((rc = check_rows_buffer(ctx, "rt_render_cost", sizeof(RtPixelCost), out, bytes))) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
     KArgs a;
@@ -2309,21 +2353,15 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     sc.numCUs = ctx->numCUs;
     const rt_plan::LaunchShape sh = rt_plan::launch_shape(sc, tiles, 1);
     void (*kern)(const KArgs, uint32_t*) = sh.many ? rtk::rt_cost_kernel<false, true> : ctx->flatScene ? rtk::rt_cost_kernel<true, false> : rtk::rt_cost_kernel<false, false>;
-    a.wavesPerGroup = 1;
-    a.hotUnits = 0;
-    a.poolCells = 0;
-    a.waveLdsDwords = sh.waveLdsDwords;
-    a.stackEntries = ctx->stackEntries;
     a.suspendNum = ctx->tuner.decided; /* scheduling only: the counts of a ray do not depend on it */
-    if (sh.ldsBytes > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.ldsBytes));
-    int perCU = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, sh.blockThreads, sh.ldsBytes));
+    long long resident = 0;
+    if ((rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), sh.ldsBytes, a, &resident))) return rc; /* (one wave per group: the group's LDS is the wave's) */
     rt_plan::Work w;
     w.tiles = tiles;
     w.nFrames = 1;
     w.flat = ctx->flatScene;
     w.spp = ctx->params.numRaysPerPixel;
-    w.residentGroups = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs;
+    w.residentGroups = resident;
     w.wavesPerGroup = 1;
     const rt_plan::PartPlan pp = rt_plan::plan_part(w, 0, 1, 0ull); /* one kernel, a tile counter that starts at 0 */
     a.tileOrder = nullptr;
@@ -2349,7 +2387,7 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     hipStream_t st = joined(ctx);
     HIP_TRY(ctx, hipMemsetAsync(words, 0, sizeof(unsigned long long) * (RT_COUNTER_FIELDS + 1), st));
     HIP_TRY(ctx, hipMemsetAsync(dOut.p, 0, bytes, st));
-    hipLaunchKernelGGL(kern, dim3(pp.grid), dim3(sh.blockThreads), sh.ldsBytes, st, a, (uint32_t*)dOut.p);
+    hipLaunchKernelGGL(kern, dim3(pp.grid), dim3(RT_WAVE), sh.ldsBytes, st, a, (uint32_t*)dOut.p);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipStreamSynchronize(st));
     unsigned long long fired = 0;
@@ -2365,21 +2403,16 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
  * frame `frame`, a counter slot of its own (ctx->dAovWords; traverse() only ever writes its watchdog word), no render target, no tile
  * queue, no pixel records.  So RtCounters and the context's watchdog word stay as they are, and a watchdog that fires here fails this
  * pass only. */
-static int aov_enqueue(RtContext* ctx, int frame, void* dOut, size_t bytes)
+static int aov_enqueue(RtContext* ctx, int frame, void* dOut)
 {
     KArgs a;
     fill_args(ctx, frame, 1, a);
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
-    const bool many = ctx->nChunks > 0 && !ctx->flatScene; /* rt_plan::launch_shape's rule */
+    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
     void (*kern)(const KArgs, float4*, const uint32_t*) = many ? rtk::rt_aov_kernel<false, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false> : rtk::rt_aov_kernel<false, false>;
     /* a wave region of the trace kernel, single waves, no cache, no pool */
     const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
-    a.wavesPerGroup = 1;
-    a.hotUnits = 0;
-    a.poolCells = 0;
-    a.waveLdsDwords = (int)(ldsBytes / sizeof(uint32_t));
-    a.stackEntries = ctx->stackEntries;
     a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
     a.frameRender = nullptr;
     a.accumulated = nullptr;
@@ -2390,26 +2423,31 @@ static int aov_enqueue(RtContext* ctx, int frame, void* dOut, size_t bytes)
     a.staging = nullptr;
     if (!ctx->dAovWords) HIP_TRY(ctx, hipMalloc(&ctx->dAovWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
     a.counters = ctx->dAovWords;
-    if (ldsBytes > 48 * 1024) HIP_TRY(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsBytes));
-    int perCU = 0;
-    HIP_TRY(ctx, hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, kern, RT_WAVE, ldsBytes));
-    long long grid = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs; /* every wave the device keeps resident; the tiles are strided over them */
+    long long grid = 0; /* every wave the device keeps resident; the tiles are strided over them */
+    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &grid)) return rc;
     if (grid > tiles) grid = tiles;
     hipStream_t st = joined(ctx);
     HIP_TRY(ctx, hipMemsetAsync(ctx->dAovWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (float4*)dOut, (const uint32_t*)ctx->dUnitTri);
     HIP_TRY(ctx, hipGetLastError());
-    (void)bytes;
     return RT_OK;
 }
 
-/* After a synchronise of the stream: the watchdog word of a device pass that has not been reported yet (8 bytes read back) */
+/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
+static int aov_fired(RtContext* ctx, unsigned long long* fired)
+{
+    *fired = 0;
+    HIP_TRY(ctx, hipMemcpy(fired, ctx->dAovWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the report of a device pass that has not been reported yet */
 static int aov_report(RtContext* ctx, const char* call)
 {
     if (!ctx->aovUnreported) return RT_OK;
     ctx->aovUnreported = false;
     unsigned long long fired = 0;
-    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if (int rc = aov_fired(ctx, &fired)) return rc;
     if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call: "
                            "walks were cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
     return RT_OK;
@@ -2421,11 +2459,7 @@ static int aov_check_args(RtContext* ctx, const char* call, int frame, const voi
     if (frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame %d < 1 (the first frame after a reset is 1)", call, frame);
     int rc = check_renderable(ctx);
     if (rc) return rc;
-    const size_t nPix = (size_t)ctx->localRows * ctx->W;
-    if (bytes != nPix * sizeof(RtPixelAov) || (bytes && !out))
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x %zu), got %zu%s", call, nPix * sizeof(RtPixelAov), ctx->localRows, ctx->W,
-                    sizeof(RtPixelAov), bytes, out ? "" : " and a null pointer");
-    return RT_OK;
+    return check_rows_buffer(ctx, call, sizeof(RtPixelAov), out, bytes);
 }
 
 /* a device pass still unreported: synchronise and report it before this call's own pass clears the word */
@@ -2444,18 +2478,11 @@ int rt_render_aov(RtContext* ctx, int frame, RtPixelAov* out, size_t bytes)
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, "rt_render_aov"))) return rc;
     if (!bytes) return RT_OK;
-    if (ctx->aovOutBytes < bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-        hipFree(ctx->dAovOut);
-        ctx->dAovOut = nullptr;
-        ctx->aovOutBytes = 0;
-        HIP_TRY(ctx, hipMalloc(&ctx->dAovOut, bytes));
-        ctx->aovOutBytes = bytes;
-    }
-    if ((rc = aov_enqueue(ctx, frame, ctx->dAovOut, bytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dAovOut, &ctx->aovOutBytes, bytes))) return rc;
+    if ((rc = aov_enqueue(ctx, frame, ctx->dAovOut))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     unsigned long long fired = 0;
-    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if ((rc = aov_fired(ctx, &fired))) return rc;
     if (fired) return watchdog_failure(ctx, "rt_render_aov", fired);
     HIP_TRY(ctx, hipMemcpy(out, ctx->dAovOut, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -2467,20 +2494,11 @@ int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes
     if (rc) return rc;
     if ((uintptr_t)d_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_aov_to_device: the records must be 16-byte aligned");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes) { /* the kernel writes through this pointer: it must be device memory of this context's device that holds `bytes` bytes */
-        hipPointerAttribute_t at;
-        void* base = nullptr;
-        size_t size = 0;
-        if (hipPointerGetAttributes(&at, d_out) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device ||
-            hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)d_out) != hipSuccess || (const char*)d_out + bytes > (const char*)base + size) {
-            (void)hipGetLastError();
-            return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_aov_to_device: d_out is not %zu bytes of device memory on device %d", bytes, ctx->device);
-        }
-    }
+    if (bytes && (rc = check_device_range(ctx, "rt_render_aov_to_device", "d_out", d_out, bytes))) return rc; /* the kernel writes through this pointer */
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, "rt_render_aov_to_device"))) return rc;
     if (!bytes) return RT_OK;
-    if ((rc = aov_enqueue(ctx, frame, d_out, bytes))) return rc;
+    if ((rc = aov_enqueue(ctx, frame, d_out))) return rc;
     ctx->aovUnreported = true;
     return RT_OK;
 }
@@ -2489,7 +2507,7 @@ int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main
  * stream.  The two context calls run the AOV pass of rt_render_aov_to_device into library-owned records first, with that pass's own
  * watchdog word and its reporting. */
-static int dn_check_params(RtContext* ctx, const char* call, const RtDenoiseParams* p, rt_dn::Job* job)
+static int denoise_check_params(RtContext* ctx, const char* call, const RtDenoiseParams* p, rt_dn::Job* job)
 {
     if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: null parameters", call);
     if (p->struct_size != sizeof(RtDenoiseParams))
@@ -2513,53 +2531,6 @@ static int dn_check_params(RtContext* ctx, const char* call, const RtDenoisePara
     return RT_OK;
 }
 
-static int dn_check_whole_image(RtContext* ctx, const char* call)
-{
-    if (ctx->partCount > 1)
-        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; the filter needs the whole image (gather, then rt_denoise_buffers)",
-                    call, ctx->partIndex, ctx->partCount);
-    return RT_OK;
-}
-
-/* `bytes` bytes of 16-byte aligned device memory of the context's device */
-static int dn_check_device_range(RtContext* ctx, const char* call, const char* what, const void* p, size_t bytes)
-{
-    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is null", call, what);
-    if ((uintptr_t)p & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s must be 16-byte aligned", call, what);
-    hipPointerAttribute_t at;
-    void* base = nullptr;
-    size_t size = 0;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device ||
-        hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess || (const char*)p + bytes > (const char*)base + size) {
-        (void)hipGetLastError();
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is not %zu bytes of device memory on device %d", call, what, bytes, ctx->device);
-    }
-    return RT_OK;
-}
-
-/* the image the two context calls filter */
-static const float* dn_source(const RtContext* ctx, int use_accumulated)
-{
-    return use_accumulated ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame);
-}
-
-static bool dn_overlap(const void* a, size_t na, const void* b, size_t nb)
-{
-    return (const char*)a < (const char*)b + nb && (const char*)b < (const char*)a + na;
-}
-
-static int dn_grow(RtContext* ctx, void** buf, size_t* have, size_t bytes)
-{
-    if (*have >= bytes) return RT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx))); /* a filter still running reads the old allocation */
-    hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    HIP_TRY(ctx, hipMalloc(buf, bytes));
-    *have = bytes;
-    return RT_OK;
-}
-
 int rt_denoise_default_params(RtDenoiseParams* out)
 {
     if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_denoise_default_params: out is null");
@@ -2579,20 +2550,19 @@ int rt_denoise_buffers(RtContext* ctx, const RtDenoiseParams* p, int width, int 
     static const char* call = "rt_denoise_buffers";
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     rt_dn::Job job;
-    int rc = dn_check_params(ctx, call, p, &job);
+    int rc = denoise_check_params(ctx, call, p, &job);
     if (rc) return rc;
-    if (width < 1 || height < 1 || (long long)width * height > (long long)INT32_MAX / 2)
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d x %d is not an image size (at least 1 x 1, at most 2^30 pixels)", call, width, height);
-    if ((rc = dn_check_whole_image(ctx, call))) return rc;
+    if ((rc = check_image_size(ctx, call, width, height, (long long)INT32_MAX / 2))) return rc;
+    if ((rc = check_whole_image(ctx, call, "the filter", "gather, then rt_denoise_buffers"))) return rc;
     const size_t n = (size_t)width * height;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = dn_check_device_range(ctx, call, "d_rgba_in", d_rgba_in, n * 16))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_aov", d_aov, n * sizeof(RtPixelAov)))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
-    if (dn_overlap(d_rgba_out, n * 16, d_rgba_in, n * 16) || dn_overlap(d_rgba_out, n * 16, d_aov, n * sizeof(RtPixelAov)))
+    if ((rc = check_device_range(ctx, call, "d_rgba_in", d_rgba_in, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_aov", d_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
+    if (ranges_overlap(d_rgba_out, n * 16, d_rgba_in, n * 16) || ranges_overlap(d_rgba_out, n * 16, d_aov, n * sizeof(RtPixelAov)))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba_out overlaps an input", call);
     RT_FLUSH(ctx);
-    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
     job.W = width;
     job.H = height;
     HIP_TRY(ctx, rt_dn::enqueue(joined(ctx), job, d_rgba_in, d_aov, d_rgba_out, ctx->dDnScratch));
@@ -2600,30 +2570,28 @@ int rt_denoise_buffers(RtContext* ctx, const RtDenoiseParams* p, int width, int 
 }
 
 /* what rt_denoise and rt_denoise_to_device share: checks, the AOV pass, the filter from the context's image into dOut (device) */
-static int dn_check_context_call(RtContext* ctx, const char* call, const RtDenoiseParams* p, int aov_frame, const void* out, size_t bytes, rt_dn::Job* job)
+static int denoise_check_context_call(RtContext* ctx, const char* call, const RtDenoiseParams* p, int aov_frame, const void* out, size_t bytes, rt_dn::Job* job)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
-    int rc = dn_check_params(ctx, call, p, job);
+    int rc = denoise_check_params(ctx, call, p, job);
     if (rc) return rc;
     if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
     if ((rc = check_renderable(ctx))) return rc;
-    if ((rc = dn_check_whole_image(ctx, call))) return rc;
-    const size_t want = (size_t)ctx->localRows * ctx->W * 16;
-    if (bytes != want || (bytes && !out))
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x 16), got %zu%s", call, want, ctx->localRows, ctx->W, bytes, out ? "" : " and a null pointer");
+    if ((rc = check_whole_image(ctx, call, "the filter", "gather, then rt_denoise_buffers"))) return rc;
+    if ((rc = check_rows_buffer(ctx, call, 16, out, bytes))) return rc;
     job->W = ctx->W;
     job->H = ctx->localRows;
     return RT_OK;
 }
 
-static int dn_enqueue_context_call(RtContext* ctx, const rt_dn::Job& job, int use_accumulated, int aov_frame, void* dOut)
+static int denoise_enqueue_context_call(RtContext* ctx, const rt_dn::Job& job, int use_accumulated, int aov_frame, void* dOut)
 {
     const size_t n = (size_t)job.W * job.H;
     int rc;
-    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
-    if ((rc = dn_grow(ctx, &ctx->dDnAov, &ctx->dnAovBytes, n * sizeof(RtPixelAov)))) return rc;
-    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov, n * sizeof(RtPixelAov)))) return rc;
-    HIP_TRY(ctx, rt_dn::enqueue(joined(ctx), job, dn_source(ctx, use_accumulated), ctx->dDnAov, dOut, ctx->dDnScratch));
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_dn::scratch_bytes(n)))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnAov, &ctx->dnAovBytes, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov))) return rc;
+    HIP_TRY(ctx, rt_dn::enqueue(joined(ctx), job, image_target(ctx, use_accumulated), ctx->dDnAov, dOut, ctx->dDnScratch));
     return RT_OK;
 }
 
@@ -2631,22 +2599,21 @@ int rt_denoise(RtContext* ctx, const RtDenoiseParams* p, int use_accumulated, in
 {
     static const char* call = "rt_denoise";
     rt_dn::Job job;
-    int rc = dn_check_context_call(ctx, call, p, aov_frame, rgba, bytes, &job);
+    int rc = denoise_check_context_call(ctx, call, p, aov_frame, rgba, bytes, &job);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, call))) return rc;
     if (!bytes) return RT_OK;
-    void* dOut = nullptr;
-    if ((rc = display_scratch(ctx, bytes, &dOut))) return rc;
-    if ((rc = dn_enqueue_context_call(ctx, job, use_accumulated, aov_frame, dOut))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
+    if ((rc = denoise_enqueue_context_call(ctx, job, use_accumulated, aov_frame, ctx->dDisplay))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
     unsigned long long fired = 0;
-    HIP_TRY(ctx, hipMemcpy(&fired, ctx->dAovWords + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
+    if ((rc = aov_fired(ctx, &fired))) return rc;
     if (fired) return watchdog_failure(ctx, call, fired);
     if ((rc = check_watchdog(ctx, ctx, call))) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgba, dOut, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -2654,19 +2621,19 @@ int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accum
 {
     static const char* call = "rt_denoise_to_device";
     rt_dn::Job job;
-    int rc = dn_check_context_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
+    int rc = denoise_check_context_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (bytes) {
-        if ((rc = dn_check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
-        if (dn_overlap(d_rgba, bytes, dn_source(ctx, use_accumulated), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the source image", call);
+        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+        if (ranges_overlap(d_rgba, bytes, image_target(ctx, use_accumulated), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the source image", call);
     } else if ((uintptr_t)d_rgba & 15) {
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
     }
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, call))) return rc;
     if (!bytes) return RT_OK;
-    if ((rc = dn_enqueue_context_call(ctx, job, use_accumulated, aov_frame, d_rgba))) return rc;
+    if ((rc = denoise_enqueue_context_call(ctx, job, use_accumulated, aov_frame, d_rgba))) return rc;
     ctx->aovUnreported = true;
     return RT_OK;
 }
@@ -2677,7 +2644,7 @@ int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accum
  * of every frame requested later, which is how rt_reset_accumulation and rt_write_accumulated order their write of the accumulator.
  * The scratch is the denoiser's: its colour images hold the reprojected image, its records the current view's; both are only ever used
  * by work on this one stream. */
-static int rp_check_params(RtContext* ctx, const char* call, const RtReprojectParams* p, rt_rp_job* job)
+static int reproject_check_params(RtContext* ctx, const char* call, const RtReprojectParams* p, rt_rp_job* job)
 {
     if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: null parameters", call);
     if (p->struct_size != sizeof(RtReprojectParams))
@@ -2703,15 +2670,6 @@ static int rp_check_params(RtContext* ctx, const char* call, const RtReprojectPa
     return RT_OK;
 }
 
-static int rp_check_size(RtContext* ctx, const char* call, int width, int height)
-{
-    if (width < 1 || height < 1 || (long long)width * height > (1ll << 30))
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: %d x %d is not an image size (at least 1 x 1, at most 2^30 pixels)", call, width, height);
-    return RT_OK;
-}
-
-static float* rp_accum(const RtContext* ctx) { return ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum; }
-
 int rt_reproject_default_params(RtReprojectParams* out)
 {
     if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_reproject_default_params: out is null");
@@ -2729,20 +2687,18 @@ int rt_reproject_buffers(RtContext* ctx, const RtReprojectParams* p, int width, 
     static const char* call = "rt_reproject_buffers";
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     rt_rp_job job;
-    int rc = rp_check_params(ctx, call, p, &job);
+    int rc = reproject_check_params(ctx, call, p, &job);
     if (rc) return rc;
-    if ((rc = rp_check_size(ctx, call, width, height))) return rc;
-    if (ctx->partCount > 1)
-        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; reprojection needs the whole image (gather first)", call, ctx->partIndex,
-                    ctx->partCount);
+    if ((rc = check_image_size(ctx, call, width, height, 1ll << 30))) return rc;
+    if ((rc = check_whole_image(ctx, call, "reprojection", "gather first"))) return rc;
     const size_t n = (size_t)width * height;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = dn_check_device_range(ctx, call, "d_prev_rgba", d_prev_rgba, n * 16))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_prev_aov", d_prev_aov, n * sizeof(RtPixelAov)))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_cur_aov", d_cur_aov, n * sizeof(RtPixelAov)))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_out_rgba", d_out_rgba, n * 16))) return rc;
-    if (dn_overlap(d_out_rgba, n * 16, d_prev_rgba, n * 16) || dn_overlap(d_out_rgba, n * 16, d_prev_aov, n * sizeof(RtPixelAov)) ||
-        dn_overlap(d_out_rgba, n * 16, d_cur_aov, n * sizeof(RtPixelAov)))
+    if ((rc = check_device_range(ctx, call, "d_prev_rgba", d_prev_rgba, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_prev_aov", d_prev_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_cur_aov", d_cur_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_out_rgba", d_out_rgba, n * 16))) return rc;
+    if (ranges_overlap(d_out_rgba, n * 16, d_prev_rgba, n * 16) || ranges_overlap(d_out_rgba, n * 16, d_prev_aov, n * sizeof(RtPixelAov)) ||
+        ranges_overlap(d_out_rgba, n * 16, d_cur_aov, n * sizeof(RtPixelAov)))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_out_rgba overlaps an input", call);
     RT_FLUSH(ctx);
     job.W = width;
@@ -2756,36 +2712,34 @@ int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const v
     static const char* call = "rt_reproject_accumulated";
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     rt_rp_job job;
-    int rc = rp_check_params(ctx, call, p, &job);
+    int rc = reproject_check_params(ctx, call, p, &job);
     if (rc) return rc;
     if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
     if ((rc = check_renderable(ctx))) return rc;
-    if (ctx->partCount > 1)
-        return fail(ctx, RT_ERR_STATE, "%s: this context owns part %d of %d of the image; reprojection needs the whole image (gather, then rt_reproject_buffers)", call,
-                    ctx->partIndex, ctx->partCount);
+    if ((rc = check_whole_image(ctx, call, "reprojection", "gather, then rt_reproject_buffers"))) return rc;
     job.W = ctx->W;
     job.H = ctx->localRows;
     const size_t n = (size_t)job.W * job.H, recBytes = n * sizeof(RtPixelAov);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    float* const accum = rp_accum(ctx);
+    float* const accum = accum_target(ctx);
     if (!d_prev_aov) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov is null", call);
     if ((uintptr_t)d_prev_aov & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov must be 16-byte aligned", call);
     if ((uintptr_t)d_cur_aov_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_cur_aov_out must be 16-byte aligned", call);
     if (n) {
-        if ((rc = dn_check_device_range(ctx, call, "d_prev_aov", d_prev_aov, recBytes))) return rc;
-        if (dn_overlap(d_prev_aov, recBytes, accum, n * 16)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov overlaps AccumulatedRender", call);
+        if ((rc = check_device_range(ctx, call, "d_prev_aov", d_prev_aov, recBytes))) return rc;
+        if (ranges_overlap(d_prev_aov, recBytes, accum, n * 16)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_prev_aov overlaps AccumulatedRender", call);
         if (d_cur_aov_out) {
-            if ((rc = dn_check_device_range(ctx, call, "d_cur_aov_out", d_cur_aov_out, recBytes))) return rc;
-            if (dn_overlap(d_cur_aov_out, recBytes, d_prev_aov, recBytes) || dn_overlap(d_cur_aov_out, recBytes, accum, n * 16))
+            if ((rc = check_device_range(ctx, call, "d_cur_aov_out", d_cur_aov_out, recBytes))) return rc;
+            if (ranges_overlap(d_cur_aov_out, recBytes, d_prev_aov, recBytes) || ranges_overlap(d_cur_aov_out, recBytes, accum, n * 16))
                 return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_cur_aov_out overlaps d_prev_aov or AccumulatedRender", call);
         }
     }
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, call))) return rc;
     if (!n) return RT_OK;
-    if ((rc = dn_grow(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, n * 16))) return rc;
-    if ((rc = dn_grow(ctx, &ctx->dDnAov, &ctx->dnAovBytes, recBytes))) return rc;
-    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov, recBytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, n * 16))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnAov, &ctx->dnAovBytes, recBytes))) return rc;
+    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov))) return rc;
     ctx->aovUnreported = true;
     hipStream_t st = joined(ctx);
     if (d_cur_aov_out) HIP_TRY(ctx, hipMemcpyAsync(d_cur_aov_out, ctx->dDnAov, recBytes, hipMemcpyDeviceToDevice, st));
@@ -2799,40 +2753,36 @@ int rt_resolve_buffers(RtContext* ctx, int width, int height, const void* d_rgba
 {
     static const char* call = "rt_resolve_buffers";
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
-    int rc = rp_check_size(ctx, call, width, height);
+    int rc = check_image_size(ctx, call, width, height, 1ll << 30);
     if (rc) return rc;
     const size_t n = (size_t)width * height;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((rc = dn_check_device_range(ctx, call, "d_rgba_sum", d_rgba_sum, n * 16))) return rc;
-    if ((rc = dn_check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
-    if (d_rgba_out != d_rgba_sum && dn_overlap(d_rgba_out, n * 16, d_rgba_sum, n * 16))
+    if ((rc = check_device_range(ctx, call, "d_rgba_sum", d_rgba_sum, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
+    if (d_rgba_out != d_rgba_sum && ranges_overlap(d_rgba_out, n * 16, d_rgba_sum, n * 16))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba_out overlaps d_rgba_sum without being it (in place means the same pointer)", call);
     RT_FLUSH(ctx);
     HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), d_rgba_sum, d_rgba_out, n));
     return RT_OK;
 }
 
-static int rp_check_resolve_call(RtContext* ctx, const char* call, const void* out, size_t bytes)
+static int resolve_check_call(RtContext* ctx, const char* call, const void* out, size_t bytes)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "%s before rt_resize", call);
-    const size_t want = (size_t)ctx->localRows * ctx->W * 16;
-    if (bytes != want || (bytes && !out))
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x 16), got %zu%s", call, want, ctx->localRows, ctx->W, bytes, out ? "" : " and a null pointer");
-    return RT_OK;
+    return check_rows_buffer(ctx, call, 16, out, bytes);
 }
 
 int rt_resolve(RtContext* ctx, float* rgba, size_t bytes)
 {
     static const char* call = "rt_resolve";
-    int rc = rp_check_resolve_call(ctx, call, rgba, bytes);
+    int rc = resolve_check_call(ctx, call, rgba, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    void* dOut = nullptr;
     if (bytes) {
-        if ((rc = display_scratch(ctx, bytes, &dOut))) return rc;
-        HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), rp_accum(ctx), dOut, bytes / 16));
+        if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
+        HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), accum_target(ctx), ctx->dDisplay, bytes / 16));
     }
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
@@ -2840,25 +2790,25 @@ int rt_resolve(RtContext* ctx, float* rgba, size_t bytes)
      * caller of this host read must not take its resolve for the reprojected image */
     if ((rc = aov_report(ctx, call))) return rc;
     if ((rc = check_watchdog(ctx, ctx, call))) return rc;
-    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, dOut, bytes, hipMemcpyDeviceToHost));
+    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
 int rt_resolve_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
 {
     static const char* call = "rt_resolve_to_device";
-    int rc = rp_check_resolve_call(ctx, call, d_rgba, bytes);
+    int rc = resolve_check_call(ctx, call, d_rgba, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (bytes) {
-        if ((rc = dn_check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
-        if (dn_overlap(d_rgba, bytes, rp_accum(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
+        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+        if (ranges_overlap(d_rgba, bytes, accum_target(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
     } else if ((uintptr_t)d_rgba & 15) {
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
     }
     RT_FLUSH(ctx);
     if (!bytes) return RT_OK;
-    HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), rp_accum(ctx), d_rgba, bytes / 16));
+    HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), accum_target(ctx), d_rgba, bytes / 16));
     return RT_OK;
 }
 
@@ -3043,7 +2993,7 @@ static int multi_gather(RtMulti* m, float* rgba, size_t bytes, bool accumulated)
     for (RtContext* c : m->ctx) {
         const size_t n = (size_t)c->localRows * rowBytes;
         if (n) {
-            const float* src = accumulated ? (c->boundAccum ? c->boundAccum : c->ownAccum) : (c->boundFrame ? c->boundFrame : c->ownFrame);
+            const float* src = image_target(c, accumulated);
             hipError_t e = hipSetDevice(c->device);
             if (e == hipSuccess) e = hipMemcpyAsync((char*)m->pinned + off, src, n, hipMemcpyDeviceToHost, joined(c));
             if (e != hipSuccess) { /* copies already enqueued still write into m->pinned: wait for them before handing the error back */
@@ -3099,7 +3049,7 @@ static int multi_gather_device(RtMulti* m, int root, void* d_rgba, size_t bytes,
     for (RtContext* c : m->ctx) {
         const int rows = c->localRows;
         if (!rows) continue;
-        const char* src = (const char*)(accumulated ? (c->boundAccum ? c->boundAccum : c->ownAccum) : (c->boundFrame ? c->boundFrame : c->ownFrame));
+        const char* src = (const char*)image_target(c, accumulated);
         hipError_t e = hipSetDevice(c->device);
         hipStream_t st = joined(c);
         for (int l = 0; l < rows && e == hipSuccess;) { /* a strip's rows are contiguous in the packed tile and in the image */
@@ -3188,7 +3138,7 @@ int rt_gather_rccl(RtContext* ctx, void* nccl_comm, int root, int use_accumulate
     const bool badDst = isRoot && (!d_rgba || bytes != (size_t)W * H * 16);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = joined(ctx);
-    const float* src = use_accumulated ? (ctx->boundAccum ? ctx->boundAccum : ctx->ownAccum) : (ctx->boundFrame ? ctx->boundFrame : ctx->ownFrame);
+    const float* src = image_target(ctx, use_accumulated);
     /* root: one staging area for every rank's packed tile (H rows in all), then one watchdog word per rank, in the display scratch */
     std::vector<size_t> rowOff(world + 1, 0);
     for (int r = 0; r < world; r++) rowOff[r + 1] = rowOff[r] + (size_t)local_rows_for(H, ctx->stripRows, r, world);
@@ -3196,10 +3146,9 @@ int rt_gather_rccl(RtContext* ctx, void* nccl_comm, int root, int use_accumulate
     char* staging = nullptr;
     unsigned long long* flags = nullptr;
     if (isRoot) {
-        void* p = nullptr;
-        const int rc = display_scratch(ctx, tileBytes + (size_t)world * sizeof(unsigned long long), &p);
+        const int rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, tileBytes + (size_t)world * sizeof(unsigned long long));
         if (rc) return rc;
-        staging = (char*)p;
+        staging = (char*)ctx->dDisplay;
         flags = (unsigned long long*)(staging + tileBytes);
     }
     auto check = [&](int e, const char* what) -> int {

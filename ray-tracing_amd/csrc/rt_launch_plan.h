@@ -117,6 +117,9 @@ inline GroupPlan plan_groups(int maxHeight, int nModels, int wantWaves, bool hot
 }
 
 /* ---- which kernel instantiation, workgroup shape and LDS a launch gets */
+/* the > 64-model (chunked) BVH instantiation: also of the passes that launch_shape does not size (rt_context.hip, the AOV pass) */
+inline bool many_models(int nChunks, bool flat) { return nChunks > 0 && !flat; }
+
 struct SceneShape {
     bool flat = false;            /* every model root is a leaf: the FLAT variant */
     bool stats = false;
@@ -154,7 +157,7 @@ inline LaunchShape launch_shape(const SceneShape& s, long long tiles, int nFrame
     l.ldsBytes = (size_t)l.hotUnits * 16 + (size_t)l.wavesPerGroup * waveBytes;
     l.poolCells = l.pooled ? s.poolCells : 0;
     l.waveLdsDwords = (int)(waveBytes / sizeof(uint32_t));
-    l.many = s.nChunks > 0 && !s.flat;
+    l.many = many_models(s.nChunks, s.flat);
     l.hot = l.hotUnits > 0;
     l.variant = (s.flat ? 2 : l.many ? 4 : 0) + (s.stats ? 1 : 0) + (l.hot ? 6 : 0);
     return l;

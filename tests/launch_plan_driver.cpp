@@ -5,6 +5,7 @@
 //   groups height= models= want= [hotkb=]                 -> wpg records
 //   shape flat= stats= stack= ext= chunks= hot= wpg= pool= poolwaves= minitems= cus= tiles= frames=
 //                                                         -> pooled many hot hotunits wpg threads poolcells wavedwords lds variant
+//   many chunks= flat=                                    -> many
 //   part tiles= frames= flat= spp= fg= grid= resident= wpg= part= parts= next=
 //                                                         -> every PartPlan field
 //   records resident= wpg= grid=                          -> waves
@@ -151,6 +152,8 @@ static std::string answer(const std::string& cmd, const Req& r)
         o << "pooled=" << l.pooled << " many=" << l.many << " hot=" << l.hot << " hotunits=" << l.hotUnits << " wpg=" << l.wavesPerGroup
           << " threads=" << l.blockThreads << " poolcells=" << l.poolCells << " wavedwords=" << l.waveLdsDwords << " lds=" << l.ldsBytes
           << " variant=" << l.variant;
+    } else if (cmd == "many") {
+        o << "many=" << many_models((int)r.i("chunks"), r.i("flat"));
     } else if (cmd == "part") {
         Work w;
         w.tiles = (int)r.i("tiles");

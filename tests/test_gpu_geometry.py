@@ -298,6 +298,44 @@ def test_a_part_with_no_rows_does_nothing_and_can_move_onto_rows(pkg, api, orc):
     tr.close()
 
 
+def test_a_part_with_no_rows_through_the_post_render_passes(pkg, api):
+    """The same zero-pixel context through the passes behind the render: the host variants return empty arrays, the device variants
+    take a null pointer with 0 bytes and still refuse a misaligned one, and the calls that need the whole image say so."""
+    abi = pkg.abi
+    w, h = 24, 20                  # 3 strips of 8: part 3 of 4 owns none
+    tr = api.create_tracer(0)
+    hip = C.CDLL("libamdhip64.so")
+    d = C.c_void_p()
+    assert hip.hipMalloc(C.byref(d), C.c_size_t(64)) == 0
+    try:
+        tr.set_partition(8, 3, 4)
+        mgr = pkg.scenes.get(*BVH[:1]).make_manager(tr, api, w, h)
+        mgr.OnEnable(renderSeed=SEED)
+        mgr.RenderFrames(2)
+        assert tr.local_rows() == 0
+        cost, aov, resolved = tr.render_cost(1), tr.render_aov(1), tr.resolve()
+        assert cost.shape == (0, w, 8) and cost.dtype == np.uint32
+        assert aov.shape == (0, w) and aov.dtype == abi.AOV_DTYPE
+        assert resolved.shape == (0, w, 4) and resolved.dtype == np.float32
+        assert api.render_aov_to_device(tr.h, 1, None, 0) == abi.RT_OK
+        assert api.resolve_to_device(tr.h, None, 0) == abi.RT_OK
+        assert api.render_aov_to_device(tr.h, 1, d.value + 4, 0) == abi.RT_ERR_INVALID_ARG
+        assert api.resolve_to_device(tr.h, d.value + 4, 0) == abi.RT_ERR_INVALID_ARG
+        # a part of an image cannot be filtered or reprojected
+        dp, rp = api.denoise_params(), api.reproject_params()
+        assert api.denoise(tr.h, C.byref(dp), 1, 1, None, 0) == abi.RT_ERR_STATE
+        assert "part 3 of 4" in api.last_error(tr.h).decode()
+        assert api.denoise_to_device(tr.h, C.byref(dp), 1, 1, None, 0) == abi.RT_ERR_STATE
+        assert api.reproject_accumulated(tr.h, C.byref(rp), d.value, 1, None) == abi.RT_ERR_STATE
+        assert "part 3 of 4" in api.last_error(tr.h).decode()
+        tr.synchronize()
+        c = tr.counters()
+        assert c["pixelFrames"] == 0 and c["segments"] == 0, c
+    finally:
+        tr.close()
+        assert hip.hipFree(d) == 0
+
+
 # ------------------------------------------------------------------------------------------------ D. more contexts than strips
 def test_multi_context_with_more_contexts_than_strips(pkg, api):
     """6 contexts on a 40 x 20 image (3 strips: 8 / 8 / 4 rows): contexts 3, 4 and 5 own no rows.  Host gathers, device gathers

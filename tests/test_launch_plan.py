@@ -132,6 +132,8 @@ def test_variant_slots_and_lds(plan):
         wave = ((0 if flat else 20) + 4 + (2 + 3 if many else 0)) * 256 + (2 * 64 * 16 if flat else 0)
         assert s["wavedwords"] * 4 == wave
         assert s["wpg"] == ((16 if flat else 12) if hot else 1)
+    # the rule for the > 64-model instantiation, as the passes outside launch_shape ask for it: chunks, and not FLAT
+    assert [m["many"] for m in plan(*[("many", dict(chunks=c, flat=f)) for c, f in ((0, False), (5, False), (5, True), (0, True))])] == [0, 1, 0, 0]
     # the BVH top-of-tree cache of config 3 (448 records) around 12 waves of 20-entry stacks
     assert shapes[keys.index((False, False, True, False))]["lds"] == 1792 * 16 + 12 * 24 * 256
 
