@@ -114,6 +114,17 @@ REPROJECT_PARAMS_DTYPE = np.dtype([
 REPROJECT_FLAG_GLASS = 1  # bit 0 of flags: carry history onto glass first hits too
 
 
+class RtObjectMotion(C.Structure):
+    """include/rt_motion.h: rows 0, 1, 2 of a 3 x 4 affine map, m[4r .. 4r+3] (48 bytes): a current world position on an object -> where
+    that point lay in the previous view's world."""
+    _fields_ = [("m", C.c_float * 12)]
+
+
+OBJECT_MOTION_DTYPE = np.dtype([("m", "<f4", (12,))])
+AOV_CENTRE = 0  # RT_AOV_CENTRE: aov_frame of rt_reproject_accumulated_moving that selects the pixel-centre records
+assert C.sizeof(RtObjectMotion) == 48 and OBJECT_MOTION_DTYPE.itemsize == 48
+
+
 class RtBvhStats(C.Structure):
     _fields_ = [
         ("triangleCount", C.c_int32), ("totalNodeCount", C.c_int32), ("leafNodeCount", C.c_int32),

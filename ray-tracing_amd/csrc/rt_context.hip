@@ -32,6 +32,7 @@
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
 #include "../../include/rt_reproject.h"
+#include "../../include/rt_motion.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
@@ -2402,15 +2403,20 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
  * stream that is not a render launch.  The pass is the context's in nothing but the scene, the parameters and the stream: KArgs as for
  * frame `frame`, a counter slot of its own (ctx->dAovWords; traverse() only ever writes its watchdog word), no render target, no tile
  * queue, no pixel records.  So RtCounters and the context's watchdog word stay as they are, and a watchdog that fires here fails this
- * pass only. */
+ * pass only.  frame == RT_AOV_CENTRE (0) selects the pixel-centre ray of include/rt_motion.h, which reads nothing of a frame: the KArgs
+ * are then those of frame 1. */
 static int aov_enqueue(RtContext* ctx, int frame, void* dOut)
 {
+    const bool centre = frame == RT_AOV_CENTRE;
+    if (centre) frame = 1;
     KArgs a;
     fill_args(ctx, frame, 1, a);
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
     const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
-    void (*kern)(const KArgs, float4*, const uint32_t*) = many ? rtk::rt_aov_kernel<false, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false> : rtk::rt_aov_kernel<false, false>;
+    void (*kern)(const KArgs, float4*, const uint32_t*) =
+        centre ? (many ? rtk::rt_aov_kernel<false, true, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false, true> : rtk::rt_aov_kernel<false, false, true>)
+               : (many ? rtk::rt_aov_kernel<false, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false> : rtk::rt_aov_kernel<false, false>);
     /* a wave region of the trace kernel, single waves, no cache, no pool */
     const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
     a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
@@ -2448,15 +2454,22 @@ static int aov_report(RtContext* ctx, const char* call)
     ctx->aovUnreported = false;
     unsigned long long fired = 0;
     if (int rc = aov_fired(ctx, &fired)) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call: "
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call (or its centre / moving form): "
                            "walks were cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
     return RT_OK;
 }
 
-static int aov_check_args(RtContext* ctx, const char* call, int frame, const void* out, size_t bytes)
+/* the frame number of the public frame calls (the centre calls pass RT_AOV_CENTRE to the shared bodies instead) */
+static int aov_check_frame(RtContext* ctx, const char* call, int frame)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     if (frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: frame %d < 1 (the first frame after a reset is 1)", call, frame);
+    return RT_OK;
+}
+
+static int aov_check_args(RtContext* ctx, const char* call, const void* out, size_t bytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     int rc = check_renderable(ctx);
     if (rc) return rc;
     return check_rows_buffer(ctx, call, sizeof(RtPixelAov), out, bytes);
@@ -2470,38 +2483,55 @@ static int aov_settle(RtContext* ctx, const char* call)
     return aov_report(ctx, call);
 }
 
-int rt_render_aov(RtContext* ctx, int frame, RtPixelAov* out, size_t bytes)
+/* the host and the device variant; `frame`: >= 1 (checked by the caller), or RT_AOV_CENTRE from the centre calls */
+static int aov_to_host(RtContext* ctx, const char* call, int frame, RtPixelAov* out, size_t bytes)
 {
-    int rc = aov_check_args(ctx, "rt_render_aov", frame, out, bytes);
+    int rc = aov_check_args(ctx, call, out, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, "rt_render_aov"))) return rc;
+    if ((rc = aov_settle(ctx, call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = grow_scratch(ctx, &ctx->dAovOut, &ctx->aovOutBytes, bytes))) return rc;
     if ((rc = aov_enqueue(ctx, frame, ctx->dAovOut))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     unsigned long long fired = 0;
     if ((rc = aov_fired(ctx, &fired))) return rc;
-    if (fired) return watchdog_failure(ctx, "rt_render_aov", fired);
+    if (fired) return watchdog_failure(ctx, call, fired);
     HIP_TRY(ctx, hipMemcpy(out, ctx->dAovOut, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
-int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes)
+static int aov_to_device(RtContext* ctx, const char* call, int frame, void* d_out, size_t bytes)
 {
-    int rc = aov_check_args(ctx, "rt_render_aov_to_device", frame, d_out, bytes);
+    int rc = aov_check_args(ctx, call, d_out, bytes);
     if (rc) return rc;
-    if ((uintptr_t)d_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "rt_render_aov_to_device: the records must be 16-byte aligned");
+    if ((uintptr_t)d_out & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: the records must be 16-byte aligned", call);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes && (rc = check_device_range(ctx, "rt_render_aov_to_device", "d_out", d_out, bytes))) return rc; /* the kernel writes through this pointer */
+    if (bytes && (rc = check_device_range(ctx, call, "d_out", d_out, bytes))) return rc; /* the kernel writes through this pointer */
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, "rt_render_aov_to_device"))) return rc;
+    if ((rc = aov_settle(ctx, call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = aov_enqueue(ctx, frame, d_out))) return rc;
     ctx->aovUnreported = true;
     return RT_OK;
 }
+
+int rt_render_aov(RtContext* ctx, int frame, RtPixelAov* out, size_t bytes)
+{
+    if (int rc = aov_check_frame(ctx, "rt_render_aov", frame)) return rc;
+    return aov_to_host(ctx, "rt_render_aov", frame, out, bytes);
+}
+
+int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes)
+{
+    if (int rc = aov_check_frame(ctx, "rt_render_aov_to_device", frame)) return rc;
+    return aov_to_device(ctx, "rt_render_aov_to_device", frame, d_out, bytes);
+}
+
+/* include/rt_motion.h, A */
+int rt_render_aov_centre(RtContext* ctx, RtPixelAov* out, size_t bytes) { return aov_to_host(ctx, "rt_render_aov_centre", RT_AOV_CENTRE, out, bytes); }
+int rt_render_aov_centre_to_device(RtContext* ctx, void* d_out, size_t bytes) { return aov_to_device(ctx, "rt_render_aov_centre_to_device", RT_AOV_CENTRE, d_out, bytes); }
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main
@@ -2638,7 +2668,7 @@ int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accum
     return RT_OK;
 }
 
-/* ---- rt_reproject_buffers / rt_reproject_accumulated / rt_resolve* (include/rt_reproject.h) -----------------------------------
+/* ---- rt_reproject_buffers / rt_reproject_accumulated / rt_resolve* (include/rt_reproject.h) and their *_moving forms (include/rt_motion.h)
  * The kernels are rt_reproject.hip's (rt_rp::enqueue*); here are the argument checks, the scratch and the order.  Everything runs on the
  * joined main stream (rt_launch_order.h, join): behind every frame either render stream holds, and — join() re-arms the fork — in front
  * of every frame requested later, which is how rt_reset_accumulation and rt_write_accumulated order their write of the accumulator.
@@ -2681,10 +2711,36 @@ int rt_reproject_default_params(RtReprojectParams* out)
     return RT_OK;
 }
 
-int rt_reproject_buffers(RtContext* ctx, const RtReprojectParams* p, int width, int height, const void* d_prev_rgba, const void* d_prev_aov, const void* d_cur_aov,
-                         void* d_out_rgba)
+/* The table of a *_moving call (nullptr: a static call, nothing to check): its size, its memory, and no overlap with what the call
+ * writes — `out` (outBytes) and, when given, `out2` (out2Bytes). */
+struct MotionArg {
+    bool moving;
+    const void* d;
+    int n;
+};
+
+static int check_motion_table(RtContext* ctx, const char* call, const MotionArg& mo, const void* out, size_t outBytes, const void* out2 = nullptr, size_t out2Bytes = 0)
 {
-    static const char* call = "rt_reproject_buffers";
+    if (!mo.moving) return RT_OK;
+    if (mo.n < 0 || mo.n > (1 << 24)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: n_objects %d outside 0..2^24", call, mo.n);
+    if (mo.n == 0) return RT_OK; /* d_motion is not looked at */
+    const size_t bytes = (size_t)mo.n * sizeof(RtObjectMotion);
+    if (int rc = check_device_range(ctx, call, "d_motion", mo.d, bytes)) return rc;
+    if (ranges_overlap(mo.d, bytes, out, outBytes) || (out2 && ranges_overlap(mo.d, bytes, out2, out2Bytes)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_motion overlaps an output", call);
+    return RT_OK;
+}
+
+/* the static kernel for the static calls (their bits and their time stay theirs), the table's kernel for the *_moving calls */
+static hipError_t reproject_enqueue(hipStream_t st, const rt_rp_job& job, const void* dPrevRgba, const void* dPrevAov, const void* dCurAov, const MotionArg& mo, void* dOut)
+{
+    if (!mo.moving) return rt_rp::enqueue(st, job, dPrevRgba, dPrevAov, dCurAov, dOut);
+    return rt_rp::enqueue_moving(st, job, dPrevRgba, dPrevAov, dCurAov, mo.n ? mo.d : nullptr, mo.n, dOut);
+}
+
+static int reproject_buffers_call(RtContext* ctx, const char* call, const RtReprojectParams* p, int width, int height, const void* d_prev_rgba, const void* d_prev_aov,
+                                  const void* d_cur_aov, const MotionArg& mo, void* d_out_rgba)
+{
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     rt_rp_job job;
     int rc = reproject_check_params(ctx, call, p, &job);
@@ -2700,21 +2756,37 @@ int rt_reproject_buffers(RtContext* ctx, const RtReprojectParams* p, int width, 
     if (ranges_overlap(d_out_rgba, n * 16, d_prev_rgba, n * 16) || ranges_overlap(d_out_rgba, n * 16, d_prev_aov, n * sizeof(RtPixelAov)) ||
         ranges_overlap(d_out_rgba, n * 16, d_cur_aov, n * sizeof(RtPixelAov)))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_out_rgba overlaps an input", call);
+    if ((rc = check_motion_table(ctx, call, mo, d_out_rgba, n * 16))) return rc;
     RT_FLUSH(ctx);
     job.W = width;
     job.H = height;
-    HIP_TRY(ctx, rt_rp::enqueue(joined(ctx), job, d_prev_rgba, d_prev_aov, d_cur_aov, d_out_rgba));
+    HIP_TRY(ctx, reproject_enqueue(joined(ctx), job, d_prev_rgba, d_prev_aov, d_cur_aov, mo, d_out_rgba));
     return RT_OK;
 }
 
-int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const void* d_prev_aov, int aov_frame, void* d_cur_aov_out)
+int rt_reproject_buffers(RtContext* ctx, const RtReprojectParams* p, int width, int height, const void* d_prev_rgba, const void* d_prev_aov, const void* d_cur_aov,
+                         void* d_out_rgba)
 {
-    static const char* call = "rt_reproject_accumulated";
+    return reproject_buffers_call(ctx, "rt_reproject_buffers", p, width, height, d_prev_rgba, d_prev_aov, d_cur_aov, MotionArg{false, nullptr, 0}, d_out_rgba);
+}
+
+int rt_reproject_buffers_moving(RtContext* ctx, const RtReprojectParams* p, int width, int height, const void* d_prev_rgba, const void* d_prev_aov, const void* d_cur_aov,
+                                const void* d_motion, int n_objects, void* d_out_rgba)
+{
+    return reproject_buffers_call(ctx, "rt_reproject_buffers_moving", p, width, height, d_prev_rgba, d_prev_aov, d_cur_aov, MotionArg{true, d_motion, n_objects}, d_out_rgba);
+}
+
+/* aov_frame: >= 1, or RT_AOV_CENTRE where the call admits it (centreAllowed) */
+static int reproject_accumulated_call(RtContext* ctx, const char* call, const RtReprojectParams* p, const void* d_prev_aov, int aov_frame, bool centreAllowed,
+                                      const MotionArg& mo, void* d_cur_aov_out)
+{
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     rt_rp_job job;
     int rc = reproject_check_params(ctx, call, p, &job);
     if (rc) return rc;
-    if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
+    if (centreAllowed ? aov_frame < 0 : aov_frame < 1)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < %d (the first frame after a reset is 1%s)", call, aov_frame, centreAllowed ? 0 : 1,
+                    centreAllowed ? "; RT_AOV_CENTRE, 0, is the pixel-centre pass" : "");
     if ((rc = check_renderable(ctx))) return rc;
     if ((rc = check_whole_image(ctx, call, "reprojection", "gather, then rt_reproject_buffers"))) return rc;
     job.W = ctx->W;
@@ -2734,6 +2806,7 @@ int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const v
                 return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_cur_aov_out overlaps d_prev_aov or AccumulatedRender", call);
         }
     }
+    if ((rc = check_motion_table(ctx, call, mo, accum, n * 16, d_cur_aov_out, recBytes))) return rc;
     RT_FLUSH(ctx);
     if ((rc = aov_settle(ctx, call))) return rc;
     if (!n) return RT_OK;
@@ -2743,9 +2816,34 @@ int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const v
     ctx->aovUnreported = true;
     hipStream_t st = joined(ctx);
     if (d_cur_aov_out) HIP_TRY(ctx, hipMemcpyAsync(d_cur_aov_out, ctx->dDnAov, recBytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, rt_rp::enqueue(st, job, accum, d_prev_aov, ctx->dDnAov, ctx->dDnScratch));
+    HIP_TRY(ctx, reproject_enqueue(st, job, accum, d_prev_aov, ctx->dDnAov, mo, ctx->dDnScratch));
     /* over the accumulator, unless the pass's watchdog fired: the device reads the pass's own word, the host reports it later */
     HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, accum, n, ctx->dAovWords + kWatchdogWord));
+    return RT_OK;
+}
+
+int rt_reproject_accumulated(RtContext* ctx, const RtReprojectParams* p, const void* d_prev_aov, int aov_frame, void* d_cur_aov_out)
+{
+    return reproject_accumulated_call(ctx, "rt_reproject_accumulated", p, d_prev_aov, aov_frame, false, MotionArg{false, nullptr, 0}, d_cur_aov_out);
+}
+
+int rt_reproject_accumulated_moving(RtContext* ctx, const RtReprojectParams* p, const void* d_prev_aov, int aov_frame, const void* d_motion, int n_objects,
+                                    void* d_cur_aov_out)
+{
+    return reproject_accumulated_call(ctx, "rt_reproject_accumulated_moving", p, d_prev_aov, aov_frame, true, MotionArg{true, d_motion, n_objects}, d_cur_aov_out);
+}
+
+/* Pure host code: no context, no device (include/rt_motion.h states the arithmetic; rt_motion_math.h is it) */
+int rt_motion_from_scene(const RtSphere* prev_spheres, const RtSphere* cur_spheres, int n_spheres, const RtModel* prev_models, const RtModel* cur_models, int n_models,
+                         RtObjectMotion* out)
+{
+    static const char* call = "rt_motion_from_scene";
+    if (n_spheres < 0 || n_models < 0) return fail(nullptr, RT_ERR_INVALID_ARG, "%s: a negative count", call);
+    if (n_spheres && (!prev_spheres || !cur_spheres)) return fail(nullptr, RT_ERR_INVALID_ARG, "%s: null spheres with n_spheres %d", call, n_spheres);
+    if (n_models && (!prev_models || !cur_models)) return fail(nullptr, RT_ERR_INVALID_ARG, "%s: null models with n_models %d", call, n_models);
+    if ((n_spheres || n_models) && !out) return fail(nullptr, RT_ERR_INVALID_ARG, "%s: out is null", call);
+    for (int i = 0; i < n_spheres; i++) rt_mo_sphere_entry(prev_spheres[i].centre, cur_spheres[i].centre, out[i].m);
+    for (int j = 0; j < n_models; j++) rt_mo_model_entry(prev_models[j].localToWorld, cur_models[j].worldToLocal, out[(size_t)n_spheres + j].m);
     return RT_OK;
 }
 

@@ -1353,8 +1353,10 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
  * kernel ([stackEntries][64] traversal stack, the pixel fields' rows unused, then the MANY variant's mask extension), so the host sizes it
  * with the same rule.  The traversal runs to completion (no suspension).  `unitTri`: uploaded triangle index by the 16-byte unit a
  * triangle record starts at (rt_layout.h moves the records), null = the dense layout (unit = 3 x index).  Only a.counters + 7 (the
- * watchdog word of traverse()) is ever written besides `out`: the host points it at a word of this pass's own. */
-template <bool FLAT, bool MANY>
+ * watchdog word of traverse()) is ever written besides `out`: the host points it at a word of this pass's own.
+ * CENTRE (include/rt_motion.h, rt_render_aov_centre): the ray through the unjittered pixel centre from the camera origin, no random draw;
+ * everything after the ray is the same code. */
+template <bool FLAT, bool MANY, bool CENTRE = false>
 __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_aov_kernel(const KArgs a, float4* __restrict__ out, const uint32_t* __restrict__ unitTri)
 {
     extern __shared__ uint32_t s_lds[];
@@ -1376,10 +1378,6 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             const float uvx = (float)(uint32_t)x * a.rcpWm1;
             const float uvy = (float)(uint32_t)y * a.rcpHm1;
             /* RC:550-556 */
-            const uint32_t pixelCoordX = (uint32_t)(uvx * (float)a.W);
-            const uint32_t pixelCoordY = (uint32_t)(uvy * (float)a.H);
-            const uint32_t pixelIndex = pixelCoordY * a.W + pixelCoordX;
-            uint32_t rng = pixelIndex + (uint32_t)a.frame0 * 719393u + (uint32_t)a.seed; /* RC:552 */
             const rt_f3 fpl = rt_v3(uvx - 0.5f, uvy - 0.5f, 1.0f) * rt_v3(a.viewParams[0], a.viewParams[1], a.viewParams[2]);
             float cam[16];
             for (int k = 0; k < 16; k++) cam[k] = a.cam[k];
@@ -1389,18 +1387,27 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             const rt_f3 camRight = rt_v3(cam[0], cam[1], cam[2]);
             const rt_f3 camUp = rt_v3(cam[4], cam[5], cam[6]);
             const float invNumPixelsX = a.rcpW; /* x / numPixels.x */
-            /* RC:565-576, rayIndex 0 */
-            rt_f3 rayOrigin;
-            if (a.raygenNoDefocus) { /* defocusStrength == 0: only the two draws of RandomPointInCircle remain (trace_body, PH_RAYGEN) */
-                rt_next_random(&rng);
-                rt_next_random(&rng);
+            rt_f3 rayOrigin, jfp;
+            if (CENTRE) { /* focusPoint seen from camOrigin: the record of the pixel, not of a frame */
                 rayOrigin = camOrigin;
+                jfp = focusPoint;
             } else {
-                rt_f2 dj = rand_circle(&rng);
-                rayOrigin = camOrigin + camRight * (dj.x * a.defocus * invNumPixelsX) + camUp * (dj.y * a.defocus * invNumPixelsX);
+                const uint32_t pixelCoordX = (uint32_t)(uvx * (float)a.W);
+                const uint32_t pixelCoordY = (uint32_t)(uvy * (float)a.H);
+                const uint32_t pixelIndex = pixelCoordY * a.W + pixelCoordX;
+                uint32_t rng = pixelIndex + (uint32_t)a.frame0 * 719393u + (uint32_t)a.seed; /* RC:552 */
+                /* RC:565-576, rayIndex 0 */
+                if (a.raygenNoDefocus) { /* defocusStrength == 0: only the two draws of RandomPointInCircle remain (trace_body, PH_RAYGEN) */
+                    rt_next_random(&rng);
+                    rt_next_random(&rng);
+                    rayOrigin = camOrigin;
+                } else {
+                    rt_f2 dj = rand_circle(&rng);
+                    rayOrigin = camOrigin + camRight * (dj.x * a.defocus * invNumPixelsX) + camUp * (dj.y * a.defocus * invNumPixelsX);
+                }
+                rt_f2 jj = rand_circle(&rng);
+                jfp = focusPoint + camRight * (jj.x * a.diverge * invNumPixelsX) + camUp * (jj.y * a.diverge * invNumPixelsX);
             }
-            rt_f2 jj = rand_circle(&rng);
-            const rt_f3 jfp = focusPoint + camRight * (jj.x * a.diverge * invNumPixelsX) + camUp * (jj.y * a.diverge * invNumPixelsX);
             const rt_f3 rpos = rayOrigin;
             const rt_f3 rdir = rt_normalize(jfp - rayOrigin);
 

@@ -7,13 +7,17 @@
  *                           touched.  One 16-byte store.  The taps of neighbouring lanes are neighbouring pixels under any camera move
  *                           that is not a large roll, so what a wave reads stays a few rows of the previous image and L2 serves the 4 x
  *                           reuse; there is nothing to stage in LDS, because where a group's taps lie is only known after the projection.
+ *   rt_mo_reproject_kernel  the same with the table of include/rt_motion.h: a lane whose object word indexes the table reads that entry (three
+ *                           16-byte loads; a wave's lanes see a handful of objects, so the entries come from cache) and carries on with the
+ *                           moved position and normal.  A kernel of its own: rt_rp_reproject_kernel stays the code it was.
  *   rt_rp_commit_kernel     copies the reprojected image over the accumulator unless the AOV pass's watchdog word is set.
  *   rt_rp_resolve_kernel    the per-pixel divide.
  *
- * All three move 16 bytes per lane and access and do a few dozen flops per pixel: they are bound by memory, 256-thread groups with no
+ * All four move 16 bytes per lane and access and do a few dozen flops per pixel: they are bound by memory, 256-thread groups with no
  * LDS and a register count far below the occupancy limit keep every CU's wave slots full, which is all a streaming kernel can use.
  *
- * The arithmetic is rt_reproject_math.h's, shared with the host driver of tests/test_reproject.py. */
+ * The arithmetic is rt_reproject_math.h's and rt_motion_math.h's, shared with the host drivers of tests/test_reproject.py and
+ * tests/test_motion.py. */
 #include <hip/hip_runtime.h>
 
 #include "rt_reproject_launch.h"
@@ -43,6 +47,30 @@ __global__ __launch_bounds__(256) void rt_rp_reproject_kernel(const rt_rp_job jo
     out[i] = make_float4(r.x, r.y, r.z, r.w);
 }
 
+/* the table as rt_mo_pixel reads it */
+struct MotionTable {
+    const float4* m;
+    __device__ __forceinline__ rt_mo_entry entry(int32_t k) const
+    {
+        const float4* e = m + 3 * (size_t)k;
+        const rt_mo_entry r = {ld4(e), ld4(e + 1), ld4(e + 2)};
+        return r;
+    }
+};
+
+__global__ __launch_bounds__(256) void rt_mo_reproject_kernel(const rt_rp_job job, const float4* __restrict__ prevRgba, const float4* __restrict__ prevAov,
+                                                              const float4* __restrict__ curAov, const float4* __restrict__ motion, int32_t nObjects,
+                                                              float4* __restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const PrevView prev = {prevRgba, prevAov};
+    const MotionTable table = {motion};
+    const int32_t object = reinterpret_cast<const int32_t*>(curAov + 4 * i + 2)[3];
+    const rt_rp4 r = rt_mo_pixel(job, ld4(curAov + 4 * i), ld4(curAov + 4 * i + 1), object, prev, table, nObjects); /* entry(k) only for 0 <= k < nObjects */
+    out[i] = make_float4(r.x, r.y, r.z, r.w);
+}
+
 __global__ __launch_bounds__(256) void rt_rp_commit_kernel(const float4* __restrict__ src, float4* __restrict__ dst, size_t n, const unsigned long long* __restrict__ skipIfSet)
 {
     if (*skipIfSet != 0ull) return; /* the same word for every lane of the grid */
@@ -66,6 +94,16 @@ hipError_t enqueue(hipStream_t st, const rt_rp_job& job, const void* dPrevRgba, 
     const size_t n = (size_t)job.W * job.H;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(rt_rp_reproject_kernel, grid_for(n), dim3(256), 0, st, job, (const float4*)dPrevRgba, (const float4*)dPrevAov, (const float4*)dCurAov, (float4*)dOut, n);
+    return hipGetLastError();
+}
+
+hipError_t enqueue_moving(hipStream_t st, const rt_rp_job& job, const void* dPrevRgba, const void* dPrevAov, const void* dCurAov, const void* dMotion, int nObjects,
+                          void* dOut)
+{
+    const size_t n = (size_t)job.W * job.H;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rt_mo_reproject_kernel, grid_for(n), dim3(256), 0, st, job, (const float4*)dPrevRgba, (const float4*)dPrevAov, (const float4*)dCurAov,
+                       (const float4*)dMotion, (int32_t)nObjects, (float4*)dOut, n);
     return hipGetLastError();
 }
 

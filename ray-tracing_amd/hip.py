@@ -38,6 +38,9 @@ DENOISE_SYMBOLS = ["rt_denoise_default_params", "rt_denoise_buffers", "rt_denois
 # every symbol include/rt_reproject.h declares
 REPROJECT_SYMBOLS = ["rt_reproject_default_params", "rt_reproject_buffers", "rt_reproject_accumulated", "rt_resolve_buffers", "rt_resolve",
                      "rt_resolve_to_device"]
+# every symbol include/rt_motion.h declares
+MOTION_SYMBOLS = ["rt_render_aov_centre", "rt_render_aov_centre_to_device", "rt_motion_from_scene", "rt_reproject_buffers_moving",
+                  "rt_reproject_accumulated_moving"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -104,6 +107,12 @@ class HipApi(abi.CApi):
         "resolve_buffers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
         "resolve": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "resolve_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "render_aov_centre": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "render_aov_centre_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "motion_from_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "reproject_buffers_moving": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_void_p]),
+        "reproject_accumulated_moving": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -244,6 +253,22 @@ class HipApi(abi.CApi):
                 setattr(p, k, v)
         return p
 
+    def motion_table(self, prev_spheres, cur_spheres, prev_models, cur_models):
+        """rt_motion_from_scene (include/rt_motion.h): the per-object table between two states of one scene, an array of
+        abi.OBJECT_MOTION_DTYPE with the object numbering of RtPixelAov.object (spheres first, then models).  Host code: no device."""
+        ps, n_ps = abi._ptr(prev_spheres, abi.sphere_dtype)
+        cs, n_cs = abi._ptr(cur_spheres, abi.sphere_dtype)
+        pm, n_pm = abi._ptr(prev_models, abi.model_dtype)
+        cm, n_cm = abi._ptr(cur_models, abi.model_dtype)
+        if n_ps != n_cs or n_pm != n_cm:
+            raise ValueError("the two states of the scene differ in their number of spheres or models")
+        out = np.zeros(n_ps + n_pm, dtype=abi.OBJECT_MOTION_DTYPE)
+        rc = self.motion_from_scene(ps.ctypes.data if n_ps else None, cs.ctypes.data if n_ps else None, n_ps, pm.ctypes.data if n_pm else None,
+                                    cm.ctypes.data if n_pm else None, n_pm, out.ctypes.data if out.size else None)
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, (self.last_error(None) or b"").decode(errors="replace"))
+        return out
+
     def create_tracer(self, device_id=0):
         h = C.c_void_p()
         rc = self.create(device_id, C.byref(h))
@@ -380,6 +405,18 @@ class MultiTracer:
     def reproject_accumulated(self, *args, **kwargs):
         self._needs_whole_image("reproject_accumulated")
 
+    def reproject_accumulated_moving(self, *args, **kwargs):
+        self._needs_whole_image("reproject_accumulated_moving")
+
+    def render_aov_centre(self):
+        """rt_render_aov_centre on every context, assembled into the whole image like render_aov."""
+        w, h = self.size
+        out = np.zeros((h, w), dtype=abi.AOV_DTYPE)
+        for i in range(self.api.multi_count(self.h)):
+            ctx = self.context(i)
+            out[ctx.local_to_global_rows()] = ctx.render_aov_centre()
+        return out
+
     def resolve(self, *args, **kwargs):
         self._needs_whole_image("resolve")
 
@@ -476,6 +513,17 @@ class HipTracer(abi.Tracer):
         enqueued on the stream the context renders on; complete after synchronize()."""
         self._check(self.api.render_aov_to_device(self.h, int(frame), ptr, int(nbytes)))
 
+    def render_aov_centre(self):
+        """rt_render_aov_centre (include/rt_motion.h): the records of the rays through the unjittered pixel centres, the same array as
+        render_aov's; they depend on no frame counter, seed, defocus or jitter.  Changes no state of the context."""
+        out = np.zeros((max(self.local_rows(), 0), self.width), dtype=abi.AOV_DTYPE)
+        self._check(self.api.render_aov_centre(self.h, out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def render_aov_centre_to_device(self, ptr, nbytes):
+        """rt_render_aov_centre_to_device: the same records into device memory, enqueued like render_aov_to_device."""
+        self._check(self.api.render_aov_centre_to_device(self.h, ptr, int(nbytes)))
+
     def denoise(self, params=None, use_accumulated=True, aov_frame=1):
         """rt_denoise (include/rt_denoise.h): the context's accumulated image (or its last frame) through the edge-avoiding a-trous
         filter, guided by the AOV pass of frame `aov_frame`: a (rows, W, 4) float32 array, rows bottom-up.  `params`: an
@@ -508,6 +556,19 @@ class HipTracer(abi.Tracer):
         current view.  prev_aov_ptr: the device records of the view that was left (render_aov_to_device before the move);
         cur_aov_out_ptr: optional device memory that receives the current view's records.  Only enqueues."""
         self._check(self.api.reproject_accumulated(self.h, C.byref(params), prev_aov_ptr, int(aov_frame), cur_aov_out_ptr))
+
+    def reproject_buffers_moving(self, width, height, prev_rgba_ptr, prev_aov_ptr, cur_aov_ptr, motion_ptr, n_objects, out_rgba_ptr, params):
+        """rt_reproject_buffers_moving (include/rt_motion.h): reproject_buffers with a device table of n_objects abi.RtObjectMotion entries
+        (api.motion_table, uploaded); motion_ptr may be None when n_objects == 0."""
+        self._check(self.api.reproject_buffers_moving(self.h, C.byref(params), int(width), int(height), prev_rgba_ptr, prev_aov_ptr, cur_aov_ptr, motion_ptr,
+                                                      int(n_objects), out_rgba_ptr))
+
+    def reproject_accumulated_moving(self, params, prev_aov_ptr, aov_frame, motion_ptr, n_objects, cur_aov_out_ptr=None):
+        """rt_reproject_accumulated_moving, in the C call's argument order: reproject_accumulated with the device table of the objects that
+        moved since the previous view (after update_models / update_spheres and set_params).  aov_frame = abi.AOV_CENTRE: pixel-centre
+        records, which prev_aov_ptr should then hold too (render_aov_centre_to_device, or the cur_aov_out_ptr of the last call).  Only
+        enqueues."""
+        self._check(self.api.reproject_accumulated_moving(self.h, C.byref(params), prev_aov_ptr, int(aov_frame), motion_ptr, int(n_objects), cur_aov_out_ptr))
 
     def resolve(self):
         """rt_resolve: the accumulated image divided per pixel by its own frame count (alpha): (rows, W, 4) float32, rows bottom-up; the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times the calls of include/rt_reproject.h on one GPU: config 3 at 1920 x 1080, a camera move of (0.05, 0.02, 0.03).
+"""Times the calls of include/rt_reproject.h and include/rt_motion.h on one GPU: config 3 at 1920 x 1080, a camera move of (0.05, 0.02, 0.03).
 
 HIP events on the stream the context renders on (a stream of this tool's, given to rt_set_stream) around back-to-back enqueued calls;
 after a warm-up, each figure is the median of --regions regions (default 9, at least 7) of at least --region-ms (default 60, at least 50)
@@ -9,6 +9,9 @@ each, with the regions' minimum and maximum next to it.  Rows:
   rt_resolve_buffers           the per-pixel divide
   rt_reproject_accumulated     AOV pass + copy of the records + reprojection + commit
   rt_render_aov_to_device      the AOV pass alone: the difference to the row above is the call without its AOV pass
+  rt_reproject_buffers_moving      the pass with an identity table of the scene's size (three more 16-byte loads per pixel, from cache)
+  rt_reproject_accumulated_moving  the context call with that table and the pixel-centre pass (RT_AOV_CENTRE)
+  rt_render_aov_centre_to_device   the pixel-centre pass alone
   device copy, reproject       hipMemcpyAsync device to device of the bytes rt_reproject_buffers must move, as the yardstick
   device copy, resolve         the same for rt_resolve_buffers (16 B in + 16 B out per pixel)
   host round trip              what a caller needed before this header: rt_read_accumulated, rt_render_aov, the NumPy restatement
@@ -68,6 +71,12 @@ def main():
         bufs[name] = C.c_void_p()
         ok(hip.hipMalloc(C.byref(bufs[name]), C.c_size_t(size)))
     tr.render_aov_to_device(1, bufs["prev"].value, n * 64)
+    models = mgr.meshInfo.copy()
+    table = api.motion_table(None, None, models, models)  # nothing moved: an identity table of the scene's size
+    n_objects = len(table)
+    bufs["motion"] = C.c_void_p()
+    ok(hip.hipMalloc(C.byref(bufs["motion"]), C.c_size_t(table.nbytes)))
+    ok(hip.hipMemcpy(bufs["motion"], C.c_void_p(table.ctypes.data), C.c_size_t(table.nbytes), C.c_int(1)))
     before = mgr.params()
     t = mgr.camera.transform
     mgr.camera.transform = pkg.Transform(tuple(np.array(t.position) + np.array([0.05, 0.02, 0.03])), t.euler, t.scale)
@@ -85,6 +94,10 @@ def main():
         "rt_resolve_buffers": lambda: tr.resolve_buffers(w, h, bufs["sum"].value, bufs["out"].value),
         "rt_reproject_accumulated": lambda: tr.reproject_accumulated(p, bufs["prev"].value, 1, bufs["cur"].value),
         "rt_render_aov_to_device": lambda: tr.render_aov_to_device(1, bufs["cur"].value, n * 64),
+        "rt_reproject_buffers_moving": lambda: tr.reproject_buffers_moving(w, h, bufs["sum"].value, bufs["prev"].value, bufs["cur"].value, bufs["motion"].value, n_objects,
+                                                                           bufs["out"].value, p),
+        "rt_reproject_accumulated_moving": lambda: tr.reproject_accumulated_moving(p, bufs["prev"].value, pkg.abi.AOV_CENTRE, bufs["motion"].value, n_objects, bufs["cur"].value),
+        "rt_render_aov_centre_to_device": lambda: tr.render_aov_centre_to_device(bufs["cur"].value, n * 64),
         "device copy, reproject": lambda: ok(hip.hipMemcpyAsync(bufs["copy_dst"], bufs["copy_src"], C.c_size_t(n * BYTES_REPROJECT // 2), C.c_int(3), stream)),
         "device copy, resolve": lambda: ok(hip.hipMemcpyAsync(bufs["out"], bufs["sum"], C.c_size_t(n * 16), C.c_int(3), stream)),
     }
@@ -104,7 +117,7 @@ def main():
         count = max(3, int(a.region_ms / one) + 1)
         region(fn, count)
         t_ms = sorted(region(fn, count) for _ in range(a.regions))
-        moved = {"rt_reproject_buffers": BYTES_REPROJECT, "device copy, reproject": BYTES_REPROJECT, "rt_resolve_buffers": BYTES_RESOLVE, "device copy, resolve": BYTES_RESOLVE}.get(name)
+        moved = {"rt_reproject_buffers": BYTES_REPROJECT, "rt_reproject_buffers_moving": BYTES_REPROJECT, "device copy, reproject": BYTES_REPROJECT, "rt_resolve_buffers": BYTES_RESOLVE, "device copy, resolve": BYTES_RESOLVE}.get(name)
         rows.append({"call": name, "median_ms": statistics.median(t_ms), "min_ms": t_ms[0], "max_ms": t_ms[-1], "calls_per_region": count,
                      "GB": None if moved is None else moved * n / 1e9, "GB_per_s": None if moved is None else moved * n / 1e6 / statistics.median(t_ms)})
     by = {r["call"]: r for r in rows}
@@ -133,11 +146,11 @@ def main():
               "reproject_accumulated_without_aov_pass_ms": without_aov, "host_round_trip": host, "commit": commit}
     if a.out:
         with open(a.out, "w") as f:
-            f.write(f"include/rt_reproject.h, {w} x {h}, config 3 ({a.frames} frames accumulated), camera moved by (0.05, 0.02, 0.03); commit {commit}\n")
+            f.write(f"include/rt_reproject.h and include/rt_motion.h, {w} x {h}, config 3 ({a.frames} frames accumulated), camera moved by (0.05, 0.02, 0.03); commit {commit}\n")
             f.write(f"median of {a.regions} regions of >= {a.region_ms:g} ms, [min, max] of the regions\n\n")
-            f.write(f"{'call':<28} {'ms per call':>11}   [min, max]            GB moved   GB/s\n")
+            f.write(f"{'call':<32} {'ms per call':>11}   [min, max]            GB moved   GB/s\n")
             for r in rows:
-                f.write(f"{r['call']:<28} {r['median_ms']:11.4f}   [{r['min_ms']:.4f}, {r['max_ms']:.4f}]")
+                f.write(f"{r['call']:<32} {r['median_ms']:11.4f}   [{r['min_ms']:.4f}, {r['max_ms']:.4f}]")
                 f.write("\n" if r["GB"] is None else f"   {r['GB']:8.3f}   {r['GB_per_s']:5.0f}\n")
             f.write(f"\nrt_reproject_accumulated without its AOV pass (difference of the medians): {without_aov:.4f} ms\n")
             if host:

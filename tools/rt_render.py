@@ -25,7 +25,8 @@ scale = 1 / frames accumulated, guided by the AOV pass of frame --aov-frame, as 
 --reproject-png PREFIX: after the --frames frames, moves the camera by --reproject-move DX,DY,DZ (world units), carries the accumulated
 image into the new view (rt_reproject_accumulated, include/rt_reproject.h), renders --reproject-frames more frames and writes
 PREFIX_resolved.png (rt_resolve: every pixel divided by its own frame count) and PREFIX_history.png (that count, white =
---frames + --reproject-frames, black = restarted).  It runs last: the other outputs show the view before the move.
+--frames + --reproject-frames, black = restarted); --reproject-centre steers it by the records of the unjittered pixel centres
+(rt_reproject_accumulated_moving with RT_AOV_CENTRE, include/rt_motion.h).  It runs last: the other outputs show the view before the move.
 
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
@@ -60,6 +61,7 @@ def main():
     ap.add_argument("--reproject-png", metavar="PREFIX", help="move the camera, reproject, render on; PREFIX_resolved.png and PREFIX_history.png")
     ap.add_argument("--reproject-move", metavar="DX,DY,DZ", default="0.05,0.02,0.03", help="camera offset in world units")
     ap.add_argument("--reproject-frames", type=int, default=4, help="frames rendered after the reprojection")
+    ap.add_argument("--reproject-centre", action="store_true", help="steer --reproject-png by pixel-centre records (include/rt_motion.h) instead of those of --aov-frame")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
@@ -143,13 +145,19 @@ def main():
         d_prev = C.c_void_p()
         if hip.hipMalloc(C.byref(d_prev), C.c_size_t(w * h * 64)) != 0:
             raise RuntimeError("hipMalloc failed")
-        tr.render_aov_to_device(a.aov_frame, d_prev.value, w * h * 64)
+        if a.reproject_centre:
+            tr.render_aov_centre_to_device(d_prev.value, w * h * 64)
+        else:
+            tr.render_aov_to_device(a.aov_frame, d_prev.value, w * h * 64)
         before = mgr.params()
         t = mgr.camera.transform
         offset = [float(x) for x in a.reproject_move.split(",")]
         mgr.camera.transform = pkg.Transform(tuple(np.array(t.position) + np.array(offset)), t.euler, t.scale)
         mgr.SetShaderParams()
-        tr.reproject_accumulated(api.reproject_params(before), d_prev.value, a.aov_frame)
+        if a.reproject_centre:
+            tr.reproject_accumulated_moving(api.reproject_params(before), d_prev.value, pkg.abi.AOV_CENTRE, None, 0)
+        else:
+            tr.reproject_accumulated(api.reproject_params(before), d_prev.value, a.aov_frame)
         mgr.RenderFrames(a.reproject_frames)
         img = tr.resolve()
         hip.hipFree(d_prev)
