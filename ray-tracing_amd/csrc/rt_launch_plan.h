@@ -3,7 +3,7 @@
  *
  * rt_context.hip gathers the inputs (scene, context, env switches, the occupancy the runtime reports, measured times), calls these pure
  * functions and copies the results into KArgs / LaunchPlan; tests/test_launch_plan.py checks them on the CPU.  The launch geometry the
- * kernels are compiled with is defined here too (rt_device.h includes this header), so that the host's rules and the kernels cannot
+ * kernels are compiled with is defined here too (rt_records.h includes this header, rt_device.h through it), so that the host's rules and the kernels cannot
  * disagree about a constant.
  *
  *   what                                  function        used by
@@ -48,7 +48,7 @@
 #ifndef RT_MIN_WAVES_PER_SIMD_FLAT
 #define RT_MIN_WAVES_PER_SIMD_FLAT 8
 #endif
-#define RT_PAIR_BYTES 64            /* sizeof(DPair): one record of the top-of-tree cache (asserted in rt_device.h) */
+#define RT_PAIR_BYTES 64            /* sizeof(DPair): one record of the top-of-tree cache (asserted in rt_records.h) */
 #define RT_STAGED_PIXEL_BYTES 16    /* a staged colour: one float4 per pixel and frame (KArgs::staging) */
 #define RT_LDS_BYTES_PER_CU (160 * 1024)
 #define RT_MAX_FILTER_EXT_WORDS 32  /* models beyond 63 are tracked in up to 32 extension words of the candidate mask */

@@ -2,9 +2,9 @@
  * rt_layout.h — WHERE the traversal's records lie in device memory (internal, host side; plain C++: rt_debug_layout hands the
  * result to tests/test_layout.py and to the line-touch model tools/layout_sim/ without a device).
  *
- * SceneBuilder::convert (rt_context.hip) validates the caller's BVHs and emits them in a CANONICAL form: node pairs in
+ * SceneBuilder::convert (rt_scene_prep.h) validates the caller's BVHs and emits them in a CANONICAL form: node pairs in
  * post-order with pair INDICES in the inner codes and triangle INDICES in the leaf codes.  LayoutEngine::run() turns that into
- * what the kernels address (rt_device.h): every record is named by the 16-byte UNIT it starts at —
+ * what the kernels address (rt_records.h): every record is named by the 16-byte UNIT it starts at —
  *     inner code = unit of the DPair in the pair space, leaf code = first unit of the leaf's run of DTri records relative
  *     to the model's triBase (three units per triangle), normals = 12 bytes per unit of the triangle space —
  * so the order and the spacing of the records are the host's to choose and no layout can change a bit of the result:
@@ -21,8 +21,8 @@
  *               down by the world-space surface area of the node they belong to, summed over the models that share the tree —
  *               lie at units [0, 4N) of the pair space, in front of every instance; the BVH kernels' workgroups copy exactly that
  *               prefix into LDS (rt_kernels.h, traverse phase B).  cache (no number) / default = as many as the LDS of a
- *               workgroup has room for (rt_context.hip, plan_groups); cache=0 = none; no word at all = the default rule: as many as fit
- *               when they cover at least 1/16 of the scene's node pairs, else none (prepare_scene: where the cache was measured to pay)
+ *               workgroup has room for (rt_launch_plan.h, plan_groups); cache=0 = none; no word at all = the default rule: as many as fit
+ *               when they cover at least 1/16 of the scene's node pairs, else none (rt_scene_prep.h, prepare_scene: where the cache was measured to pay)
  * Anything but `dense` needs a regular scene (no node pair shared between meshes, referenced triangles not much more
  * than the triangles there are); an irregular one silently gets `dense`.
  */
@@ -48,7 +48,7 @@
 
 #include "../../include/rt_abi.h"
 #include "../../include/rt_math.h"
-#include "rt_device.h"
+#include "rt_records.h"
 
 /* Uninitialised storage for plain records that are about to be written in full (std::vector::resize would first zero
  * ~150 MB for a million triangles, on one thread: page faults, a third of rt_upload_scene's host time). */
@@ -98,7 +98,7 @@ struct RtLayout {
     int triMode = 0; /* 0 dense, 1 align, 2 arena */
     bool pairAlign = false;
     int cacheRecords = -1; /* node pairs in the hot prefix of the pair space: -1 = default rule (what the workgroups' LDS holds IF that covers
-                            * enough of the scene's pairs to pay, rt_context.hip prepare_scene), -2 = what the LDS holds, 0 = none */
+                            * enough of the scene's pairs to pay, rt_scene_prep.h prepare_scene), -2 = what the LDS holds, 0 = none */
     bool dense() const { return hotLevels == 0 && !preorder && triMode == 0; }
     std::string name() const
     {

@@ -6,6 +6,8 @@ import re
 
 import pytest
 
+from scene_corruptions import corrupted_scenes, scene_arrays
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -90,11 +92,7 @@ def test_product_never_touches_the_oracle(pkg):
                 assert "liboracle" not in text and "oracle_lib" not in text and "oracle/" not in text.replace("oracle/rt_oracle.cpp", ""), f
 
 
-def _scene_arrays(pkg, api, cfg=4, **kw):
-    sc = pkg.scenes.get(cfg, **kw)
-    mgr = sc.make_manager(None, api)
-    mgr.renderSeed = 1
-    return mgr.CreateAllMeshData(mgr.models), mgr._pack_spheres()
+_scene_arrays = scene_arrays
 
 
 def test_validate_scene_is_the_host_half_of_upload_scene(pkg, api, monkeypatch):
@@ -186,7 +184,6 @@ def test_validate_scene_fuzz_parallel_and_sequential_agree(pkg, api, monkeypatch
     import numpy as np
     a = pkg.abi
     data, sph = _scene_arrays(pkg, api, 4)
-    rng = np.random.default_rng(1)
 
     def outcome(models, tris, nodes, seq):
         if seq:
@@ -200,26 +197,7 @@ def test_validate_scene_fuzz_parallel_and_sequential_agree(pkg, api, monkeypatch
             return ("err", e.status)
 
     seen = {"ok": 0, "err": 0}
-    for it in range(150):
-        nodes, models, tris = data["nodes"].copy(), data["meshInfo"].copy(), data["triangles"]
-        kind = it % 6
-        for _ in range(int(rng.integers(1, 6))):
-            i = int(rng.integers(0, len(nodes)))
-            if kind == 0:
-                nodes[i]["startIndex"] = int(rng.integers(-5, len(nodes) + 5))
-            elif kind == 1:
-                nodes[i]["triangleCount"] = int(rng.integers(-3, 200))
-            elif kind == 2:
-                raw = nodes.view(np.uint8)
-                raw[int(rng.integers(0, raw.size))] ^= np.uint8(1 << int(rng.integers(0, 8)))
-            elif kind == 3:
-                m = int(rng.integers(0, len(models)))
-                models[m]["nodeOffset"] = int(rng.integers(-2, len(nodes) + 2))
-                models[m]["triOffset"] = int(rng.integers(-2, len(tris) + 2))
-            elif kind == 4:
-                nodes[i]["startIndex"] = nodes[int(rng.integers(0, len(nodes)))]["startIndex"]
-            else:
-                nodes[i]["boundsMin"][int(rng.integers(0, 3))] = [np.nan, np.inf, -np.inf][int(rng.integers(0, 3))]
+    for it, kind, models, tris, nodes in corrupted_scenes(data, seed=1, iterations=150):
         o1, o2 = outcome(models, tris, nodes, False), outcome(models, tris, nodes, True)
         assert o1 == o2, (it, kind, o1, o2)
         seen[o1[0]] += 1
