@@ -114,6 +114,19 @@ REPROJECT_PARAMS_DTYPE = np.dtype([
 REPROJECT_FLAG_GLASS = 1  # bit 0 of flags: carry history onto glass first hits too
 
 
+class RtVarianceDenoiseParams(C.Structure):
+    """include/rt_variance.h: the parameters of the variance-guided a-trous filter (40 bytes; struct_size is the handshake)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("iterations", C.c_int32), ("sigmaLuminance", C.c_float), ("sigmaNormal", C.c_float),
+        ("sigmaPlane", C.c_float), ("demodulate", C.c_int32), ("scale", C.c_float), ("unknownVariance", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+# the same 40 bytes as a numpy record
+VARIANCE_DENOISE_PARAMS_DTYPE = np.dtype([
+    ("struct_size", "<u4"), ("iterations", "<i4"), ("sigmaLuminance", "<f4"), ("sigmaNormal", "<f4"),
+    ("sigmaPlane", "<f4"), ("demodulate", "<i4"), ("scale", "<f4"), ("unknownVariance", "<f4"), ("reserved", "<i4", (2,))])
+
+
 class RtObjectMotion(C.Structure):
     """include/rt_motion.h: rows 0, 1, 2 of a 3 x 4 affine map, m[4r .. 4r+3] (48 bytes): a current world position on an object -> where
     that point lay in the previous view's world."""

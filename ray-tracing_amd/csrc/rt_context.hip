@@ -29,11 +29,13 @@
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
 #include "../../include/rt_reproject.h"
+#include "../../include/rt_variance.h"
 #include "../../include/rt_motion.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
 #include "rt_reproject_launch.h"
+#include "rt_variance_launch.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -192,6 +194,11 @@ struct RtContext {
     size_t dnScratchBytes = 0;
     void* dDnAov = nullptr;
     size_t dnAovBytes = 0;
+    /* rt_variance (include/rt_variance.h): the moments image and the snapshot of the sum for this context's rows, momentsBytes each;
+     * made and zeroed on first use, dropped by rt_resize (so the next use finds them zeroed again) */
+    void* dMoments = nullptr;
+    void* dSnapshot = nullptr;
+    size_t momentsBytes = 0;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     double gpuMs = 0;
     int timerState = 0; /* 0 idle, 1 begun, 2 ended (elapsed not yet read) */
@@ -499,6 +506,8 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dAovWords);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
+    hipFree(ctx->dMoments);
+    hipFree(ctx->dSnapshot);
     hipFree(ctx->dStaging[0]);
     hipFree(ctx->dStaging[1]);
     hipFree(ctx->dPxCold);
@@ -570,6 +579,9 @@ int rt_resize(RtContext* ctx, int width, int height)
     }
     if (int rc = clear_watchdog(ctx)) return rc; /* new targets: nothing rendered into them yet */
     ctx->boundFrame = ctx->boundAccum = nullptr;
+    hipFree(ctx->dMoments); ctx->dMoments = nullptr; /* (the stream is idle: synchronised above) */
+    hipFree(ctx->dSnapshot); ctx->dSnapshot = nullptr;
+    ctx->momentsBytes = 0;
     ctx->orderTiles = 0; /* tile costs belong to the old geometry */
     for (int i = 0; i < 2; i++)
         if (ctx->dStaging[i]) {
@@ -2267,6 +2279,295 @@ int rt_resolve_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
     RT_FLUSH(ctx);
     if (!bytes) return RT_OK;
     HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), accum_target(ctx), d_rgba, bytes / 16));
+    return RT_OK;
+}
+
+/* ---- rt_moments_update_buffers / rt_denoise_variance* / rt_variance_* (include/rt_variance.h) ------------------------------------
+ * The kernels are rt_variance.hip's (rt_vr::enqueue*) and, for the carry, rt_reproject.hip's; here are the argument checks, the
+ * context's moments and the order on the joined main stream.  The filter's scratch is the plain filter's (same layout), with the
+ * resolved image of the two context calls behind it. */
+static int variance_check_params(RtContext* ctx, const char* call, const RtVarianceDenoiseParams* p, rt_vr::Job* job)
+{
+    if (!p) return fail(ctx, RT_ERR_INVALID_ARG, "%s: null parameters", call);
+    if (p->struct_size != sizeof(RtVarianceDenoiseParams))
+        return fail(ctx, RT_ERR_ABI_MISMATCH, "%s: RtVarianceDenoiseParams.struct_size is %u, this library's is %zu", call, p->struct_size, sizeof(RtVarianceDenoiseParams));
+    if (p->iterations < 0 || p->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: iterations %d outside 0..%d", call, p->iterations, RT_DENOISE_MAX_ITERATIONS);
+    const float sig[3] = {p->sigmaLuminance, p->sigmaNormal, p->sigmaPlane};
+    for (float s : sig)
+        if (!(s > 0.0f) || !rt_dn_finite(s)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: every sigma must be finite and > 0", call);
+    if (!rt_dn_finite(p->scale)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: scale is not finite", call);
+    if (!(p->unknownVariance >= 0.0f) || !rt_dn_finite(p->unknownVariance)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: unknownVariance must be finite and >= 0", call);
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(ctx, RT_ERR_INVALID_ARG, "%s: reserved must be 0", call);
+    job->iterations = p->iterations;
+    job->demodulate = p->demodulate != 0;
+    job->scale = p->scale;
+    job->unknownVariance = p->unknownVariance;
+    job->sigmaLuminance = p->sigmaLuminance;
+    job->aN = rt_dn_inv_sq(p->sigmaNormal);
+    job->aP = rt_dn_inv_sq(p->sigmaPlane);
+    if (!rt_dn_finite(job->aN) || !rt_dn_finite(job->aP)) /* the centre tap's e = 0 * inf would be NaN, as in denoise_check_params */
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: a sigma is too small: 1 / sigma^2 is not finite in fp32", call);
+    return RT_OK;
+}
+
+int rt_denoise_variance_default_params(RtVarianceDenoiseParams* out)
+{
+    if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_denoise_variance_default_params: out is null");
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(RtVarianceDenoiseParams);
+    out->iterations = 5;
+    out->sigmaLuminance = 4.0f;
+    out->sigmaNormal = 0.25f;
+    out->sigmaPlane = 0.1f;
+    out->demodulate = 1;
+    out->scale = 1.0f;
+    out->unknownVariance = 1.0f;
+    return RT_OK;
+}
+
+int rt_moments_update_buffers(RtContext* ctx, int width, int height, const void* d_sum, void* d_snapshot, void* d_moments, int rebase)
+{
+    static const char* call = "rt_moments_update_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    int rc = check_image_size(ctx, call, width, height, 1ll << 30);
+    if (rc) return rc;
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_range(ctx, call, "d_sum", d_sum, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_snapshot", d_snapshot, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_moments", d_moments, n * 16))) return rc;
+    if (ranges_overlap(d_sum, n * 16, d_snapshot, n * 16) || ranges_overlap(d_sum, n * 16, d_moments, n * 16) || ranges_overlap(d_snapshot, n * 16, d_moments, n * 16))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: two of the three images overlap", call);
+    RT_FLUSH(ctx);
+    HIP_TRY(ctx, rt_vr::enqueue_update(joined(ctx), d_sum, d_snapshot, d_moments, n, rebase));
+    return RT_OK;
+}
+
+int rt_denoise_variance_buffers(RtContext* ctx, const RtVarianceDenoiseParams* p, int width, int height, const void* d_rgba_in, const void* d_moments, const void* d_aov,
+                                void* d_rgba_out)
+{
+    static const char* call = "rt_denoise_variance_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    rt_vr::Job job;
+    int rc = variance_check_params(ctx, call, p, &job);
+    if (rc) return rc;
+    if ((rc = check_image_size(ctx, call, width, height, 1ll << 30))) return rc;
+    if ((rc = check_whole_image(ctx, call, "the filter", "gather, then rt_denoise_variance_buffers"))) return rc;
+    const size_t n = (size_t)width * height;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = check_device_range(ctx, call, "d_rgba_in", d_rgba_in, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_moments", d_moments, n * 16))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_aov", d_aov, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = check_device_range(ctx, call, "d_rgba_out", d_rgba_out, n * 16))) return rc;
+    if (ranges_overlap(d_rgba_out, n * 16, d_rgba_in, n * 16) || ranges_overlap(d_rgba_out, n * 16, d_moments, n * 16) ||
+        ranges_overlap(d_rgba_out, n * 16, d_aov, n * sizeof(RtPixelAov)))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba_out overlaps an input", call);
+    RT_FLUSH(ctx);
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_vr::scratch_bytes(n)))) return rc;
+    job.W = width;
+    job.H = height;
+    HIP_TRY(ctx, rt_vr::enqueue(joined(ctx), job, d_rgba_in, d_moments, d_aov, d_rgba_out, ctx->dDnScratch));
+    return RT_OK;
+}
+
+/* The context's moments and snapshot exist, for its rows as they are now; fresh ones are all zero (stream-ordered) */
+static int variance_images(RtContext* ctx)
+{
+    const size_t bytes = (size_t)ctx->localRows * ctx->W * 16;
+    if (ctx->dMoments || !bytes) return RT_OK;
+    void* m = nullptr;
+    void* s = nullptr;
+    HIP_TRY(ctx, hipMalloc(&m, bytes));
+    const hipError_t e = hipMalloc(&s, bytes);
+    if (e != hipSuccess) {
+        hipFree(m);
+        HIP_TRY(ctx, e);
+    }
+    ctx->dMoments = m;
+    ctx->dSnapshot = s;
+    ctx->momentsBytes = bytes;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(m, 0, bytes, st));
+    HIP_TRY(ctx, hipMemsetAsync(s, 0, bytes, st));
+    return RT_OK;
+}
+
+/* what every context call of this header starts with */
+static int variance_check_context(RtContext* ctx, const char* call)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "%s before rt_resize", call);
+    return RT_OK;
+}
+
+static int variance_update_call(RtContext* ctx, const char* call, bool reset)
+{
+    int rc = variance_check_context(ctx, call);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = variance_images(ctx))) return rc;
+    const size_t n = ctx->momentsBytes / 16;
+    if (!n) return RT_OK;
+    hipStream_t st = joined(ctx);
+    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->dMoments, 0, ctx->momentsBytes, st));
+    HIP_TRY(ctx, rt_vr::enqueue_update(st, accum_target(ctx), ctx->dSnapshot, ctx->dMoments, n, reset ? 1 : 0));
+    return RT_OK;
+}
+
+int rt_variance_update(RtContext* ctx) { return variance_update_call(ctx, "rt_variance_update", false); }
+int rt_variance_reset(RtContext* ctx) { return variance_update_call(ctx, "rt_variance_reset", true); }
+
+int rt_variance_carry(RtContext* ctx, const RtReprojectParams* p, const void* d_prev_aov, const void* d_cur_aov, const void* d_motion, int n_objects)
+{
+    static const char* call = "rt_variance_carry";
+    int rc = variance_check_context(ctx, call);
+    if (rc) return rc;
+    rt_rp_job job;
+    if ((rc = reproject_check_params(ctx, call, p, &job))) return rc;
+    if ((rc = check_whole_image(ctx, call, "reprojection", "gather, then rt_reproject_buffers on the moments"))) return rc;
+    job.W = ctx->W;
+    job.H = ctx->localRows;
+    const size_t n = (size_t)job.W * job.H, recBytes = n * sizeof(RtPixelAov);
+    const MotionArg mo = {d_motion != nullptr, d_motion, d_motion ? n_objects : 0};
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!d_prev_aov || !d_cur_aov) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s is null", call, d_prev_aov ? "d_cur_aov" : "d_prev_aov");
+    if (n) {
+        if ((rc = check_device_range(ctx, call, "d_prev_aov", d_prev_aov, recBytes))) return rc;
+        if ((rc = check_device_range(ctx, call, "d_cur_aov", d_cur_aov, recBytes))) return rc;
+    } else if (((uintptr_t)d_prev_aov | (uintptr_t)d_cur_aov) & 15) {
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: the records must be 16-byte aligned", call);
+    }
+    if ((rc = check_motion_table(ctx, call, mo, nullptr, 0))) return rc; /* (what this call writes is the library's own memory) */
+    RT_FLUSH(ctx);
+    if (!n) return RT_OK;
+    if ((rc = variance_images(ctx))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, n * 16))) return rc;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, reproject_enqueue(st, job, ctx->dMoments, d_prev_aov, d_cur_aov, mo, ctx->dDnScratch));
+    /* over the moments, unless the watchdog of the AOV pass that wrote d_cur_aov fired — rt_reproject_accumulated's commit read the same
+     * word and then left the sum alone.  Before any AOV pass of this context there is no such word and nothing to skip for. */
+    if (ctx->dAovWords)
+        HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, ctx->dMoments, n, ctx->dAovWords + kWatchdogWord));
+    else
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->dMoments, ctx->dDnScratch, n * 16, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(ctx, rt_vr::enqueue_update(st, accum_target(ctx), ctx->dSnapshot, ctx->dMoments, n, 1));
+    return RT_OK;
+}
+
+static int variance_check_moments_call(RtContext* ctx, const char* call, const void* out, size_t bytes)
+{
+    if (int rc = variance_check_context(ctx, call)) return rc;
+    return check_rows_buffer(ctx, call, 16, out, bytes);
+}
+
+int rt_variance_read_moments(RtContext* ctx, float* rgba, size_t bytes)
+{
+    static const char* call = "rt_variance_read_moments";
+    int rc = variance_check_moments_call(ctx, call, rgba, bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = variance_images(ctx))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    if ((rc = aov_report(ctx, call))) return rc; /* as rt_resolve: a carry behind a pass whose watchdog fired carried nothing */
+    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
+    if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, ctx->dMoments, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_variance_moments_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
+{
+    static const char* call = "rt_variance_moments_to_device";
+    int rc = variance_check_moments_call(ctx, call, d_rgba, bytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (!bytes) {
+        if ((uintptr_t)d_rgba & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
+        return RT_OK;
+    }
+    if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+    RT_FLUSH(ctx);
+    if ((rc = variance_images(ctx))) return rc;
+    if (ranges_overlap(d_rgba, bytes, ctx->dMoments, bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the moments", call);
+    HIP_TRY(ctx, hipMemcpyAsync(d_rgba, ctx->dMoments, bytes, hipMemcpyDeviceToDevice, joined(ctx)));
+    return RT_OK;
+}
+
+/* what rt_denoise_variance and rt_denoise_variance_to_device share, as denoise_check_context_call / denoise_enqueue_context_call */
+static int variance_check_filter_call(RtContext* ctx, const char* call, const RtVarianceDenoiseParams* p, int aov_frame, const void* out, size_t bytes, rt_vr::Job* job)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    int rc = variance_check_params(ctx, call, p, job);
+    if (rc) return rc;
+    if (aov_frame < 1) return fail(ctx, RT_ERR_INVALID_ARG, "%s: aov_frame %d < 1 (the first frame after a reset is 1)", call, aov_frame);
+    if ((rc = check_renderable(ctx))) return rc;
+    if ((rc = check_whole_image(ctx, call, "the filter", "gather, then rt_denoise_variance_buffers"))) return rc;
+    if ((rc = check_rows_buffer(ctx, call, 16, out, bytes))) return rc;
+    job->W = ctx->W;
+    job->H = ctx->localRows;
+    return RT_OK;
+}
+
+static int variance_enqueue_filter_call(RtContext* ctx, const rt_vr::Job& job, int aov_frame, void* dOut)
+{
+    const size_t n = (size_t)job.W * job.H;
+    int rc;
+    if ((rc = variance_images(ctx))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, rt_vr::scratch_bytes(n) + n * 16))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dDnAov, &ctx->dnAovBytes, n * sizeof(RtPixelAov)))) return rc;
+    if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov))) return rc;
+    void* resolved = (char*)ctx->dDnScratch + rt_vr::scratch_bytes(n);
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, rt_rp::enqueue_resolve(st, accum_target(ctx), resolved, n));
+    HIP_TRY(ctx, rt_vr::enqueue(st, job, resolved, ctx->dMoments, ctx->dDnAov, dOut, ctx->dDnScratch));
+    return RT_OK;
+}
+
+int rt_denoise_variance(RtContext* ctx, const RtVarianceDenoiseParams* p, int aov_frame, float* rgba, size_t bytes)
+{
+    static const char* call = "rt_denoise_variance";
+    rt_vr::Job job;
+    int rc = variance_check_filter_call(ctx, call, p, aov_frame, rgba, bytes, &job);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, call))) return rc;
+    if (!bytes) return RT_OK;
+    if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
+    if ((rc = variance_enqueue_filter_call(ctx, job, aov_frame, ctx->dDisplay))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    unsigned long long fired = 0;
+    if ((rc = aov_fired(ctx, &fired))) return rc;
+    if (fired) return watchdog_failure(ctx, call, fired);
+    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_denoise_variance_to_device(RtContext* ctx, const RtVarianceDenoiseParams* p, int aov_frame, void* d_rgba, size_t bytes)
+{
+    static const char* call = "rt_denoise_variance_to_device";
+    rt_vr::Job job;
+    int rc = variance_check_filter_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (bytes) {
+        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+        if (ranges_overlap(d_rgba, bytes, accum_target(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
+    } else if ((uintptr_t)d_rgba & 15) {
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
+    }
+    RT_FLUSH(ctx);
+    if ((rc = aov_settle(ctx, call))) return rc;
+    if (!bytes) return RT_OK;
+    if ((rc = variance_images(ctx))) return rc;
+    if (ranges_overlap(d_rgba, bytes, ctx->dMoments, bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the moments", call);
+    if ((rc = variance_enqueue_filter_call(ctx, job, aov_frame, d_rgba))) return rc;
+    ctx->aovUnreported = true;
     return RT_OK;
 }
 

@@ -41,6 +41,10 @@ REPROJECT_SYMBOLS = ["rt_reproject_default_params", "rt_reproject_buffers", "rt_
 # every symbol include/rt_motion.h declares
 MOTION_SYMBOLS = ["rt_render_aov_centre", "rt_render_aov_centre_to_device", "rt_motion_from_scene", "rt_reproject_buffers_moving",
                   "rt_reproject_accumulated_moving"]
+# every symbol include/rt_variance.h declares
+VARIANCE_SYMBOLS = ["rt_denoise_variance_default_params", "rt_moments_update_buffers", "rt_denoise_variance_buffers", "rt_variance_update",
+                    "rt_variance_reset", "rt_variance_carry", "rt_variance_read_moments", "rt_variance_moments_to_device", "rt_denoise_variance",
+                    "rt_denoise_variance_to_device"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -113,6 +117,16 @@ class HipApi(abi.CApi):
         "reproject_buffers_moving": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                C.c_void_p]),
         "reproject_accumulated_moving": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+        "denoise_variance_default_params": (C.c_int, [C.POINTER(abi.RtVarianceDenoiseParams)]),
+        "moments_update_buffers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+        "denoise_variance_buffers": (C.c_int, [C.c_void_p, C.POINTER(abi.RtVarianceDenoiseParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "variance_update": (C.c_int, [C.c_void_p]),
+        "variance_reset": (C.c_int, [C.c_void_p]),
+        "variance_carry": (C.c_int, [C.c_void_p, C.POINTER(abi.RtReprojectParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+        "variance_read_moments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "variance_moments_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(abi.RtVarianceDenoiseParams), C.c_int, C.c_void_p, C.c_size_t]),
+        "denoise_variance_to_device": (C.c_int, [C.c_void_p, C.POINTER(abi.RtVarianceDenoiseParams), C.c_int, C.c_void_p, C.c_size_t]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -232,6 +246,22 @@ class HipApi(abi.CApi):
             if k not in dict(abi.RtDenoiseParams._fields_):
                 raise TypeError(f"RtDenoiseParams has no field {k!r}")
             setattr(p, k, v)
+        return p
+
+    def variance_denoise_params(self, **fields):
+        """rt_denoise_variance_default_params, with `fields` (iterations, sigmaLuminance, sigmaNormal, sigmaPlane, demodulate, scale,
+        unknownVariance) set on top."""
+        p = abi.RtVarianceDenoiseParams()
+        rc = self.denoise_variance_default_params(C.byref(p))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, "rt_denoise_variance_default_params failed")
+        for k, v in fields.items():
+            if k not in dict(abi.RtVarianceDenoiseParams._fields_):
+                raise TypeError(f"RtVarianceDenoiseParams has no field {k!r}")
+            if k == "reserved":
+                p.reserved[:] = [int(x) for x in v]
+            else:
+                setattr(p, k, v)
         return p
 
     def reproject_params(self, prev_params=None, **fields):
@@ -584,6 +614,56 @@ class HipTracer(abi.Tracer):
     def resolve_buffers(self, width, height, rgba_sum_ptr, rgba_out_ptr):
         """rt_resolve_buffers: the per-pixel divide on caller-owned device memory (in place when both pointers are equal)."""
         self._check(self.api.resolve_buffers(self.h, int(width), int(height), rgba_sum_ptr, rgba_out_ptr))
+
+    def variance_denoise_params(self, **fields):
+        """api.variance_denoise_params: the defaults of rt_denoise_variance_default_params with `fields` set on top."""
+        return self.api.variance_denoise_params(**fields)
+
+    def moments_update_buffers(self, width, height, sum_ptr, snapshot_ptr, moments_ptr, rebase=False):
+        """rt_moments_update_buffers (include/rt_variance.h): one batch — the sum's growth since the snapshot — into a moments image
+        (sum of L, sum of L^2, 0, batches), all caller-owned device memory; rebase=True only copies the sum into the snapshot."""
+        self._check(self.api.moments_update_buffers(self.h, int(width), int(height), sum_ptr, snapshot_ptr, moments_ptr, 1 if rebase else 0))
+
+    def denoise_variance_buffers(self, width, height, rgba_in_ptr, moments_ptr, aov_ptr, rgba_out_ptr, params=None):
+        """rt_denoise_variance_buffers: the variance-guided filter alone on caller-owned device memory.  Needs no scene and no resize."""
+        p = params if params is not None else self.api.variance_denoise_params()
+        self._check(self.api.denoise_variance_buffers(self.h, C.byref(p), int(width), int(height), rgba_in_ptr, moments_ptr, aov_ptr, rgba_out_ptr))
+
+    def variance_update(self):
+        """rt_variance_update: the frames rendered since the last update become one batch of the context's moments."""
+        self._check(self.api.variance_update(self.h))
+
+    def variance_reset(self):
+        """rt_variance_reset: no batches; the snapshot is the accumulated image as it stands (after reset_accumulation / write_accumulated)."""
+        self._check(self.api.variance_reset(self.h))
+
+    def variance_carry(self, params, prev_aov_ptr, cur_aov_ptr, motion_ptr=None, n_objects=0):
+        """rt_variance_carry: right after reproject_accumulated[_moving], with its parameters, its prev_aov_ptr and the records it wrote
+        (cur_aov_out_ptr): the context's moments follow the accumulated image into the new view."""
+        self._check(self.api.variance_carry(self.h, C.byref(params), prev_aov_ptr, cur_aov_ptr, motion_ptr, int(n_objects)))
+
+    def read_moments(self):
+        """rt_variance_read_moments: the context's moments, (rows, W, 4) float32, rows bottom-up: sum of L, sum of L^2, 0, batches."""
+        out = np.zeros((max(self.local_rows(), 0), self.width, 4), dtype=np.float32)
+        self._check(self.api.variance_read_moments(self.h, out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def moments_to_device(self, ptr, nbytes):
+        """rt_variance_moments_to_device: the same image into device memory (rows * W * 16 bytes), enqueued."""
+        self._check(self.api.variance_moments_to_device(self.h, ptr, int(nbytes)))
+
+    def denoise_variance(self, params=None, aov_frame=1):
+        """rt_denoise_variance: the accumulated image, resolved per pixel, through the variance-guided a-trous filter, steered by the
+        context's moments and the AOV pass of frame `aov_frame`: (rows, W, 4) float32, rows bottom-up.  Changes no state."""
+        p = params if params is not None else self.api.variance_denoise_params()
+        out = np.zeros((max(self.local_rows(), 0), self.width, 4), dtype=np.float32)
+        self._check(self.api.denoise_variance(self.h, C.byref(p), int(aov_frame), out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def denoise_variance_to_device(self, ptr, nbytes, params=None, aov_frame=1):
+        """rt_denoise_variance_to_device: the same image into device memory (rows * W * 16 bytes), enqueued; complete after synchronize()."""
+        p = params if params is not None else self.api.variance_denoise_params()
+        self._check(self.api.denoise_variance_to_device(self.h, C.byref(p), int(aov_frame), ptr, int(nbytes)))
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

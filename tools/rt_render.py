@@ -28,6 +28,14 @@ PREFIX_resolved.png (rt_resolve: every pixel divided by its own frame count) and
 --frames + --reproject-frames, black = restarted); --reproject-centre steers it by the records of the unjittered pixel centres
 (rt_reproject_accumulated_moving with RT_AOV_CENTRE, include/rt_motion.h).  It runs last: the other outputs show the view before the move.
 
+    python tools/rt_render.py 3 --frames 8 --png noisy.png --vdenoise-png filtered.png --variance-png sd.png
+
+--vdenoise-png FILE renders the --frames frames in --variance-batches equal batches (default 8), takes a batch of luminance moments after
+each (rt_variance_update, include/rt_variance.h) and writes the accumulated image through the variance-guided a-trous filter
+(rt_denoise_variance; --denoise-iterations applies to it too).  --variance-png FILE writes the standard deviation of the mean those
+moments give, as a heatmap: grey = sd / --variance-scale (default 0.25), pure red above the scale, blue where fewer than two batches
+are known.
+
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
 icosphere:SUBDIV[:DISPLACEMENT_SEED[:RADIUS]] | a JSON mesh spec); a stand-in has to have the
@@ -58,6 +66,10 @@ def main():
     ap.add_argument("--denoise-png", metavar="FILE", help="the accumulated image through rt_denoise, as an sRGB picture")
     ap.add_argument("--denoise-iterations", type=int, help="passes of the filter, 0..8 (default: the library's)")
     ap.add_argument("--denoise-sigma", metavar="C,N,P", help="sigmaColour,sigmaNormal,sigmaPlane (default: the library's)")
+    ap.add_argument("--vdenoise-png", metavar="FILE", help="the accumulated image through rt_denoise_variance, as an sRGB picture")
+    ap.add_argument("--variance-png", metavar="FILE", help="heatmap of the standard deviation of the mean (from the luminance moments)")
+    ap.add_argument("--variance-batches", type=int, default=8, help="equal batches the frames are rendered in for the moments (default 8)")
+    ap.add_argument("--variance-scale", type=float, default=0.25, help="standard deviation drawn white; above it a pixel is red")
     ap.add_argument("--reproject-png", metavar="PREFIX", help="move the camera, reproject, render on; PREFIX_resolved.png and PREFIX_history.png")
     ap.add_argument("--reproject-move", metavar="DX,DY,DZ", default="0.05,0.02,0.03", help="camera offset in world units")
     ap.add_argument("--reproject-frames", type=int, default=4, help="frames rendered after the reprojection")
@@ -99,8 +111,17 @@ def main():
     else:
         mgr.OnEnable(renderSeed=a.seed)
     frames = a.frames if a.frames is not None else scene.frames
+    variance = bool(a.vdenoise_png or a.variance_png)
+    if variance and (a.variance_batches < 2 or frames % a.variance_batches):
+        ap.error(f"--variance-batches must be at least 2 and divide --frames ({frames})")
     tr.reset_counters(); tr.timer_begin()
-    mgr.RenderFrames(frames)
+    if variance:
+        tr.variance_reset()  # (a resumed sum is where the batches start from)
+        for _ in range(a.variance_batches):
+            mgr.RenderFrames(frames // a.variance_batches)
+            tr.variance_update()
+    else:
+        mgr.RenderFrames(frames)
     tr.timer_end(); c = tr.counters()
     print(json.dumps({"scene": scene.name, "size": [w, h], "frames": frames, "spp_total": (mgr.numAccumulatedFrames - 1) * mgr.numRaysPerPixel,
                       "gpu_ms": c["gpuMs"], "Mrays_per_s": c["segments"] / max(c["gpuMs"], 1e-9) / 1e3}))
@@ -138,6 +159,26 @@ def main():
         pkg.display.write_png(a.denoise_png, pkg.display.linear_srgb8(img))
         print(json.dumps({"denoise_png": a.denoise_png, "iterations": p.iterations, "sigma": [p.sigmaColour, p.sigmaNormal, p.sigmaPlane],
                           "demodulate": p.demodulate, "scale": p.scale, "aov_frame": a.aov_frame}))
+    if a.vdenoise_png:
+        p = api.variance_denoise_params(**({"iterations": a.denoise_iterations} if a.denoise_iterations is not None else {}))
+        img = tr.denoise_variance(p, aov_frame=a.aov_frame)
+        pkg.display.write_png(a.vdenoise_png, pkg.display.linear_srgb8(img))
+        print(json.dumps({"vdenoise_png": a.vdenoise_png, "iterations": p.iterations, "sigma": [p.sigmaLuminance, p.sigmaNormal, p.sigmaPlane],
+                          "demodulate": p.demodulate, "unknownVariance": p.unknownVariance, "batches": a.variance_batches, "aov_frame": a.aov_frame}))
+    if a.variance_png:
+        import numpy as np
+        m = tr.read_moments().astype(np.float64)
+        nb = m[..., 3]
+        known = nb >= 2
+        safe = np.where(known, nb, 2.0)
+        sd = np.sqrt(np.maximum(m[..., 1] - m[..., 0] * m[..., 0] / safe, 0.0) / (safe * (safe - 1.0)))
+        grey = np.clip(sd / a.variance_scale, 0.0, 1.0)
+        heat = np.stack([grey, grey, grey], axis=-1)
+        heat[sd > a.variance_scale] = (1.0, 0.0, 0.0)
+        heat[~known] = (0.0, 0.0, 1.0)
+        pkg.display.write_png(a.variance_png, pkg.display.linear_srgb8(heat.astype(np.float32)))
+        print(json.dumps({"variance_png": a.variance_png, "batches": a.variance_batches, "scale": a.variance_scale, "median_sd": float(np.median(sd[known])) if known.any() else None,
+                          "pixels_over_scale": int((sd > a.variance_scale).sum()), "pixels_unknown": int((~known).sum())}))
     if a.reproject_png:
         import ctypes as C
         import numpy as np
