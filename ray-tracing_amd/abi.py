@@ -127,6 +127,28 @@ VARIANCE_DENOISE_PARAMS_DTYPE = np.dtype([
     ("sigmaPlane", "<f4"), ("demodulate", "<i4"), ("scale", "<f4"), ("unknownVariance", "<f4"), ("reserved", "<i4", (2,))])
 
 
+class RtAdaptiveParams(C.Structure):
+    """include/rt_adaptive.h: which tiles count as not yet converged (32 bytes; struct_size is the handshake)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("threshold", C.c_float), ("darkFloor", C.c_float), ("minFrames", C.c_int32), ("maxFrames", C.c_int32),
+        ("reserved", C.c_int32 * 3)]
+
+
+class RtAdaptiveResult(C.Structure):
+    """include/rt_adaptive.h: what rt_adaptive_select hands back (16 bytes)."""
+    _fields_ = [("tiles_total", C.c_uint32), ("tiles_active", C.c_uint32), ("pixels_active", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"tiles_total": int(self.tiles_total), "tiles_active": int(self.tiles_active), "pixels_active": int(self.pixels_active)}
+
+
+# the same 32 and 16 bytes as numpy records
+ADAPTIVE_PARAMS_DTYPE = np.dtype([
+    ("struct_size", "<u4"), ("threshold", "<f4"), ("darkFloor", "<f4"), ("minFrames", "<i4"), ("maxFrames", "<i4"), ("reserved", "<i4", (3,))])
+ADAPTIVE_RESULT_DTYPE = np.dtype([("tiles_total", "<u4"), ("tiles_active", "<u4"), ("pixels_active", "<u4"), ("reserved", "<u4")])
+ADAPTIVE_TILE = 8  # the tracer's tile edge: tile t = ty * ceil(W / 8) + tx
+
+
 class RtObjectMotion(C.Structure):
     """include/rt_motion.h: rows 0, 1, 2 of a 3 x 4 affine map, m[4r .. 4r+3] (48 bytes): a current world position on an object -> where
     that point lay in the previous view's world."""

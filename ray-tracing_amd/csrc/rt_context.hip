@@ -30,12 +30,14 @@
 #include "../../include/rt_denoise.h"
 #include "../../include/rt_reproject.h"
 #include "../../include/rt_variance.h"
+#include "../../include/rt_adaptive.h"
 #include "../../include/rt_motion.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
 #include "rt_reproject_launch.h"
 #include "rt_variance_launch.h"
+#include "rt_adaptive_launch.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -199,6 +201,18 @@ struct RtContext {
     void* dMoments = nullptr;
     void* dSnapshot = nullptr;
     size_t momentsBytes = 0;
+    /* rt_adaptive (include/rt_adaptive.h): the tile errors of the last selection and the current tile list, adTilesTotal entries each,
+     * for this context's rows; made on first use, dropped by rt_resize.  The host knows the list's length and pixel count (a selection
+     * reads them back, a caller's list is counted here).  The launches over a list draw their queue positions from a counter of their
+     * own, which counts on across launches like the render streams' (adQueueNext: its value when the next launch starts). */
+    float* dAdTileError = nullptr;
+    uint32_t* dAdTiles = nullptr;
+    uint32_t* dAdCounts = nullptr;
+    long long adTilesTotal = -1; /* what the two arrays are sized for; -1 = none */
+    bool adHaveList = false, adHaveErrors = false;
+    uint32_t adTilesActive = 0, adPixelsActive = 0;
+    unsigned long long* dAdQueue = nullptr;
+    unsigned long long adQueueNext = 0;
     hipEvent_t evStart = nullptr, evStop = nullptr;
     double gpuMs = 0;
     int timerState = 0; /* 0 idle, 1 begun, 2 ended (elapsed not yet read) */
@@ -508,6 +522,10 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
     hipFree(ctx->dSnapshot);
+    hipFree(ctx->dAdTileError);
+    hipFree(ctx->dAdTiles);
+    hipFree(ctx->dAdCounts);
+    hipFree(ctx->dAdQueue);
     hipFree(ctx->dStaging[0]);
     hipFree(ctx->dStaging[1]);
     hipFree(ctx->dPxCold);
@@ -582,6 +600,11 @@ int rt_resize(RtContext* ctx, int width, int height)
     hipFree(ctx->dMoments); ctx->dMoments = nullptr; /* (the stream is idle: synchronised above) */
     hipFree(ctx->dSnapshot); ctx->dSnapshot = nullptr;
     ctx->momentsBytes = 0;
+    hipFree(ctx->dAdTileError); ctx->dAdTileError = nullptr; /* the tile list and the tile errors belong to the old geometry */
+    hipFree(ctx->dAdTiles); ctx->dAdTiles = nullptr;
+    ctx->adTilesTotal = -1;
+    ctx->adHaveList = ctx->adHaveErrors = false;
+    ctx->adTilesActive = ctx->adPixelsActive = 0;
     ctx->orderTiles = 0; /* tile costs belong to the old geometry */
     for (int i = 0; i < 2; i++)
         if (ctx->dStaging[i]) {
@@ -1767,6 +1790,262 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     HIP_TRY(ctx, hipMemcpy(&fired, words + kWatchdogWord, sizeof(fired), hipMemcpyDeviceToHost));
     if (fired) return watchdog_failure(ctx, "rt_render_cost", fired);
     HIP_TRY(ctx, hipMemcpy(out, dOut.p, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* ---- rt_adaptive_* (include/rt_adaptive.h): tile selection and the frames of a tile list ---------------------------------------
+ * The kernels of the selection and of the list's accumulate step are rt_adaptive.hip's (rt_ad::enqueue_*); the frames themselves are the
+ * production trace kernel choose_variant picks, launched over the list: ONE kernel on the joined main stream, whose queue position q is
+ * entry q of the list (tileOrder = the list, orderOffset / orderStride = 0 / 1), launchItems from rt_plan::plan_part with tiles = the
+ * list's length, tileCost = null (the cost records that order the normal launches are not skewed by partial frames), the main stream's
+ * pixel-record slot and staging slab (stream order), and a tile counter of its own.  ctx->order sees a join and nothing else; the
+ * tuner and the fuse probes are not touched. */
+static int variance_images(RtContext* ctx);
+
+static int adaptive_check_params(RtContext* ctx, const char* call, const RtAdaptiveParams* p, rt_ad_job* job)
+{
+    const char* why = "";
+    const int rc = rt_ad::check_params(p, job, &why);
+    return rc ? fail(ctx, rc, "%s: %s", call, why) : RT_OK;
+}
+
+int rt_adaptive_default_params(RtAdaptiveParams* out)
+{
+    if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_adaptive_default_params: out is null");
+    memset(out, 0, sizeof(*out));
+    out->struct_size = (uint32_t)sizeof(RtAdaptiveParams);
+    out->threshold = 0.05f;
+    out->darkFloor = 0.01f;
+    out->minFrames = 8;
+    out->maxFrames = 1024;
+    return RT_OK;
+}
+
+int rt_adaptive_select_buffers(RtContext* ctx, const RtAdaptiveParams* p, int width, int height, const void* d_sum, const void* d_moments, void* d_tile_error,
+                               void* d_tiles, void* d_counts)
+{
+    static const char* call = "rt_adaptive_select_buffers";
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    rt_ad_job job;
+    int rc = adaptive_check_params(ctx, call, p, &job);
+    if (rc) return rc;
+    if ((rc = check_image_size(ctx, call, width, height, 1ll << 30))) return rc;
+    const size_t n = (size_t)width * height, tiles = (size_t)rt_ad::tiles_total(width, height);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const struct { const char* what; const void* p; size_t bytes; bool out; } mem[5] = {
+        {"d_sum", d_sum, n * 16, false}, {"d_moments", d_moments, n * 16, false}, {"d_tile_error", d_tile_error, tiles * 4, true},
+        {"d_tiles", d_tiles, tiles * 4, true}, {"d_counts", d_counts, 16, true}};
+    for (const auto& m : mem)
+        if ((rc = check_device_range(ctx, call, m.what, m.p, m.bytes))) return rc;
+    for (int i = 0; i < 5; i++)
+        for (int j = i + 1; j < 5; j++)
+            if ((mem[i].out || mem[j].out) && ranges_overlap(mem[i].p, mem[i].bytes, mem[j].p, mem[j].bytes))
+                return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s overlaps %s", call, mem[j].what, mem[i].what);
+    RT_FLUSH(ctx);
+    HIP_TRY(ctx, rt_ad::enqueue_select(joined(ctx), job, width, height, d_sum, d_moments, (float*)d_tile_error, (uint32_t*)d_tiles, (uint32_t*)d_counts));
+    return RT_OK;
+}
+
+/* what every context call of this header starts with */
+static int adaptive_check_context(RtContext* ctx, const char* call)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (ctx->W == 0) return fail(ctx, RT_ERR_STATE, "%s before rt_resize", call);
+    return RT_OK;
+}
+
+/* The context's tile errors, list and counts exist, for its rows as they are now */
+static int adaptive_buffers(RtContext* ctx)
+{
+    const long long total = rt_ad::tiles_total(ctx->W, ctx->localRows);
+    if (!ctx->dAdCounts) HIP_TRY(ctx, hipMalloc(&ctx->dAdCounts, 16));
+    if (ctx->adTilesTotal == total) return RT_OK;
+    const size_t bytes = (size_t)(total > 0 ? total : 1) * 4;
+    float* e = nullptr;
+    uint32_t* t = nullptr;
+    HIP_TRY(ctx, hipMalloc(&e, bytes));
+    const hipError_t err = hipMalloc(&t, bytes);
+    if (err != hipSuccess) {
+        hipFree(e);
+        HIP_TRY(ctx, err);
+    }
+    ctx->dAdTileError = e; /* (rt_resize freed the old pair) */
+    ctx->dAdTiles = t;
+    ctx->adTilesTotal = total;
+    return RT_OK;
+}
+
+int rt_adaptive_select(RtContext* ctx, const RtAdaptiveParams* p, RtAdaptiveResult* out)
+{
+    static const char* call = "rt_adaptive_select";
+    int rc = adaptive_check_context(ctx, call);
+    if (rc) return rc;
+    rt_ad_job job;
+    if ((rc = adaptive_check_params(ctx, call, p, &job))) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = variance_images(ctx))) return rc;
+    if ((rc = adaptive_buffers(ctx))) return rc;
+    ctx->adHaveList = ctx->adHaveErrors = false; /* until this selection has come back */
+    hipStream_t st = joined(ctx);
+    uint32_t counts[4] = {0, 0, 0, 0};
+    if (ctx->adTilesTotal > 0)
+        HIP_TRY(ctx, rt_ad::enqueue_select(st, job, ctx->W, ctx->localRows, accum_target(ctx), ctx->dMoments, ctx->dAdTileError, ctx->dAdTiles, ctx->dAdCounts));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    flush_timer(ctx);
+    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
+    if (ctx->adTilesTotal > 0) HIP_TRY(ctx, hipMemcpy(counts, ctx->dAdCounts, sizeof(counts), hipMemcpyDeviceToHost));
+    ctx->adTilesActive = counts[0];
+    ctx->adPixelsActive = counts[1];
+    ctx->adHaveList = ctx->adHaveErrors = true;
+    if (out) {
+        out->tiles_total = (uint32_t)ctx->adTilesTotal;
+        out->tiles_active = counts[0];
+        out->pixels_active = counts[1];
+        out->reserved = 0;
+    }
+    return RT_OK;
+}
+
+int rt_adaptive_set_tiles(RtContext* ctx, const uint32_t* tiles, int n)
+{
+    static const char* call = "rt_adaptive_set_tiles";
+    int rc = adaptive_check_context(ctx, call);
+    if (rc) return rc;
+    if (n < 0 || (n > 0 && !tiles)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: %s", call, n < 0 ? "n < 0" : "tiles is null");
+    uint32_t pixels = 0;
+    if (const long long bad = rt_ad::check_tiles(tiles, n, ctx->W, ctx->localRows, &pixels))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: entry %lld (tile %u) is not above its predecessor or not below tiles_total = %lld", call, bad - 1, tiles[bad - 1],
+                    rt_ad::tiles_total(ctx->W, ctx->localRows));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = adaptive_buffers(ctx))) return rc;
+    ctx->adHaveList = false;
+    if ((rc = stage_upload(ctx, ctx->dAdTiles, tiles, (size_t)n * 4))) return rc; /* stream-ordered: behind the launches that read the old list */
+    ctx->adTilesActive = (uint32_t)n;
+    ctx->adPixelsActive = pixels;
+    ctx->adHaveList = true;
+    return RT_OK;
+}
+
+int rt_adaptive_read_tiles(RtContext* ctx, uint32_t* tiles, int capacity, int* n)
+{
+    static const char* call = "rt_adaptive_read_tiles";
+    int rc = adaptive_check_context(ctx, call);
+    if (rc) return rc;
+    if (!n) return fail(ctx, RT_ERR_INVALID_ARG, "%s: n is null", call);
+    if (!ctx->adHaveList) return fail(ctx, RT_ERR_STATE, "%s: no tile list (rt_adaptive_select or rt_adaptive_set_tiles makes one; rt_resize drops it)", call);
+    *n = (int)ctx->adTilesActive;
+    if (!tiles) return RT_OK;
+    if (capacity < (int)ctx->adTilesActive) return fail(ctx, RT_ERR_INVALID_ARG, "%s: the list has %u entries, capacity is %d", call, ctx->adTilesActive, capacity);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    if (ctx->adTilesActive) HIP_TRY(ctx, hipMemcpy(tiles, ctx->dAdTiles, (size_t)ctx->adTilesActive * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_adaptive_read_tile_error(RtContext* ctx, float* err, size_t bytes)
+{
+    static const char* call = "rt_adaptive_read_tile_error";
+    int rc = adaptive_check_context(ctx, call);
+    if (rc) return rc;
+    if (!ctx->adHaveErrors) return fail(ctx, RT_ERR_STATE, "%s: no rt_adaptive_select since the last rt_resize", call);
+    if (bytes != (size_t)ctx->adTilesTotal * 4 || (!err && bytes))
+        return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%lld tiles x 4), got %zu%s", call, (size_t)ctx->adTilesTotal * 4, ctx->adTilesTotal, bytes,
+                    err ? "" : " and a null pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    if (bytes) HIP_TRY(ctx, hipMemcpy(err, ctx->dAdTileError, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* Frames frame0 ... frame0 + nFrames - 1 of the current (non-empty) list: one trace kernel and, for nFrames > 1, the list's accumulate
+ * step.  *unstaged = true (and nothing enqueued) when nFrames > 1 and there is no staging slab for them. */
+static int adaptive_launch(RtContext* ctx, int frame0, int nFrames, bool* unstaged)
+{
+    *unstaged = false;
+    KArgs a;
+    fill_args(ctx, frame0, nFrames, a);
+    LaunchPlan plan;
+    int rc = choose_variant(ctx, a, plan);
+    if (rc) return rc;
+    if ((rc = prepare_records(ctx, plan))) return rc;
+    const size_t nPix = (size_t)ctx->localRows * ctx->W;
+    if (nFrames > 1) {
+        if ((rc = prepare_staging(ctx, a, nFrames, nPix, 0, false, unstaged))) return rc;
+        if (*unstaged) return RT_OK;
+    }
+    if (!ctx->dAdQueue) {
+        HIP_TRY(ctx, hipMalloc(&ctx->dAdQueue, sizeof(unsigned long long)));
+        HIP_TRY(ctx, hipMemsetAsync(ctx->dAdQueue, 0, sizeof(unsigned long long), joined(ctx)));
+        ctx->adQueueNext = 0;
+    }
+    a.suspendNum = ctx->tuner.decided; /* scheduling only; the tuner itself is not sampled by these launches */
+    rt_plan::Work w;
+    w.tiles = (int)ctx->adTilesActive;
+    w.nFrames = nFrames;
+    w.flat = ctx->flatScene;
+    w.spp = ctx->params.numRaysPerPixel;
+    w.frameGroupOverride = ctx->frameGroupOverride;
+    w.gridOverride = ctx->gridOverride;
+    w.residentGroups = plan.resident;
+    w.wavesPerGroup = plan.shape.wavesPerGroup;
+    const rt_plan::PartPlan pp = rt_plan::plan_part(w, 0, 1, ctx->adQueueNext);
+    a.tileOrder = ctx->dAdTiles;
+    a.tileCost = nullptr;
+    a.frameGroup = pp.frameGroup;
+    a.frameGroupShift = pp.frameGroupShift;
+    a.frameGroups = pp.frameGroups;
+    a.launchTiles = pp.partTiles;
+    a.launchItems = (int)pp.items;
+    a.orderOffset = 0;
+    a.orderStride = 1;
+    a.queueStart = pp.queueStart;
+    a.pxCold = (float4*)ctx->dPxCold; /* the main stream's slot */
+    a.tileQueue = ctx->dAdQueue;
+    a.tileQueueBase = pp.tileQueueBase;
+    if (ctx->verbose) fprintf(stderr, "[raytrace_hip] adaptive launch variant=%d tiles=%d of %d frames=%d grid=%d x %d waves\n", plan.shape.variant, pp.partTiles, a.tilesX * a.tilesY, nFrames, pp.grid, plan.shape.wavesPerGroup);
+    hipStream_t st = joined(ctx);
+    hipLaunchKernelGGL(plan.kern, dim3(pp.grid), dim3(plan.shape.blockThreads), plan.shape.ldsBytes, st, a);
+    HIP_TRY(ctx, hipGetLastError()); /* a refused launch ran no wave: the device counter did not move */
+    ctx->adQueueNext = pp.queueNext;
+    if (nFrames > 1)
+        HIP_TRY(ctx, rt_ad::enqueue_accumulate_tiles(st, ctx->dAdTiles, (int)ctx->adTilesActive, ctx->W, ctx->localRows, ctx->dStaging[0], nFrames, nPix, a.accumulated,
+                                                     a.frameRender));
+    ctx->pixelFrames += (uint64_t)ctx->adPixelsActive * nFrames;
+    return RT_OK;
+}
+
+int rt_adaptive_render_frames(RtContext* ctx, int n)
+{
+    static const char* call = "rt_adaptive_render_frames";
+    int rc = check_renderable(ctx);
+    if (rc) return rc;
+    if (n < 0) return fail(ctx, RT_ERR_INVALID_ARG, "%s: n < 0", call);
+    if (!ctx->params.accumulate) return fail(ctx, RT_ERR_STATE, "%s: params.accumulate is 0: a frame that adds nothing has nothing to be selective about", call);
+    if (!ctx->adHaveList) return fail(ctx, RT_ERR_STATE, "%s: no tile list (rt_adaptive_select or rt_adaptive_set_tiles makes one; rt_resize drops it)", call);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if (ctx->adTilesActive == 0) { /* nothing to render: the frames still count */
+        ctx->frame += n;
+        return RT_OK;
+    }
+    bool fuse = ctx->fuseFrames;
+    while (n > 0) {
+        const int k = fuse ? (n < ctx->fuseCap ? n : ctx->fuseCap) : 1;
+        bool unstaged = false;
+        if ((rc = adaptive_launch(ctx, ctx->frame, k, &unstaged))) return rc;
+        if (unstaged) { /* no slab: one launch per frame, the same bits */
+            fuse = false;
+            continue;
+        }
+        ctx->frame += k;
+        n -= k;
+    }
     return RT_OK;
 }
 

@@ -45,6 +45,9 @@ MOTION_SYMBOLS = ["rt_render_aov_centre", "rt_render_aov_centre_to_device", "rt_
 VARIANCE_SYMBOLS = ["rt_denoise_variance_default_params", "rt_moments_update_buffers", "rt_denoise_variance_buffers", "rt_variance_update",
                     "rt_variance_reset", "rt_variance_carry", "rt_variance_read_moments", "rt_variance_moments_to_device", "rt_denoise_variance",
                     "rt_denoise_variance_to_device"]
+# every symbol include/rt_adaptive.h declares
+ADAPTIVE_SYMBOLS = ["rt_adaptive_default_params", "rt_adaptive_select_buffers", "rt_adaptive_select", "rt_adaptive_set_tiles", "rt_adaptive_read_tiles",
+                    "rt_adaptive_read_tile_error", "rt_adaptive_render_frames"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -127,6 +130,13 @@ class HipApi(abi.CApi):
         "variance_moments_to_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "denoise_variance": (C.c_int, [C.c_void_p, C.POINTER(abi.RtVarianceDenoiseParams), C.c_int, C.c_void_p, C.c_size_t]),
         "denoise_variance_to_device": (C.c_int, [C.c_void_p, C.POINTER(abi.RtVarianceDenoiseParams), C.c_int, C.c_void_p, C.c_size_t]),
+        "adaptive_default_params": (C.c_int, [C.POINTER(abi.RtAdaptiveParams)]),
+        "adaptive_select_buffers": (C.c_int, [C.c_void_p, C.POINTER(abi.RtAdaptiveParams), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+        "adaptive_select": (C.c_int, [C.c_void_p, C.POINTER(abi.RtAdaptiveParams), C.POINTER(abi.RtAdaptiveResult)]),
+        "adaptive_set_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+        "adaptive_read_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
+        "adaptive_read_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+        "adaptive_render_frames": (C.c_int, [C.c_void_p, C.c_int]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -258,6 +268,21 @@ class HipApi(abi.CApi):
         for k, v in fields.items():
             if k not in dict(abi.RtVarianceDenoiseParams._fields_):
                 raise TypeError(f"RtVarianceDenoiseParams has no field {k!r}")
+            if k == "reserved":
+                p.reserved[:] = [int(x) for x in v]
+            else:
+                setattr(p, k, v)
+        return p
+
+    def adaptive_params(self, **fields):
+        """rt_adaptive_default_params, with `fields` (threshold, darkFloor, minFrames, maxFrames) set on top."""
+        p = abi.RtAdaptiveParams()
+        rc = self.adaptive_default_params(C.byref(p))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, "rt_adaptive_default_params failed")
+        for k, v in fields.items():
+            if k not in dict(abi.RtAdaptiveParams._fields_):
+                raise TypeError(f"RtAdaptiveParams has no field {k!r}")
             if k == "reserved":
                 p.reserved[:] = [int(x) for x in v]
             else:
@@ -664,6 +689,49 @@ class HipTracer(abi.Tracer):
         """rt_denoise_variance_to_device: the same image into device memory (rows * W * 16 bytes), enqueued; complete after synchronize()."""
         p = params if params is not None else self.api.variance_denoise_params()
         self._check(self.api.denoise_variance_to_device(self.h, C.byref(p), int(aov_frame), ptr, int(nbytes)))
+
+    def adaptive_params(self, **fields):
+        """api.adaptive_params: the defaults of rt_adaptive_default_params with `fields` set on top."""
+        return self.api.adaptive_params(**fields)
+
+    def adaptive_select_buffers(self, width, height, sum_ptr, moments_ptr, tile_error_ptr, tiles_ptr, counts_ptr, params=None):
+        """rt_adaptive_select_buffers (include/rt_adaptive.h): tile errors, the ordered list of active tiles and uint32[4] counts =
+        (tiles_active, pixels_active, 0, 0), all caller-owned device memory.  Needs no scene and no resize; enqueued."""
+        p = params if params is not None else self.api.adaptive_params()
+        self._check(self.api.adaptive_select_buffers(self.h, C.byref(p), int(width), int(height), sum_ptr, moments_ptr, tile_error_ptr, tiles_ptr, counts_ptr))
+
+    def adaptive_select(self, params=None):
+        """rt_adaptive_select: the context's tiles whose error exceeds params.threshold become its current list.  Returns
+        {tiles_total, tiles_active, pixels_active}.  Does not run variance_update."""
+        p = params if params is not None else self.api.adaptive_params()
+        out = abi.RtAdaptiveResult()
+        self._check(self.api.adaptive_select(self.h, C.byref(p), C.byref(out)))
+        return out.as_dict()
+
+    def adaptive_set_tiles(self, tiles):
+        """rt_adaptive_set_tiles: a list from the host (strictly increasing tile indices) in place of a selected one."""
+        t = np.ascontiguousarray(tiles, dtype=np.uint32).reshape(-1)
+        self._check(self.api.adaptive_set_tiles(self.h, t.ctypes.data if t.size else None, int(t.size)))
+
+    def adaptive_tiles(self):
+        """rt_adaptive_read_tiles: the current list, uint32, increasing."""
+        n = C.c_int(0)
+        self._check(self.api.adaptive_read_tiles(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            self._check(self.api.adaptive_read_tiles(self.h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def adaptive_tile_error(self):
+        """rt_adaptive_read_tile_error: (tilesY, tilesX) float32, the tile errors of the last adaptive_select (row 0 at the bottom)."""
+        ty, tx = (max(self.local_rows(), 0) + 7) // 8, (self.width + 7) // 8
+        out = np.zeros((ty, tx), dtype=np.float32)
+        self._check(self.api.adaptive_read_tile_error(self.h, out.ctypes.data if out.size else None, out.nbytes))
+        return out
+
+    def adaptive_render_frames(self, n):
+        """rt_adaptive_render_frames: frames Frame ... Frame + n - 1 of the current list's tiles; every other pixel keeps its bits."""
+        self._check(self.api.adaptive_render_frames(self.h, int(n)))
 
     def debug_math_eval(self, op, x, y=None):
         x = np.ascontiguousarray(x, dtype=np.float32)

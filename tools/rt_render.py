@@ -36,6 +36,15 @@ each (rt_variance_update, include/rt_variance.h) and writes the accumulated imag
 moments give, as a heatmap: grey = sd / --variance-scale (default 0.25), pure red above the scale, blue where fewer than two batches
 are known.
 
+    python tools/rt_render.py 3 --frames 64 --adaptive 0.05 --png adaptive.png --adaptive-png counts.png
+
+--adaptive THRESHOLD spends the --frames frames (as a budget of frames x pixels) where the image is noisy (include/rt_adaptive.h): two
+full batches of --adaptive-batch frames (default 4) with a batch of luminance moments after each (rt_variance_update), then
+rt_adaptive_select — the 8 x 8 tiles whose relative standard error of the mean luminance exceeds THRESHOLD, with --adaptive-min /
+--adaptive-max frames per pixel (default: the library's) — and rt_adaptive_render_frames of the next batch on those tiles alone, until no
+tile is active or the budget is spent.  --png / --pfm then hold the per-pixel resolve (rt_resolve: every pixel divided by its own frame
+count), and --adaptive-png FILE writes that count, white = the largest.
+
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
 icosphere:SUBDIV[:DISPLACEMENT_SEED[:RADIUS]] | a JSON mesh spec); a stand-in has to have the
@@ -70,6 +79,11 @@ def main():
     ap.add_argument("--variance-png", metavar="FILE", help="heatmap of the standard deviation of the mean (from the luminance moments)")
     ap.add_argument("--variance-batches", type=int, default=8, help="equal batches the frames are rendered in for the moments (default 8)")
     ap.add_argument("--variance-scale", type=float, default=0.25, help="standard deviation drawn white; above it a pixel is red")
+    ap.add_argument("--adaptive", type=float, metavar="THRESHOLD", help="render further frames only on tiles whose relative standard error exceeds THRESHOLD (rt_adaptive_*)")
+    ap.add_argument("--adaptive-min", type=int, help="frames every pixel gets at least (default: the library's)")
+    ap.add_argument("--adaptive-max", type=int, help="frames after which a pixel no longer keeps its tile active, 0 = no cap (default: the library's)")
+    ap.add_argument("--adaptive-batch", type=int, default=4, help="frames between two selections = frames of one batch of moments (default 4)")
+    ap.add_argument("--adaptive-png", metavar="FILE", help="the per-pixel frame count after --adaptive, white = the largest")
     ap.add_argument("--reproject-png", metavar="PREFIX", help="move the camera, reproject, render on; PREFIX_resolved.png and PREFIX_history.png")
     ap.add_argument("--reproject-move", metavar="DX,DY,DZ", default="0.05,0.02,0.03", help="camera offset in world units")
     ap.add_argument("--reproject-frames", type=int, default=4, help="frames rendered after the reprojection")
@@ -114,8 +128,31 @@ def main():
     variance = bool(a.vdenoise_png or a.variance_png)
     if variance and (a.variance_batches < 2 or frames % a.variance_batches):
         ap.error(f"--variance-batches must be at least 2 and divide --frames ({frames})")
+    adaptive = None
+    if a.adaptive is not None:
+        if variance or a.resume or a.adaptive_batch < 1 or frames < 2 * a.adaptive_batch:
+            ap.error("--adaptive needs --frames >= 2 x --adaptive-batch and goes with neither --resume nor the --variance outputs")
+        fields = {k: v for k, v in (("minFrames", a.adaptive_min), ("maxFrames", a.adaptive_max)) if v is not None}
+        adaptive = api.adaptive_params(threshold=a.adaptive, **fields)
+    elif a.adaptive_png:
+        ap.error("--adaptive-png needs --adaptive")
     tr.reset_counters(); tr.timer_begin()
-    if variance:
+    if adaptive is not None:
+        batch, budget, rounds, active = a.adaptive_batch, frames * w * h, 0, None
+        for _ in range(2):
+            mgr.RenderFrames(batch)
+            tr.variance_update()
+        spent = 2 * batch * w * h
+        while True:
+            active = tr.adaptive_select(adaptive)
+            if active["tiles_active"] == 0 or spent + active["pixels_active"] * batch > budget:
+                break
+            tr.adaptive_render_frames(batch)
+            tr.variance_update()
+            spent += active["pixels_active"] * batch
+            rounds += 1
+        mgr.numAccumulatedFrames = tr.frame()  # the manager did not see the adaptive frames
+    elif variance:
         tr.variance_reset()  # (a resumed sum is where the batches start from)
         for _ in range(a.variance_batches):
             mgr.RenderFrames(frames // a.variance_batches)
@@ -126,8 +163,21 @@ def main():
     print(json.dumps({"scene": scene.name, "size": [w, h], "frames": frames, "spp_total": (mgr.numAccumulatedFrames - 1) * mgr.numRaysPerPixel,
                       "gpu_ms": c["gpuMs"], "Mrays_per_s": c["segments"] / max(c["gpuMs"], 1e-9) / 1e3}))
     disp = pkg.display.RayTraceDisplay(mgr)
-    if a.png: disp.save_png(a.png)
-    if a.pfm: disp.save_pfm(a.pfm)
+    if adaptive is not None:  # pixels hold different numbers of frames: the per-pixel resolve, not Display.shader's division by Frame
+        import numpy as np
+        img = tr.resolve()
+        count = img[..., 3]
+        if a.png: pkg.display.write_png(a.png, pkg.display.linear_srgb8(img))
+        if a.pfm: pkg.display.write_pfm(a.pfm, img[..., :3])
+        if a.adaptive_png:
+            grey = np.repeat((count / max(float(count.max()), 1.0))[..., None], 3, axis=-1).astype(np.float32)
+            pkg.display.write_png(a.adaptive_png, pkg.display.linear_srgb8(grey))
+        print(json.dumps({"adaptive": a.adaptive, "minFrames": adaptive.minFrames, "maxFrames": adaptive.maxFrames, "batch": a.adaptive_batch, "selections": rounds + 1,
+                          "tiles_active_at_the_end": active["tiles_active"], "pixel_frames": int(c["pixelFrames"]), "budget": frames * w * h,
+                          "frames_per_pixel": {"min": float(count.min()), "mean": float(count.mean()), "max": float(count.max())}}))
+    else:
+        if a.png: disp.save_png(a.png)
+        if a.pfm: disp.save_pfm(a.pfm)
     if a.checkpoint: pkg.display.save_checkpoint(a.checkpoint, mgr)
     if a.cost_png:
         cost = tr.render_cost(a.cost_frame)
