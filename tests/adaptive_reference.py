@@ -136,7 +136,8 @@ def hazard_images(w, h, seed, minFrames=4, maxFrames=64, **_):
     m[..., 1] = (mean * mean) * (F(1) + rel * rel) * nb
     m[..., 3] = nb
     inner = [(j, i) for j in range(ty) for i in range(tx) if TILE * (i + 1) <= w and TILE * (j + 1) <= h]
-    ragged = [(j, i) for j in range(ty) for i in range(tx) if (j, i) not in inner]
+    whole = set(inner)
+    ragged = [(j, i) for j in range(ty) for i in range(tx) if (j, i) not in whole]
     every = inner + ragged
     # the all-zero tile: sum of L^2 = nb mu^2 exactly (small integers), counts inside the limits
     zj, zi = (inner or every)[0]
@@ -158,5 +159,21 @@ def hazard_images(w, h, seed, minFrames=4, maxFrames=64, **_):
     return np.ascontiguousarray(s, dtype=F), np.ascontiguousarray(m, dtype=F), planted
 
 
+def planted_images(w, h, active):
+    """(S, M) in which every pixel has an error of exactly +0 under minFrames = 4, maxFrames = 0 (16 frames, and the zero variance of
+    hazard_images' all-zero tile), except one pixel in each tile of `active`: its S.a = 1 is below minFrames, which rule 3 turns
+    into +inf.  The pixel's place inside its tile moves with the tile's index and is clamped to the image."""
+    tx, _ = tiles_xy(w, h)
+    s = np.empty((h, w, 4), dtype=F)
+    m = np.empty((h, w, 4), dtype=F)
+    s[...] = (F(3), F(2), F(1), F(16))
+    m[...] = (F(4), F(8), F(0), F(2))
+    t = np.asarray(active, dtype=np.int64).reshape(-1)
+    y = np.minimum(TILE * (t // tx) + (t // TILE) % TILE, h - 1)
+    x = np.minimum(TILE * (t % tx) + t % TILE, w - 1)
+    s[y, x, 3] = F(1)
+    return s, m
+
+
 __all__ = ["F", "TILE", "PARAM_SETS", "tiles_xy", "pixel_error", "tile_pixels", "tile_error", "select", "tile_mask", "add_frames", "checkerboard",
-           "hazards", "hazard_images"]
+           "hazards", "hazard_images", "planted_images"]
