@@ -85,6 +85,24 @@ AOV_DTYPE = np.dtype([
 AOV_HIT_CLASS_MASK = 3   # RtPixelAov.hit bits 0-1: 0 miss, 1 opaque, 2 glass
 AOV_HIT_BACKFACE = 0x100  # bit 8: HitInfo.isBackface
 
+# ---- rt_query.h -------------------------------------------------------------
+# RtRay / RtRayHit: one record per ray of the rt_query_* calls
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("tmax", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
+RAYHIT_DTYPE = np.dtype([
+    ("dst", "<f4"), ("normal", "<f4", (3,)), ("pos", "<f4", (3,)), ("hit", "<u4"), ("object", "<i4"), ("triangle", "<i4"), ("reserved", "<u4", (2,))])
+QUERY_MAX_RAYS = 1 << 26
+assert RAY_DTYPE.itemsize == 32 and RAYHIT_DTYPE.itemsize == 48
+
+
+def make_rays(origins, dirs, tmax=np.inf):
+    """n records of RAY_DTYPE from (n, 3) origins and directions and a scalar or per-ray tmax."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros(len(o), dtype=RAY_DTYPE)
+    r["origin"] = o
+    r["dir"] = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+    r["tmax"] = tmax
+    return r
+
 
 class RtDenoiseParams(C.Structure):
     """include/rt_denoise.h: the parameters of the a-trous filter (32 bytes; struct_size is the handshake)."""

@@ -32,12 +32,14 @@
 #include "../../include/rt_variance.h"
 #include "../../include/rt_adaptive.h"
 #include "../../include/rt_motion.h"
+#include "../../include/rt_query.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
 #include "rt_reproject_launch.h"
 #include "rt_variance_launch.h"
 #include "rt_adaptive_launch.h"
+#include "rt_query_launch.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -190,6 +192,14 @@ struct RtContext {
     size_t aovOutBytes = 0;
     unsigned long long* dAovWords = nullptr;
     bool aovUnreported = false;
+    /* rt_query_* (include/rt_query.h): the host forms' device rays and results, kept between calls (grow on demand); the pass's own counter
+     * slot (only its watchdog word is ever written); a buffer-form pass whose watchdog word has not been read back yet */
+    void* dQueryRays = nullptr;
+    size_t queryRaysBytes = 0;
+    void* dQueryOut = nullptr;
+    size_t queryOutBytes = 0;
+    unsigned long long* dQueryWords = nullptr;
+    bool queryUnreported = false;
     /* rt_denoise (include/rt_denoise.h): the filter's two colour images and packed guide image, and the AOV records of the two context
      * calls' internal pass; kept between calls (grow on demand) */
     void* dDnScratch = nullptr;
@@ -518,6 +528,9 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dDisplay);
     hipFree(ctx->dAovOut);
     hipFree(ctx->dAovWords);
+    hipFree(ctx->dQueryRays);
+    hipFree(ctx->dQueryOut);
+    hipFree(ctx->dQueryWords);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
@@ -1388,6 +1401,7 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
 extern "C" {
 
 static int aov_report(RtContext* ctx, const char* call);
+static int query_report(RtContext* ctx, const char* call);
 
 static int check_renderable(RtContext* ctx)
 {
@@ -1477,7 +1491,8 @@ int rt_synchronize(RtContext* ctx)
     RT_FLUSH(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
-    return aov_report(ctx, "rt_synchronize"); /* a device AOV pass completes here: so does its watchdog report (no-op otherwise) */
+    if (int rc = aov_report(ctx, "rt_synchronize")) return rc; /* a device AOV pass completes here: so does its watchdog report (no-op otherwise) */
+    return query_report(ctx, "rt_synchronize"); /* and that of a buffer-form ray query (include/rt_query.h) */
 }
 
 int rt_get_frame(const RtContext* ctx) { return ctx ? ctx->frame : RT_ERR_INVALID_ARG; }
@@ -2183,6 +2198,125 @@ int rt_render_aov_to_device(RtContext* ctx, int frame, void* d_out, size_t bytes
 /* include/rt_motion.h, A */
 int rt_render_aov_centre(RtContext* ctx, RtPixelAov* out, size_t bytes) { return aov_to_host(ctx, "rt_render_aov_centre", RT_AOV_CENTRE, out, bytes); }
 int rt_render_aov_centre_to_device(RtContext* ctx, void* d_out, size_t bytes) { return aov_to_device(ctx, "rt_render_aov_centre_to_device", RT_AOV_CENTRE, d_out, bytes); }
+
+/* ---- rt_query_closest / rt_query_occluded and their *_buffers forms (include/rt_query.h): caller-made rays against the scene ----------
+ * One launch of rt_query_kernel (rt_kernels.h) on the joined main stream, built like the AOV pass: the context's in nothing but the scene
+ * and the stream.  It needs neither an image nor parameters — fill_args as rt_debug_intersect calls it; the kernel reads the scene fields,
+ * stackEntries and travLimit alone — a counter slot of its own (ctx->dQueryWords), no render target, no tile queue, no pixel records.
+ * The checks and the block and grid arithmetic are rt_query_launch.h's. */
+static int query_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut, bool any)
+{
+    KArgs a;
+    fill_args(ctx, 1, 1, a);
+    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
+    void (*kern)(const KArgs, const float4*, int, void*, const uint32_t*) =
+        any ? (many ? rtk::rt_query_kernel<false, true, true> : ctx->flatScene ? rtk::rt_query_kernel<true, false, true> : rtk::rt_query_kernel<false, false, true>)
+            : (many ? rtk::rt_query_kernel<false, true, false> : ctx->flatScene ? rtk::rt_query_kernel<true, false, false> : rtk::rt_query_kernel<false, false, false>);
+    /* a wave region of the trace kernel, single waves, no cache, no pool */
+    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
+    a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
+    a.frameRender = nullptr;
+    a.accumulated = nullptr;
+    a.tileQueue = nullptr;
+    a.tileOrder = nullptr;
+    a.tileCost = nullptr;
+    a.pxCold = nullptr;
+    a.staging = nullptr;
+    if (!ctx->dQueryWords) HIP_TRY(ctx, hipMalloc(&ctx->dQueryWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
+    a.counters = ctx->dQueryWords;
+    long long resident = 0; /* every wave the device keeps resident; the blocks are strided over them */
+    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &resident)) return rc;
+    const long long grid = rt_qr::grid(rt_qr::blocks(n), resident, ctx->gridOverride);
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dQueryWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (const float4*)dRays, n, dOut, (const uint32_t*)ctx->dUnitTri);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
+static int query_fired(RtContext* ctx, unsigned long long* fired)
+{
+    *fired = 0;
+    HIP_TRY(ctx, hipMemcpy(fired, ctx->dQueryWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the report of a buffer-form pass that has not been reported yet */
+static int query_report(RtContext* ctx, const char* call)
+{
+    if (!ctx->queryUnreported) return RT_OK;
+    ctx->queryUnreported = false;
+    unsigned long long fired = 0;
+    if (int rc = query_fired(ctx, &fired)) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call: "
+                           "walks were cut short, that call's records or answers are not valid (the context's images are not affected)", call, fired);
+    return RT_OK;
+}
+
+/* what the four calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch */
+static int query_check(RtContext* ctx, const char* call, const void* rays, int n, const void* out, size_t outPerRay, size_t* rayBytes, size_t* outBytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    const char* why = "";
+    if (int rc = rt_qr::check_batch(rays, n, out, outPerRay, rayBytes, outBytes, &why)) return fail(ctx, rc, "%s: %s", call, why);
+    if (!ctx->haveScene) return fail(ctx, RT_ERR_STATE, "%s before rt_upload_scene", call);
+    return RT_OK;
+}
+
+/* a buffer-form pass still unreported: synchronise and report it before this call's own pass clears the word */
+static int query_settle(RtContext* ctx, const char* call)
+{
+    if (!ctx->queryUnreported) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    return query_report(ctx, call);
+}
+
+static int query_to_host(RtContext* ctx, const char* call, const RtRay* rays, int n, void* out, size_t outPerRay, bool any)
+{
+    size_t rayBytes = 0, outBytes = 0;
+    int rc = query_check(ctx, call, rays, n, out, outPerRay, &rayBytes, &outBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = query_settle(ctx, call))) return rc;
+    if (n == 0) return RT_OK;
+    if ((rc = grow_scratch(ctx, &ctx->dQueryRays, &ctx->queryRaysBytes, rayBytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dQueryOut, &ctx->queryOutBytes, outBytes))) return rc;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dQueryRays, rays, rayBytes, hipMemcpyHostToDevice, st));
+    if ((rc = query_enqueue(ctx, ctx->dQueryRays, n, ctx->dQueryOut, any))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    unsigned long long fired = 0;
+    if ((rc = query_fired(ctx, &fired))) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in this pass: walks were cut short, the %s are not valid "
+                           "(the context's images are not affected)", call, fired, any ? "answers" : "records");
+    HIP_TRY(ctx, hipMemcpy(out, ctx->dQueryOut, outBytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+static int query_to_device(RtContext* ctx, const char* call, const void* d_rays, int n, void* d_out, size_t outPerRay, bool any)
+{
+    size_t rayBytes = 0, outBytes = 0;
+    int rc = query_check(ctx, call, d_rays, n, d_out, outPerRay, &rayBytes, &outBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n > 0) { /* the kernel reads and writes through these pointers */
+        if ((rc = check_device_range(ctx, call, "d_rays", d_rays, rayBytes))) return rc;
+        if ((rc = check_device_range(ctx, call, any ? "d_occluded" : "d_hits", d_out, outBytes))) return rc;
+    }
+    RT_FLUSH(ctx);
+    if ((rc = query_settle(ctx, call))) return rc;
+    if (n == 0) return RT_OK;
+    if ((rc = query_enqueue(ctx, d_rays, n, d_out, any))) return rc;
+    ctx->queryUnreported = true;
+    return RT_OK;
+}
+
+int rt_query_closest(RtContext* ctx, const RtRay* rays, int n, RtRayHit* hits) { return query_to_host(ctx, "rt_query_closest", rays, n, hits, sizeof(RtRayHit), false); }
+int rt_query_closest_buffers(RtContext* ctx, const void* d_rays, int n, void* d_hits) { return query_to_device(ctx, "rt_query_closest_buffers", d_rays, n, d_hits, sizeof(RtRayHit), false); }
+int rt_query_occluded(RtContext* ctx, const RtRay* rays, int n, uint32_t* occluded) { return query_to_host(ctx, "rt_query_occluded", rays, n, occluded, sizeof(uint32_t), true); }
+int rt_query_occluded_buffers(RtContext* ctx, const void* d_rays, int n, void* d_occluded) { return query_to_device(ctx, "rt_query_occluded_buffers", d_rays, n, d_occluded, sizeof(uint32_t), true); }
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main

@@ -242,8 +242,11 @@ struct Trav {
     bool cull;
 };
 
-template <bool STATS, bool FLAT, bool MANY>
-__device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st)
+/* ANY (include/rt_query.h, occlusion): a lane whose ray has an accepted hit with dst < tmax needs no more of the walk — the closest-hit
+ * walk accepts that hit too and only lowers dst afterwards — so it tests no further sphere here and leaves parked in RT_CODE_DONE.  The
+ * default (false) is the closest-hit walk every other caller gets: tmax is then not read. */
+template <bool STATS, bool FLAT, bool MANY, bool ANY = false>
+__device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f)
 {
     h.dst = RT_INF;
     h.obj = -1;
@@ -307,6 +310,7 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
             }
             cand |= ((keep0 ? 1u : 0u) << k) | ((keep1 ? 1u : 0u) << (k + 1));
         }
+        if (ANY && h.dst < tmax) cand = 0;
         while (cand) {
             phase_mark<STATS>(st, PH_SPHERE_ROOTS);
             const int k = __builtin_ctz(cand);
@@ -329,6 +333,7 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
                     h.dst = d;
                     h.obj = s;
                     h.backface = inside;
+                    if (ANY && d < tmax) cand = 0;
                 }
             }
         }
@@ -483,6 +488,10 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
     t.lpos = t.ldir = t.linv = rt_v3s(0.0f);
     t.triBase = 0;
     t.cull = true;
+    if (ANY && h.dst < tmax) { /* occluded by a sphere: no model to visit */
+        t.cur = RT_CODE_DONE;
+        t.cand = 0;
+    }
 }
 
 /* Model loop (RC:347-371) and per-model BVH traversal (RayTriangleBVH, RC:234-287) as
@@ -501,9 +510,9 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
  * the stragglers keep their state in `t`/`h`/LDS and resume at the next call.  The loop has a
  * single, wave-uniform exit (finished lanes park in RT_CODE_DONE instead of leaving one by
  * one), which keeps the loop-carried state in one set of registers. */
-template <bool STATS, bool SUSPEND, bool MANY, bool HOT = false>
+template <bool STATS, bool SUSPEND, bool MANY, bool HOT = false, bool ANY = false>
 __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* stackBase, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st,
-                                         const RT_LDS char* hotLds, const uint32_t hotUnits)
+                                         const RT_LDS char* hotLds, const uint32_t hotUnits, const float tmax = 0.0f)
 {
     const DModel* __restrict__ models = a.models;
     const DPair* __restrict__ pairs = a.pairs;
@@ -670,9 +679,14 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
                 if (h.dst < before) { /* RC:362-369 (an update strictly lowers dst) */
                     h.obj = a.nSpheres + t.m;
                     h.backface = h.det < 0;
+                    if (ANY && h.dst < tmax) break; /* (begin_intersect: the answer is known) */
                 }
             }
-            if (t.sp == 0) t.cur = RT_CODE_NEXT_MODEL;
+            if (ANY && h.dst < tmax) { /* park: the loop's exit stays the wave-uniform one */
+                t.cur = RT_CODE_DONE;
+                t.sp = 0;
+                t.cand = 0;
+            } else if (t.sp == 0) t.cur = RT_CODE_NEXT_MODEL;
             else t.cur = stackBase[(--t.sp) * RT_WAVE];
         }
         if (++watchdog > a.travLimit) { /* wave-uniform */
@@ -689,12 +703,15 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
  * Quality.Disabled — BASELINE configs 1 and 2): there is no tree to walk, so the
  * reference's nested form is already convergent.  Wave-uniform model loop, matrices in
  * SGPRs, the root leaf's triangles tested in order; no stack, no suspension. */
-template <bool STATS>
-__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st)
+/* ANY (begin_intersect): a lane whose answer is known tests no further triangle, and the wave leaves the model loop once that holds for
+ * all of its lanes (a vote: the loop stays wave-uniform). */
+template <bool STATS, bool ANY = false>
+__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st, const float tmax = 0.0f)
 {
     const RT_CAS DModel* cm = (const RT_CAS DModel*)a.models;
     const DTri* __restrict__ tris = a.tris;
     for (int m = 0; m < a.nModels; m++) {
+        if (ANY && __ballot(!(h.dst < tmax)) == 0ull) break;
         const RT_CAS DModel& M = cm[m];
         rt_f3 lpos = rt_v3(M.w2l[0] * rpos.x + M.w2l[1] * rpos.y + M.w2l[2] * rpos.z + M.w2l[3] * 1.0f,
                            M.w2l[4] * rpos.x + M.w2l[5] * rpos.y + M.w2l[6] * rpos.z + M.w2l[7] * 1.0f,
@@ -714,6 +731,7 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
         const bool cull = M.cullBackface != 0;
         for (uint32_t i = 0; i < count; i++) {
             phase_mark<STATS>(st, PH_TRI);
+            if (ANY && h.dst < tmax) break;
             const float before = h.dst;
             tri_test(tris, first + 3 * (int)i, lpos, ldir, cull, h.dst, h.tri, h.u, h.v, h.det);
             if (h.dst < before) {
@@ -1442,6 +1460,74 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             o[1] = q1;
             o[2] = q2;
             o[3] = q3;
+        }
+    }
+}
+
+/* rt_query_* (include/rt_query.h): CalculateRayCollision for n caller-made rays.  Not a flag of trace_body or of the AOV pass: there is
+ * no camera, no pixel and no frame here.  One ray per lane; a wave takes block b = 64 consecutive rays (the caller's order decides how
+ * coherent they are) and strides over the ceil(n / 64) blocks by the grid.  Single-wave workgroups without the top-of-tree cache and
+ * without the pool; LDS as a wave region of the trace kernel (rt_aov_kernel), so the host sizes it with rt_plan::wave_lds_bytes.  A ray
+ * (RtRay, 32 bytes) comes in as two 16-byte loads; a record (RtRayHit, 48 bytes) leaves as three 16-byte stores, an occlusion answer as
+ * one 4-byte store.  The traversal runs to completion (no suspension).
+ * The lanes past n of the last block load and store nothing, but stay in the wave through begin_intersect and traverse, whose votes
+ * count lanes: they carry the null ray and enter the traversal parked (BVH variants: RT_CODE_DONE).
+ * ANY: the occlusion form, `out` = one uint32 per ray; the early exit of begin_intersect / traverse / traverse_flat.  Otherwise `out` =
+ * the records, and `unitTri` as for rt_aov_kernel.  Only a.counters + 7 (the watchdog word of traverse()) is written besides `out`: the
+ * host points it at a word of this pass's own.  n <= RT_QUERY_MAX_RAYS = 2^26: 64 x blocks fits an int. */
+template <bool FLAT, bool MANY, bool ANY>
+__global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_query_kernel(const KArgs a, const float4* __restrict__ rays, const int n, void* __restrict__ out, const uint32_t* __restrict__ unitTri)
+{
+    extern __shared__ uint32_t s_lds[];
+    const int lane = (int)threadIdx.x;
+    uint32_t* const stackBase = &s_lds[lane];
+    uint32_t* const extBase = &s_lds[(size_t)(a.stackEntries + RT_PIXEL_FIELDS) * RT_WAVE + lane];
+    const int blocks = (n + RT_WAVE - 1) / RT_WAVE;
+    for (int b = (int)blockIdx.x; b < blocks; b += (int)gridDim.x) {
+        const int i = b * RT_WAVE + lane;
+        const bool live = i < n;
+        rt_f3 rpos = rt_v3s(0.0f), rdir = rt_v3s(0.0f);
+        float tmax = RT_INF;
+        if (live) { /* i < n: inside the n * 32 bytes the host checked */
+            const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+            rpos = rt_v3(r0.x, r0.y, r0.z);
+            tmax = r0.w;
+            rdir = rt_v3(r1.x, r1.y, r1.z);
+        }
+        /* CalculateRayCollision — RC:335-374 */
+        SceneHit h;
+        Trav t;
+        Stats st = {};
+        begin_intersect<false, FLAT, MANY, ANY>(a, rpos, rdir, extBase, h, t, st, tmax);
+        if (FLAT) {
+            if (!live) h.dst = -RT_INF; /* the flat form of parking: no test beats it, and with ANY it is below tmax = +inf */
+            traverse_flat<false, ANY>(a, rpos, rdir, h, st, tmax);
+        } else {
+            if (!live) {
+                t.cur = RT_CODE_DONE;
+                t.cand = 0;
+            }
+            traverse<false, false, MANY, false, ANY>(a, rpos, rdir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u, tmax);
+        }
+        if (!live) continue; /* (behind the traversal: nothing below votes) */
+        if (ANY) {
+            reinterpret_cast<uint32_t*>(out)[i] = (h.obj >= 0 && h.dst < tmax) ? 1u : 0u; /* i < n: inside the n * 4 bytes */
+        } else {
+            float4 q0 = make_float4(h.dst, 0.0f, 0.0f, 0.0f), q1 = make_float4(0.0f, 0.0f, 0.0f, __uint_as_float(0u));
+            float4 q2 = make_float4(__uint_as_float(0xffffffffu), __uint_as_float(0xffffffffu), 0.0f, 0.0f); /* object = triangle = -1 */
+            if (h.obj >= 0) {
+                rt_f3 hpos, normal;
+                resolve_hit(a, rpos, rdir, h, hpos, normal);
+                int tri = -1;
+                if (h.obj >= a.nSpheres) tri = unitTri ? (int)unitTri[h.tri] : h.tri / 3;
+                q0 = make_float4(h.dst, normal.x, normal.y, normal.z);
+                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float((a.materials[h.obj].flag == RT_MATERIAL_GLASS ? 2u : 1u) | (h.backface ? 0x100u : 0u)));
+                q2 = make_float4(__uint_as_float((uint32_t)h.obj), __uint_as_float((uint32_t)tri), 0.0f, 0.0f);
+            }
+            float4* const o = reinterpret_cast<float4*>(out) + 3 * (size_t)i; /* i < n: inside the n * 48 bytes */
+            o[0] = q0;
+            o[1] = q1;
+            o[2] = q2;
         }
     }
 }

@@ -48,6 +48,8 @@ VARIANCE_SYMBOLS = ["rt_denoise_variance_default_params", "rt_moments_update_buf
 # every symbol include/rt_adaptive.h declares
 ADAPTIVE_SYMBOLS = ["rt_adaptive_default_params", "rt_adaptive_select_buffers", "rt_adaptive_select", "rt_adaptive_set_tiles", "rt_adaptive_read_tiles",
                     "rt_adaptive_read_tile_error", "rt_adaptive_render_frames"]
+# every symbol include/rt_query.h declares
+QUERY_SYMBOLS = ["rt_query_closest", "rt_query_closest_buffers", "rt_query_occluded", "rt_query_occluded_buffers"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -137,6 +139,10 @@ class HipApi(abi.CApi):
         "adaptive_read_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
         "adaptive_read_tile_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
         "adaptive_render_frames": (C.c_int, [C.c_void_p, C.c_int]),
+        "query_closest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "query_closest_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "query_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "query_occluded_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -578,6 +584,31 @@ class HipTracer(abi.Tracer):
     def render_aov_centre_to_device(self, ptr, nbytes):
         """rt_render_aov_centre_to_device: the same records into device memory, enqueued like render_aov_to_device."""
         self._check(self.api.render_aov_centre_to_device(self.h, ptr, int(nbytes)))
+
+    def query_closest(self, rays):
+        """rt_query_closest (include/rt_query.h): CalculateRayCollision for each of `rays` (n records of abi.RAY_DTYPE: origin, tmax, dir,
+        reserved; the direction is used as given, not normalised) against the uploaded scene: n records of abi.RAYHIT_DTYPE (dst, normal,
+        pos, hit, object, triangle, reserved).  abi.make_rays builds the input.  Changes no state of the context."""
+        r = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), dtype=abi.RAYHIT_DTYPE)
+        self._check(self.api.query_closest(self.h, r.ctypes.data if len(r) else None, len(r), out.ctypes.data if len(r) else None))
+        return out
+
+    def query_occluded(self, rays):
+        """rt_query_occluded: per ray, 1 if it hits anything at a distance (in units of |dir|) strictly below its tmax, else 0: n uint32."""
+        r = np.ascontiguousarray(rays, dtype=abi.RAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), dtype=np.uint32)
+        self._check(self.api.query_occluded(self.h, r.ctypes.data if len(r) else None, len(r), out.ctypes.data if len(r) else None))
+        return out
+
+    def query_closest_buffers(self, rays_ptr, n, hits_ptr):
+        """rt_query_closest_buffers: the same on device memory (e.g. torch tensors' data_ptr(): n * 32 bytes of rays, n * 48 bytes of
+        records, 16-byte aligned), enqueued on the stream the context renders on; complete after synchronize()."""
+        self._check(self.api.query_closest_buffers(self.h, rays_ptr, int(n), hits_ptr))
+
+    def query_occluded_buffers(self, rays_ptr, n, occluded_ptr):
+        """rt_query_occluded_buffers: the answers (n uint32, 0 / 1) into device memory, enqueued like query_closest_buffers."""
+        self._check(self.api.query_occluded_buffers(self.h, rays_ptr, int(n), occluded_ptr))
 
     def denoise(self, params=None, use_accumulated=True, aov_frame=1):
         """rt_denoise (include/rt_denoise.h): the context's accumulated image (or its last frame) through the edge-avoiding a-trous

@@ -45,6 +45,14 @@ rt_adaptive_select — the 8 x 8 tiles whose relative standard error of the mean
 tile is active or the budget is spent.  --png / --pfm then hold the per-pixel resolve (rt_resolve: every pixel divided by its own frame
 count), and --adaptive-png FILE writes that count, white = the largest.
 
+    python tools/rt_render.py 3 --frames 1 --ao-png ao.png --ao-samples 32
+
+--ao-png FILE writes an ambient-occlusion picture made on the device with the ray queries of include/rt_query.h: the records of the
+pixel centres (rt_render_aov_centre_to_device) stay in a torch tensor, torch builds --ao-samples (default 16) cosine-weighted hemisphere
+rays per first hit (origin = the hit position pushed out along the normal, tmax = --ao-distance of the hits' extent, default 0.25),
+rt_query_occluded_buffers answers each batch into a tensor, and the picture is 1 - the mean answer (misses white).  Needs torch, which
+is then imported before the library is loaded so that both share one HIP runtime.
+
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
 icosphere:SUBDIV[:DISPLACEMENT_SEED[:RADIUS]] | a JSON mesh spec); a stand-in has to have the
@@ -88,9 +96,17 @@ def main():
     ap.add_argument("--reproject-move", metavar="DX,DY,DZ", default="0.05,0.02,0.03", help="camera offset in world units")
     ap.add_argument("--reproject-frames", type=int, default=4, help="frames rendered after the reprojection")
     ap.add_argument("--reproject-centre", action="store_true", help="steer --reproject-png by pixel-centre records (include/rt_motion.h) instead of those of --aov-frame")
+    ap.add_argument("--ao-png", metavar="FILE", help="ambient occlusion from rt_query_occluded_buffers on torch-generated hemisphere rays")
+    ap.add_argument("--ao-samples", type=int, default=16, help="hemisphere rays per first hit (default 16)")
+    ap.add_argument("--ao-distance", type=float, default=0.25, help="tmax of the rays as a fraction of the hits' extent (default 0.25)")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
+    if a.ao_png:
+        if a.ao_samples < 1 or not a.ao_distance > 0:
+            ap.error("--ao-samples must be >= 1 and --ao-distance > 0")
+        import torch  # before the library: one HIP runtime for both
+        torch.cuda.set_device(0)
     pkg = g.load_package()
 
     def mesh_spec(text):
@@ -229,6 +245,37 @@ def main():
         pkg.display.write_png(a.variance_png, pkg.display.linear_srgb8(heat.astype(np.float32)))
         print(json.dumps({"variance_png": a.variance_png, "batches": a.variance_batches, "scale": a.variance_scale, "median_sd": float(np.median(sd[known])) if known.any() else None,
                           "pixels_over_scale": int((sd > a.variance_scale).sum()), "pixels_unknown": int((~known).sum())}))
+    if a.ao_png:
+        import numpy as np
+        dev = torch.device("cuda:0")
+        aov = torch.zeros((h * w, 16), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        tr.render_aov_centre_to_device(aov.data_ptr(), aov.numel() * 4)
+        tr.synchronize()
+        hit = (aov[:, 7].view(torch.int32) & 3) != 0
+        nrm, pos = aov[hit, 1:4], aov[hit, 4:7]
+        n = int(hit.sum().item())
+        ao = torch.ones(h * w, dtype=torch.float32, device=dev)
+        if n:
+            extent = float((pos.max(dim=0).values - pos.min(dim=0).values).norm())
+            rays = torch.zeros((n, 8), dtype=torch.float32, device=dev)
+            rays[:, 0:3] = pos + nrm * (1e-4 * extent)
+            rays[:, 3] = a.ao_distance * extent
+            occ = torch.zeros(n, dtype=torch.int32, device=dev)
+            blocked = torch.zeros(n, dtype=torch.float32, device=dev)
+            gen = torch.Generator(device=dev).manual_seed(a.seed)
+            for _ in range(a.ao_samples):  # normalize(normal + unit vector): cosine-weighted about the normal
+                u = torch.nn.functional.normalize(torch.randn((n, 3), generator=gen, device=dev), dim=-1)
+                rays[:, 4:7] = torch.nn.functional.normalize(nrm + 0.999 * u, dim=-1)
+                torch.cuda.synchronize()  # torch's stream is not the context's: the rays are complete before the pass reads them
+                tr.query_occluded_buffers(rays.data_ptr(), n, occ.data_ptr())
+                tr.synchronize()
+                blocked += occ.to(torch.float32)
+            ao[hit] = 1.0 - blocked / a.ao_samples
+        grey = ao.reshape(h, w, 1).expand(h, w, 3).cpu().numpy().astype(np.float32)
+        pkg.display.write_png(a.ao_png, pkg.display.linear_srgb8(np.ascontiguousarray(grey)))
+        print(json.dumps({"ao_png": a.ao_png, "samples": a.ao_samples, "distance": a.ao_distance, "hit_pixels": n, "rays": n * a.ao_samples,
+                          "mean_ao": float(ao[hit].mean().item()) if n else None}))
     if a.reproject_png:
         import ctypes as C
         import numpy as np
