@@ -104,6 +104,23 @@ def make_rays(origins, dirs, tmax=np.inf):
     return r
 
 
+# ---- rt_radiance.h ----------------------------------------------------------
+# RtPathRay / RtRadiance: one record per ray of the rt_radiance_* calls
+PATHRAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("unused", "<f4"), ("dir", "<f4", (3,)), ("rng", "<u4")])
+RADIANCE_DTYPE = np.dtype([("rgb", "<f4", (3,)), ("rng", "<u4")])
+assert PATHRAY_DTYPE.itemsize == 32 and RADIANCE_DTYPE.itemsize == 16
+
+
+def make_path_rays(origins, dirs, rng):
+    """n records of PATHRAY_DTYPE from (n, 3) origins and directions and a scalar or per-ray generator state (uint32)."""
+    o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+    r = np.zeros(len(o), dtype=PATHRAY_DTYPE)
+    r["origin"] = o
+    r["dir"] = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+    r["rng"] = np.asarray(rng, dtype=np.uint32)
+    return r
+
+
 class RtDenoiseParams(C.Structure):
     """include/rt_denoise.h: the parameters of the a-trous filter (32 bytes; struct_size is the handshake)."""
     _fields_ = [

@@ -33,6 +33,7 @@
 #include "../../include/rt_adaptive.h"
 #include "../../include/rt_motion.h"
 #include "../../include/rt_query.h"
+#include "../../include/rt_radiance.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
@@ -40,6 +41,7 @@
 #include "rt_variance_launch.h"
 #include "rt_adaptive_launch.h"
 #include "rt_query_launch.h"
+#include "rt_radiance_launch.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -200,6 +202,14 @@ struct RtContext {
     size_t queryOutBytes = 0;
     unsigned long long* dQueryWords = nullptr;
     bool queryUnreported = false;
+    /* rt_radiance_* (include/rt_radiance.h): the same for the radiance pass — the host form's device rays and records, the pass's own
+     * counter slot (word 0: the block counter of the launch, word 7: its watchdog word), a buffer-form pass not yet reported */
+    void* dRadianceRays = nullptr;
+    size_t radianceRaysBytes = 0;
+    void* dRadianceOut = nullptr;
+    size_t radianceOutBytes = 0;
+    unsigned long long* dRadianceWords = nullptr;
+    bool radianceUnreported = false;
     /* rt_denoise (include/rt_denoise.h): the filter's two colour images and packed guide image, and the AOV records of the two context
      * calls' internal pass; kept between calls (grow on demand) */
     void* dDnScratch = nullptr;
@@ -531,6 +541,9 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dQueryRays);
     hipFree(ctx->dQueryOut);
     hipFree(ctx->dQueryWords);
+    hipFree(ctx->dRadianceRays);
+    hipFree(ctx->dRadianceOut);
+    hipFree(ctx->dRadianceWords);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
@@ -1402,6 +1415,7 @@ extern "C" {
 
 static int aov_report(RtContext* ctx, const char* call);
 static int query_report(RtContext* ctx, const char* call);
+static int radiance_report(RtContext* ctx, const char* call);
 
 static int check_renderable(RtContext* ctx)
 {
@@ -1492,7 +1506,8 @@ int rt_synchronize(RtContext* ctx)
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
     if (int rc = aov_report(ctx, "rt_synchronize")) return rc; /* a device AOV pass completes here: so does its watchdog report (no-op otherwise) */
-    return query_report(ctx, "rt_synchronize"); /* and that of a buffer-form ray query (include/rt_query.h) */
+    if (int rc = query_report(ctx, "rt_synchronize")) return rc; /* and that of a buffer-form ray query (include/rt_query.h) */
+    return radiance_report(ctx, "rt_synchronize"); /* and that of a buffer-form radiance pass (include/rt_radiance.h) */
 }
 
 int rt_get_frame(const RtContext* ctx) { return ctx ? ctx->frame : RT_ERR_INVALID_ARG; }
@@ -2317,6 +2332,124 @@ int rt_query_closest(RtContext* ctx, const RtRay* rays, int n, RtRayHit* hits) {
 int rt_query_closest_buffers(RtContext* ctx, const void* d_rays, int n, void* d_hits) { return query_to_device(ctx, "rt_query_closest_buffers", d_rays, n, d_hits, sizeof(RtRayHit), false); }
 int rt_query_occluded(RtContext* ctx, const RtRay* rays, int n, uint32_t* occluded) { return query_to_host(ctx, "rt_query_occluded", rays, n, occluded, sizeof(uint32_t), true); }
 int rt_query_occluded_buffers(RtContext* ctx, const void* d_rays, int n, void* d_occluded) { return query_to_device(ctx, "rt_query_occluded_buffers", d_rays, n, d_occluded, sizeof(uint32_t), true); }
+
+/* ---- rt_radiance_trace / rt_radiance_trace_buffers (include/rt_radiance.h): Trace for caller-made rays -------------------------------
+ * One launch of rt_radiance_kernel (rt_kernels.h) on the joined main stream, built like the query pass above: the context's in nothing
+ * but the scene, the parameters and the stream.  fill_args with the parameters present (the kernel reads maxBounce, useSky and the sun's
+ * fields besides the scene), the variant as choose_variant would choose it (FLAT / BVH / MANY) in its single-wave form, a counter slot of
+ * the pass's own (ctx->dRadianceWords: word 0 hands out the blocks, word 7 is the watchdog's), no render target, no tile order, no pixel
+ * records.  The checks and the block and grid arithmetic are rt_radiance_launch.h's. */
+static int radiance_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut)
+{
+    KArgs a;
+    fill_args(ctx, 1, 1, a);
+    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
+    void (*kern)(const KArgs, const float4*, int, float4*) =
+        many ? rtk::rt_radiance_kernel<false, true> : ctx->flatScene ? rtk::rt_radiance_kernel<true, false> : rtk::rt_radiance_kernel<false, false>;
+    /* a wave region of the trace kernel, single waves, no cache, no pool */
+    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
+    a.suspendNum = ctx->tuner.decided; /* scheduling only: a path's bits do not depend on it */
+    a.frameRender = nullptr;
+    a.accumulated = nullptr;
+    a.tileOrder = nullptr;
+    a.tileCost = nullptr;
+    a.pxCold = nullptr;
+    a.staging = nullptr;
+    if (!ctx->dRadianceWords) HIP_TRY(ctx, hipMalloc(&ctx->dRadianceWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
+    a.counters = ctx->dRadianceWords;
+    a.tileQueue = ctx->dRadianceWords; /* word 0: a launch of this pass counts no segments there */
+    a.tileQueueBase = 0;
+    long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
+    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &resident)) return rc;
+    const long long grid = rt_rd::grid(rt_rd::blocks(n), resident, ctx->gridOverride);
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->dRadianceWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (const float4*)dRays, n, (float4*)dOut);
+    HIP_TRY(ctx, hipGetLastError());
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
+static int radiance_fired(RtContext* ctx, unsigned long long* fired)
+{
+    *fired = 0;
+    HIP_TRY(ctx, hipMemcpy(fired, ctx->dRadianceWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the report of a buffer-form pass that has not been reported yet */
+static int radiance_report(RtContext* ctx, const char* call)
+{
+    if (!ctx->radianceUnreported) return RT_OK;
+    ctx->radianceUnreported = false;
+    unsigned long long fired = 0;
+    if (int rc = radiance_fired(ctx, &fired)) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the pass of an rt_radiance_trace_buffers call: "
+                           "walks were cut short, that call's records are not valid (the context's images are not affected)", call, fired);
+    return RT_OK;
+}
+
+/* what the two calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch */
+static int radiance_check(RtContext* ctx, const char* call, const void* rays, int n, const void* out, size_t* rayBytes, size_t* outBytes)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    const char* why = "";
+    if (int rc = rt_rd::check_batch(rays, n, out, rayBytes, outBytes, &why)) return fail(ctx, rc, "%s: %s", call, why);
+    if (!ctx->haveScene) return fail(ctx, RT_ERR_STATE, "%s before rt_upload_scene", call);
+    if (!ctx->haveParams) return fail(ctx, RT_ERR_STATE, "%s before rt_set_params", call);
+    return RT_OK;
+}
+
+/* a buffer-form pass still unreported: synchronise and report it before this call's own pass clears the word */
+static int radiance_settle(RtContext* ctx, const char* call)
+{
+    if (!ctx->radianceUnreported) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    return radiance_report(ctx, call);
+}
+
+int rt_radiance_trace(RtContext* ctx, const RtPathRay* rays, int n, RtRadiance* out)
+{
+    const char* const call = "rt_radiance_trace";
+    size_t rayBytes = 0, outBytes = 0;
+    int rc = radiance_check(ctx, call, rays, n, out, &rayBytes, &outBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    RT_FLUSH(ctx);
+    if ((rc = radiance_settle(ctx, call))) return rc;
+    if (n == 0) return RT_OK;
+    if ((rc = grow_scratch(ctx, &ctx->dRadianceRays, &ctx->radianceRaysBytes, rayBytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dRadianceOut, &ctx->radianceOutBytes, outBytes))) return rc;
+    hipStream_t st = joined(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dRadianceRays, rays, rayBytes, hipMemcpyHostToDevice, st));
+    if ((rc = radiance_enqueue(ctx, ctx->dRadianceRays, n, ctx->dRadianceOut))) return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    unsigned long long fired = 0;
+    if ((rc = radiance_fired(ctx, &fired))) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in this pass: walks were cut short, the records are not valid "
+                           "(the context's images are not affected)", call, fired);
+    HIP_TRY(ctx, hipMemcpy(out, ctx->dRadianceOut, outBytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_radiance_trace_buffers(RtContext* ctx, const void* d_rays, int n, void* d_out)
+{
+    const char* const call = "rt_radiance_trace_buffers";
+    size_t rayBytes = 0, outBytes = 0;
+    int rc = radiance_check(ctx, call, d_rays, n, d_out, &rayBytes, &outBytes);
+    if (rc) return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (n > 0) { /* the kernel reads and writes through these pointers */
+        if ((rc = check_device_range(ctx, call, "d_rays", d_rays, rayBytes))) return rc;
+        if ((rc = check_device_range(ctx, call, "d_out", d_out, outBytes))) return rc;
+    }
+    RT_FLUSH(ctx);
+    if ((rc = radiance_settle(ctx, call))) return rc;
+    if (n == 0) return RT_OK;
+    if ((rc = radiance_enqueue(ctx, d_rays, n, d_out))) return rc;
+    ctx->radianceUnreported = true;
+    return RT_OK;
+}
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main

@@ -1532,6 +1532,112 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     }
 }
 
+/* rt_radiance_* (include/rt_radiance.h): Trace (RC:479-542) for n caller-made rays, each with the generator state the caller gives it.
+ * trace_body without camera, pixel, frame and image: a path starts from a ray of `rays` (RtPathRay, 32 bytes, two 16-byte loads) and
+ * ends in one 16-byte store of its RtRadiance (the light and the generator's state) into `out`.  Between the two it is the frame's
+ * path: begin_intersect, traverse (suspending, as trace_body calls it, at the context's threshold a.suspendNum) or traverse_flat,
+ * and rt_shade_phase.inl — included here a third time behind locals of trace_body's names, so there is one copy of the arithmetic.  The
+ * pixel's sum that the include adds a finished path to (PXF) is a local that starts at 0 in the iteration the path ends in: 0 + light.
+ * One path per lane.  A wave owns a block of 64 consecutive rays at a time; a lane without a path takes the next unassigned ray of that
+ * block by ballot and prefix rank (trace_body's refill with "slot of an 8 x 8 tile" replaced by "index into the block"), and when the
+ * block is used up the wave takes another: block blockIdx.x first, then gridDim.x + ticket from the counter a.tileQueue, which the host
+ * zeroes for the launch (rt_radiance_launch.h).  So a wave does not idle on its longest path, and a wave of long paths draws fewer blocks.
+ * Rays at or past n are never assigned: those lanes load and store nothing and stay in the loop, idle, until the wave leaves.
+ * Single-wave workgroups without the top-of-tree cache and without the chain pool; LDS as a wave region of the trace kernel
+ * (rt_plan::wave_lds_bytes): the traversal stack, the pixel fields' rows — row 0 holds the lane's ray index, the others are unused —
+ * and the MANY variant's mask extension and bounce count.  Only a.counters + 7 (the watchdog word of traverse()) and the block counter
+ * are written besides `out`: the host points both at words of this pass's own.  n <= RT_QUERY_MAX_RAYS = 2^26: 64 x blocks fits an int. */
+template <bool FLAT, bool MANY>
+__global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_radiance_kernel(const KArgs a, const float4* __restrict__ rays, const int n, float4* __restrict__ out)
+{
+    extern __shared__ uint32_t s_lds[];
+    /* the names rt_shade_phase.inl reads that have one value here */
+    constexpr bool STATS = false, HOT = false, COST = false;
+    const RT_LDS char* const hotLds = (const RT_LDS char*)s_lds;
+    const uint32_t hotUnits = 0u;
+    uint32_t* const cost = nullptr;
+    const int lane = (int)threadIdx.x;
+    uint32_t* const stackBase = &s_lds[lane];
+    uint32_t* const pxu = &s_lds[(size_t)cold_args().stackEntries * RT_WAVE + lane];
+    uint32_t* const extBase = pxu + RT_PIXEL_FIELDS * RT_WAVE;
+    enum { PX_SAMPLE = 0, PX_TIX, PX_TIY, PX_TIZ, PX_RAY = 0 };
+#define PXU(k) pxu[(k) * RT_WAVE]
+#define PXF(k) pxacc[(k)]
+#define RT_COST_SLOT(c) (reinterpret_cast<uint4*>(cost)) /* (COST is false: never evaluated) */
+
+    const int blocks = (n + RT_WAVE - 1) / RT_WAVE;
+    int poolBase = (int)blockIdx.x * RT_WAVE; /* first ray of the wave's block */
+    int poolPos = (int)blockIdx.x < blocks ? 0 : 64; /* next unassigned ray of the block, 64 = used up */
+    bool queueEmpty = false;
+
+    uint32_t rng = 0;
+    bool pathActive = false; /* the lane holds a path */
+    bool inTrav = false;     /* suspended inside traverse() */
+    int bounce = 0;
+    rt_f3 rpos = rt_v3s(0.0f), rdir = rt_v3s(0.0f), transmittance = rt_v3s(0.0f), pathLight = rt_v3s(0.0f);
+    SceneHit h;
+    Trav t;
+    h.dst = RT_INF; h.obj = -1; h.tri = -1; h.u = h.v = h.det = 0.0f; h.backface = false;
+    t.cand = 0; t.rootStep = false; t.m = 0; t.cur = RT_CODE_NEXT_MODEL; t.sp = 0; t.lpos = t.ldir = t.linv = rt_v3s(0.0f); t.triBase = 0; t.cull = true;
+    Stats st = {};
+
+    for (;;) {
+        /* ---- hand rays to idle lanes (every lane of the wave is active here) */
+        unsigned long long idle = __ballot(!pathActive);
+        while (idle) {
+            const RT_CAS KArgs& c = cold_args();
+            if (poolPos >= 64) {
+                if (queueEmpty) break;
+                int next = 0;
+                if (lane == 0) next = (int)atomicAdd(c.tileQueue, 1ull);
+                next = __builtin_amdgcn_readfirstlane(next) + (int)gridDim.x;
+                if (next >= blocks) { queueEmpty = true; break; }
+                poolBase = next * RT_WAVE;
+                poolPos = 0;
+            }
+            const int rank = __popcll(idle & ((1ull << lane) - 1ull));
+            const int avail = 64 - poolPos;
+            if (!pathActive && rank < avail) {
+                const int i = poolBase + poolPos + rank;
+                if (i < n) { /* inside the n * 32 and n * 16 bytes the host checked */
+                    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+                    if (c.maxBounce >= 0) { /* RC:485: the loop runs for i = 0 */
+                        rpos = rt_v3(r0.x, r0.y, r0.z);
+                        rdir = rt_v3(r1.x, r1.y, r1.z);
+                        rng = __float_as_uint(r1.w);
+                        transmittance = rt_v3s(1.0f);
+                        pathLight = rt_v3s(0.0f);
+                        if (MANY) extBase[(1 + a.extWords) * RT_WAVE] = 0u; /* (trace_body: this variant keeps the bounce count in LDS) */
+                        else bounce = 0;
+                        PXU(PX_RAY) = (uint32_t)i;
+                        inTrav = false;
+                        pathActive = true;
+                    } else {
+                        out[i] = make_float4(0.0f, 0.0f, 0.0f, r1.w); /* Trace returned 0 without a draw */
+                    }
+                }
+            }
+            const int wanted = __popcll(idle);
+            poolPos += wanted < avail ? wanted : avail;
+            idle = __ballot(!pathActive);
+        }
+        if (idle == ~0ull) break; /* no lane holds a path and there is no ray left */
+        if (pathActive) {
+            if (!inTrav) {
+                begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
+                inTrav = true;
+                if (FLAT) traverse_flat<STATS>(a, rpos, rdir, h, st);
+            }
+            float pxacc[4] = {0.0f, 0.0f, 0.0f, 0.0f}; /* RC:578's sum for this one path */
+#include "rt_shade_phase.inl"
+            if (!pathActive) out[PXU(PX_RAY)] = make_float4(pxacc[PX_TIX], pxacc[PX_TIY], pxacc[PX_TIZ], __uint_as_float(rng));
+        }
+    }
+#undef RT_COST_SLOT
+#undef PXU
+#undef PXF
+}
+
 /* ---- test hooks (rt_debug_*): the same device functions, one ray / value per lane */
 __global__ void __launch_bounds__(RT_WAVE) rt_debug_intersect_kernel(const KArgs a, const float* origins, const float* dirs, int n, float* out)
 {

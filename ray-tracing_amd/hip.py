@@ -50,6 +50,8 @@ ADAPTIVE_SYMBOLS = ["rt_adaptive_default_params", "rt_adaptive_select_buffers", 
                     "rt_adaptive_read_tile_error", "rt_adaptive_render_frames"]
 # every symbol include/rt_query.h declares
 QUERY_SYMBOLS = ["rt_query_closest", "rt_query_closest_buffers", "rt_query_occluded", "rt_query_occluded_buffers"]
+# every symbol include/rt_radiance.h declares
+RADIANCE_SYMBOLS = ["rt_radiance_trace", "rt_radiance_trace_buffers"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -143,6 +145,8 @@ class HipApi(abi.CApi):
         "query_closest_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "query_occluded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "query_occluded_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "radiance_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "radiance_trace_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -609,6 +613,21 @@ class HipTracer(abi.Tracer):
     def query_occluded_buffers(self, rays_ptr, n, occluded_ptr):
         """rt_query_occluded_buffers: the answers (n uint32, 0 / 1) into device memory, enqueued like query_closest_buffers."""
         self._check(self.api.query_occluded_buffers(self.h, rays_ptr, int(n), occluded_ptr))
+
+    def radiance_trace(self, rays):
+        """rt_radiance_trace (include/rt_radiance.h): the reference's Trace for each of `rays` (n records of abi.PATHRAY_DTYPE: origin,
+        unused, dir, rng; the direction is used as given, rng is the generator state the path starts with) against the uploaded scene
+        under the parameters last set: n records of abi.RADIANCE_DTYPE (rgb, and rng = the state when Trace returned, to chain further
+        samples).  abi.make_path_rays builds the input.  Changes no state of the context."""
+        r = np.ascontiguousarray(rays, dtype=abi.PATHRAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), dtype=abi.RADIANCE_DTYPE)
+        self._check(self.api.radiance_trace(self.h, r.ctypes.data if len(r) else None, len(r), out.ctypes.data if len(r) else None))
+        return out
+
+    def radiance_trace_buffers(self, rays_ptr, n, out_ptr):
+        """rt_radiance_trace_buffers: the same on device memory (e.g. torch tensors' data_ptr(): n * 32 bytes of rays, n * 16 bytes of
+        records, 16-byte aligned), enqueued on the stream the context renders on; complete after synchronize()."""
+        self._check(self.api.radiance_trace_buffers(self.h, rays_ptr, int(n), out_ptr))
 
     def denoise(self, params=None, use_accumulated=True, aov_frame=1):
         """rt_denoise (include/rt_denoise.h): the context's accumulated image (or its last frame) through the edge-avoiding a-trous

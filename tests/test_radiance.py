@@ -1,0 +1,105 @@
+"""include/rt_radiance.h without a GPU: the header is plain C (C99 and C++17), RtPathRay is 32 and RtRadiance 16 bytes, RtPathRay's
+origin, dir and rng sit where RtRay's origin, dir and reserved do, and the numpy dtypes of abi.py match the header field by field;
+hip.RADIANCE_SYMBOLS is the header's list, disjoint from every other list, and the library exports exactly it; each call refuses a null
+context; and ray-tracing_amd/csrc/rt_radiance_launch.h — the HIP-free half of the entry points — passes its stand-alone driver
+(tests/radiance_launch_driver.cpp) built with the address and undefined-behaviour sanitizers."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INCLUDE = os.path.join(ROOT, "include")
+RAY_OFFSETS = {"origin": (0, 12), "unused": (12, 4), "dir": (16, 12), "rng": (28, 4)}
+OUT_OFFSETS = {"rgb": (0, 12), "rng": (12, 4)}
+SHARED = {"origin": "origin", "dir": "dir", "rng": "reserved"}  # RtPathRay field -> the RtRay field whose place it takes
+FUNCTIONS = ["rt_radiance_trace", "rt_radiance_trace_buffers"]
+
+
+def header_functions():
+    text = open(os.path.join(INCLUDE, "rt_radiance.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    return sorted(set(re.findall(r"\b(rt_[a-z_0-9]+)\s*\(", text)))
+
+
+@pytest.mark.parametrize("lang", ["c99", "c++17"])
+def test_header_compiles_and_has_the_documented_layout(lang, tmp_path):
+    cxx = lang.startswith("c++")
+    src = tmp_path / ("radiance.cpp" if cxx else "radiance.c")
+    checks = "\n".join(f"typedef char ray_at_{f}[offsetof(RtPathRay, {f}) == {o} && sizeof(((RtPathRay*)0)->{f}) == {s} ? 1 : -1];" for f, (o, s) in RAY_OFFSETS.items())
+    checks += "\n" + "\n".join(f"typedef char out_at_{f}[offsetof(RtRadiance, {f}) == {o} && sizeof(((RtRadiance*)0)->{f}) == {s} ? 1 : -1];"
+                               for f, (o, s) in OUT_OFFSETS.items())
+    checks += "\n" + "\n".join(f"typedef char same_place_{a}[offsetof(RtPathRay, {a}) == offsetof(RtRay, {b}) && sizeof(((RtPathRay*)0)->{a}) == sizeof(((RtRay*)0)->{b}) ? 1 : -1];"
+                               for a, b in SHARED.items())
+    src.write_text('#include <stddef.h>\n#include "rt_radiance.h"\ntypedef char ray_is_32[sizeof(RtPathRay) == 32 ? 1 : -1];\n'
+                   "typedef char out_is_16[sizeof(RtRadiance) == 16 ? 1 : -1];\ntypedef char as_large_as_a_ray[sizeof(RtPathRay) == sizeof(RtRay) ? 1 : -1];\n"
+                   "typedef char max_is_2_26[RT_QUERY_MAX_RAYS == 67108864 ? 1 : -1];\n" + checks +
+                   "\nint use(RtContext* c, RtPathRay* r, RtRadiance* o) { return rt_radiance_trace(c, r, 1, o) + rt_radiance_trace_buffers(c, r, 1, o); }\n")
+    cmd = ["g++", "-x", "c++"] if cxx else ["gcc", "-x", "c"]
+    subprocess.check_call(cmd + [f"-std={lang}", "-pedantic", "-Wall", "-Wextra", "-Werror", "-fsyntax-only", "-I", INCLUDE, str(src)])
+
+
+def test_numpy_dtypes_match_the_header_field_by_field(pkg):
+    abi = pkg.abi
+    for dtype, offsets, size in ((abi.PATHRAY_DTYPE, RAY_OFFSETS, 32), (abi.RADIANCE_DTYPE, OUT_OFFSETS, 16)):
+        assert dtype.itemsize == size and dtype.names == tuple(offsets)
+        for f, (off, nbytes) in offsets.items():
+            assert dtype.fields[f][1] == off and dtype.fields[f][0].itemsize == nbytes, f
+    for a, b in SHARED.items():
+        assert abi.PATHRAY_DTYPE.fields[a][1] == abi.RAY_DTYPE.fields[b][1]
+    # the field types, as the header's declarations state them
+    text = open(os.path.join(INCLUDE, "rt_radiance.h")).read()
+    kinds = {"float": "f", "uint32_t": "u", "int32_t": "i"}
+    for struct, dtype in (("RtPathRay", abi.PATHRAY_DTYPE), ("RtRadiance", abi.RADIANCE_DTYPE)):
+        body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (struct, struct), text, flags=re.S).group(1)
+        body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+        decl = re.findall(r"(float|uint32_t|int32_t)\s+([a-z]+)(?:\[(\d+)\])?;", body)
+        assert [d[1] for d in decl] == list(dtype.names), struct
+        for ctype, name, count in decl:
+            sub = dtype.fields[name][0]
+            assert sub.base.kind == kinds[ctype] and sub.base.itemsize == 4 and sub.shape == ((int(count),) if count else ()), (struct, name)
+    r = abi.make_path_rays([[1, 2, 3], [4, 5, 6]], [[0, 0, 1], [0, 1, 0]], [7, 0xfffffffe])
+    want = np.array([1, 2, 3, 0, 0, 0, 1, 0, 4, 5, 6, 0, 0, 1, 0, 0], dtype=np.float32).view(np.uint32)
+    want[7], want[15] = 7, 0xfffffffe
+    assert r.dtype == abi.PATHRAY_DTYPE and r.tobytes() == want.tobytes()
+    assert abi.make_path_rays(np.zeros((3, 3)), np.ones((3, 3)), 5)["rng"].tolist() == [5, 5, 5]
+
+
+def test_header_symbols_are_exported_and_listed(pkg, api):
+    names = header_functions()
+    assert names == FUNCTIONS
+    assert sorted(pkg.hip.RADIANCE_SYMBOLS) == names, "hip.RADIANCE_SYMBOLS is out of sync with include/rt_radiance.h"
+    for other in (pkg.hip.ABI_SYMBOLS, pkg.hip.COST_SYMBOLS, pkg.hip.AOV_SYMBOLS, pkg.hip.DENOISE_SYMBOLS, pkg.hip.REPROJECT_SYMBOLS, pkg.hip.MOTION_SYMBOLS,
+                  pkg.hip.VARIANCE_SYMBOLS, pkg.hip.ADAPTIVE_SYMBOLS, pkg.hip.QUERY_SYMBOLS):
+        assert not set(names) & set(other)
+    for n in names:
+        assert hasattr(api.lib, n), f"libraytrace_hip.so does not export {n}"
+    exported = subprocess.run(["nm", "-D", "--defined-only", api.lib._name], capture_output=True, text=True, check=True).stdout
+    mine = sorted(set(re.findall(r"\b(rt_radiance_[a-z_0-9]*)\b", exported)))
+    assert mine == names, "the library exports a radiance call the header does not declare"
+
+
+def test_every_call_refuses_a_null_context(pkg, api):
+    rays = pkg.abi.make_path_rays([[0, 0, 0]], [[0, 0, 1]], 1)
+    out = np.zeros(1, dtype=pkg.abi.RADIANCE_DTYPE)
+    for call in (api.radiance_trace, api.radiance_trace_buffers):
+        assert call(None, rays.ctypes.data, 1, out.ctypes.data) == pkg.abi.RT_ERR_INVALID_ARG
+        assert b"null context" in api.last_error(None)
+        assert call(None, None, 0, None) == pkg.abi.RT_ERR_INVALID_ARG
+
+
+def test_launch_header_driver_is_clean_under_address_and_undefined_sanitizers(tmp_path):
+    """Blocks and grid at n = 0, 1, 63, 64, 65, 2^26; the hand-out of blocks (first block by wave, the rest by ticket) in three drawing
+    orders; the byte-size overflow guard; the overlap predicate; the shared argument checks at this pass's record size.  A program of
+    its own: nothing of it is loaded into this process."""
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    exe = str(tmp_path / "radiance_launch_driver")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           os.path.join(ROOT, "tests", "radiance_launch_driver.cpp"), "-o", exe])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and p.stdout.strip() == "RADIANCE_LAUNCH_OK", (p.returncode, p.stdout, p.stderr)

@@ -53,6 +53,14 @@ rays per first hit (origin = the hit position pushed out along the normal, tmax 
 rt_query_occluded_buffers answers each batch into a tensor, and the picture is 1 - the mean answer (misses white).  Needs torch, which
 is then imported before the library is loaded so that both share one HIP runtime.
 
+    python tools/rt_render.py 3 --frames 1 --panorama-png pano.png --panorama-samples 64
+
+--panorama-png FILE writes an equirectangular 360 x 180 degree view from the camera position, made with the path tracer of
+include/rt_radiance.h on rays the camera of the library does not have: torch builds one ray per texel of a --panorama-size image
+(default 1024x512; longitude along x, latitude along y, jittered inside the texel) with a generator state per texel,
+rt_radiance_trace_buffers traces them into a tensor, and each of the --panorama-samples samples (default 16) starts from the state the
+previous one returned (the chain of RtRadiance.rng).  The picture is the mean.  Needs torch, imported before the library.
+
 A Unity scene file is converted by ray_tracing_amd/unityscene.py; meshes that only exist inside the
 engine or are missing on disk need `--stand-in NAME=SPEC` (SPEC: cube | quad | rounded_cube |
 icosphere:SUBDIV[:DISPLACEMENT_SEED[:RADIUS]] | a JSON mesh spec); a stand-in has to have the
@@ -99,9 +107,21 @@ def main():
     ap.add_argument("--ao-png", metavar="FILE", help="ambient occlusion from rt_query_occluded_buffers on torch-generated hemisphere rays")
     ap.add_argument("--ao-samples", type=int, default=16, help="hemisphere rays per first hit (default 16)")
     ap.add_argument("--ao-distance", type=float, default=0.25, help="tmax of the rays as a fraction of the hits' extent (default 0.25)")
+    ap.add_argument("--panorama-png", metavar="FILE", help="equirectangular 360 x 180 view from the camera position through rt_radiance_trace_buffers")
+    ap.add_argument("--panorama-samples", type=int, default=16, help="paths per texel, chained through the returned generator state (default 16)")
+    ap.add_argument("--panorama-size", default="1024x512", help="WxH of the panorama (default 1024x512)")
     a = ap.parse_args()
     if a.cost_png and a.cost_scale is None:
         ap.error("--cost-png needs --cost-scale")
+    if a.panorama_png:
+        try:
+            pano_w, pano_h = (int(v) for v in a.panorama_size.lower().split("x"))
+        except ValueError:
+            ap.error("--panorama-size is WxH")
+        if a.panorama_samples < 1 or pano_w < 1 or pano_h < 1 or pano_w * pano_h > 1 << 26:
+            ap.error("--panorama-samples must be >= 1 and --panorama-size at most 2^26 texels")
+        import torch  # before the library: one HIP runtime for both
+        torch.cuda.set_device(0)
     if a.ao_png:
         if a.ao_samples < 1 or not a.ao_distance > 0:
             ap.error("--ao-samples must be >= 1 and --ao-distance > 0")
@@ -276,6 +296,37 @@ def main():
         pkg.display.write_png(a.ao_png, pkg.display.linear_srgb8(np.ascontiguousarray(grey)))
         print(json.dumps({"ao_png": a.ao_png, "samples": a.ao_samples, "distance": a.ao_distance, "hit_pixels": n, "rays": n * a.ao_samples,
                           "mean_ao": float(ao[hit].mean().item()) if n else None}))
+    if a.panorama_png:
+        import math
+        import numpy as np
+        dev = torch.device("cuda:0")
+        n = pano_w * pano_h
+        origin = torch.tensor(list(mgr.params().camLocalToWorld)[12:15], dtype=torch.float32, device=dev)  # the camera position
+        ys, xs = torch.meshgrid(torch.arange(pano_h, device=dev), torch.arange(pano_w, device=dev), indexing="ij")
+        rays = torch.zeros((n, 8), dtype=torch.float32, device=dev)  # RtPathRay: origin, unused, dir, rng
+        rays[:, 0:3] = origin
+        idx = torch.arange(n, dtype=torch.int64, device=dev)
+        state = ((idx + 1) * 747796405 + a.seed * 2891336453) & 0xffffffff  # one generator state per texel; later samples chain the returned one
+        rays.view(torch.int32)[:, 7] = torch.where(state >= 1 << 31, state - (1 << 32), state).to(torch.int32)
+        out = torch.zeros((n, 4), dtype=torch.float32, device=dev)  # RtRadiance: rgb, rng
+        total = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(a.seed)
+        for _ in range(a.panorama_samples):
+            jit = torch.rand((2, pano_h, pano_w), generator=gen, device=dev)
+            lon = ((xs + jit[0]) / pano_w * 2.0 - 1.0) * math.pi  # -pi .. pi, 0 = +z
+            lat = (0.5 - (ys + jit[1]) / pano_h) * math.pi        # +pi/2 (up) at the top row
+            rays[:, 4] = (torch.cos(lat) * torch.sin(lon)).reshape(n)
+            rays[:, 5] = torch.sin(lat).reshape(n)
+            rays[:, 6] = (torch.cos(lat) * torch.cos(lon)).reshape(n)
+            torch.cuda.synchronize()  # torch's stream is not the context's: the rays are complete before the pass reads them
+            tr.radiance_trace_buffers(rays.data_ptr(), n, out.data_ptr())
+            tr.synchronize()
+            total += out[:, 0:3]
+            rays.view(torch.int32)[:, 7] = out.view(torch.int32)[:, 3]  # the next sample goes on where this path's generator stopped
+        img = (total / a.panorama_samples).reshape(pano_h, pano_w, 3).flip(0).cpu().numpy().astype(np.float32)  # rows bottom-up, as the frames
+        pkg.display.write_png(a.panorama_png, pkg.display.linear_srgb8(np.ascontiguousarray(img)))
+        print(json.dumps({"panorama_png": a.panorama_png, "size": [pano_w, pano_h], "samples": a.panorama_samples, "rays": n * a.panorama_samples,
+                          "mean_rgb": [float(v) for v in img.reshape(-1, 3).mean(axis=0)]}))
     if a.reproject_png:
         import ctypes as C
         import numpy as np
