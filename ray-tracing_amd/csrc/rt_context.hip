@@ -26,6 +26,7 @@
 
 #include "rt_kernels.h"
 #include "../../include/rt_cost.h"
+#include "../../include/rt_primary.h"
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
 #include "../../include/rt_reproject.h"
@@ -46,6 +47,7 @@
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
 #include "rt_scene_prep.h"
+#include "rt_primary.h"
 #define RT_VERSION_STRING "raytrace_hip gfx950 abi=1"
 
 static thread_local char g_err[512] = "";
@@ -121,6 +123,9 @@ struct RtContext {
     std::vector<RtModel> hModels;
     std::vector<uint32_t> hRootCodes;
     std::vector<int32_t> hTriBase; /* per model: first unit of its triangles in the triangle space */
+    PrimaryTris primaryTris;       /* FLAT scenes within rt_primary.h's caps: the root leaves' triangles, for the per-launch table of origin constants */
+    bool primaryOn = true;         /* RT_PRIMARY=0: the table stays off (A/B runs, tests) */
+    int lastPrimaryOn = -1;        /* the table's flag in the most recent trace launch's arguments (rt_debug_primary_table); -1 = none yet */
 
     /* uniforms */
     RtParams params;
@@ -488,6 +493,7 @@ int rt_create(int device_id, RtContext** out)
     memset(&ctx->params, 0, sizeof(ctx->params));
     if (const char* g = getenv("RT_GRID")) ctx->gridOverride = atoi(g); /* tuning hook */
     if (const char* g = getenv("RT_POOL_MIN_ITEMS")) ctx->poolMinItems = atoi(g);
+    if (const char* g = getenv("RT_PRIMARY")) ctx->primaryOn = atoi(g) != 0;
     if (const char* g = getenv("RT_POOL_FAULT")) { if (atoi(g)) ctx->poolSpinLimit = 64u | 0x80000000u; }
     if (getenv("RT_VERBOSE")) ctx->verbose = true;
     if (const char* f = getenv("RT_FUSE_FRAMES")) ctx->fuseFrames = atoi(f) != 0;
@@ -763,6 +769,10 @@ static int commit_scene(RtContext* ctx, const PreparedScene& ps, const RtContext
     ctx->nTris = ps.nTris;
     ctx->nPairs = (int)ps.nPairs;
     ctx->hTriBase = ps.lay.triBase;
+    {
+        const auto& triSpace = ps.lay.arena ? ps.lay.pairBuf : ps.lay.triBuf;
+        primary_collect_tris(ps.flat, ps.dmodels.data(), (int)ps.dmodels.size(), triSpace.data(), triSpace.size(), ps.lay.bigLeaves.data(), ps.lay.bigLeaves.size(), ctx->primaryTris);
+    }
     ctx->stackEntries = ps.flat ? 0 : ps.maxHeight; /* (the FLAT variant pushes nothing: its LDS is pixel bookkeeping only) */
     ctx->flatScene = ps.flat;
     ctx->hotUnits = ps.flat ? 0u : ps.lay.hotUnits;
@@ -896,10 +906,12 @@ int rt_update_models(RtContext* ctx, const RtModel* models, int n_models)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     /* stream-ordered: lands after the frames already enqueued, before the next launch */
     int rc;
-    if ((rc = stage_upload(ctx, ctx->dModels, dmodels.data(), sizeof(DModel) * n_models))) return rc;
-    if ((rc = stage_upload(ctx, ctx->dMaterials + ctx->nSpheres, mats.data(), sizeof(DMaterial) * n_models))) return rc;
+    /* (a failure from here on may leave device memory ahead of the host mirrors the table of origin constants is built from:
+     * the table then stays off until the next rt_upload_scene — rt_primary.h) */
+    if ((rc = stage_upload(ctx, ctx->dModels, dmodels.data(), sizeof(DModel) * n_models))) { ctx->primaryTris.usable = false; return rc; }
+    if ((rc = stage_upload(ctx, ctx->dMaterials + ctx->nSpheres, mats.data(), sizeof(DMaterial) * n_models))) { ctx->primaryTris.usable = false; return rc; }
     if (matricesChanged) { /* the world-space root filter boxes depend on the matrices only */
-        if ((rc = refresh_filters(ctx, models, ctx->hSpheres))) return rc;
+        if ((rc = refresh_filters(ctx, models, ctx->hSpheres))) { ctx->primaryTris.usable = false; return rc; }
     }
     ctx->hModels.assign(models, models + n_models);
     return RT_OK;
@@ -917,13 +929,17 @@ int rt_update_spheres(RtContext* ctx, const RtSphere* spheres, int n_spheres)
     }
     RT_FLUSH(ctx);
     std::vector<float> sph;
-    pack_spheres(spheres, n_spheres, sph, &ctx->sphereBound);
+    float bound = 0.0f;
+    pack_spheres(spheres, n_spheres, sph, &bound);
     std::vector<DMaterial> mats(n_spheres);
     for (int i = 0; i < n_spheres; i++) pack_material(spheres[i].material, mats[i]);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     int rc;
-    if ((rc = stage_upload(ctx, ctx->dSpheres, sph.data(), sph.size() * 4))) return rc;
-    if ((rc = stage_upload(ctx, ctx->dMaterials, mats.data(), sizeof(DMaterial) * n_spheres))) return rc;
+    /* (the bound and the mirror change together with the device records; a failure after the first upload leaves the table of origin
+     * constants off until the next rt_upload_scene, as in rt_update_models) */
+    if ((rc = stage_upload(ctx, ctx->dSpheres, sph.data(), sph.size() * 4))) { ctx->primaryTris.usable = false; return rc; }
+    ctx->sphereBound = bound;
+    if ((rc = stage_upload(ctx, ctx->dMaterials, mats.data(), sizeof(DMaterial) * n_spheres))) { ctx->primaryTris.usable = false; return rc; }
     ctx->hSpheres.assign(spheres, spheres + n_spheres);
     if (ctx->nModels) { /* the filter margins scale with the scene extent, which includes the spheres */
         if ((rc = refresh_filters(ctx, ctx->hModels.data(), ctx->hSpheres))) return rc;
@@ -968,7 +984,9 @@ int rt_reset_accumulation(RtContext* ctx)
     return RT_OK;
 }
 
-static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
+/* withTable: the launch is one of the trace kernels' (launch_frames, adaptive_launch) — the only readers of the table of per-launch
+ * origin constants (rt_primary.h); every other launch carries it switched off and pays nothing for it */
+static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool withTable = false)
 {
     memset(&a, 0, sizeof(a));
     a.spheres = ctx->dSpheres;
@@ -1025,9 +1043,23 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a)
          * here with the kernel's own rt_mul_point — is a negative zero */
         bool fin = true;
         for (int k = 0; k < 16; k++) fin = fin && std::isfinite(a.cam[k]);
-        const rt_f3 o = rt_mul_point(a.cam, rt_v3(0.0f, 0.0f, 0.0f), 1.0f);
+        const rt_f3 o = primary_cam_origin(a.cam);
         const bool noNegZero = rt_f2u(o.x) != 0x80000000u && rt_f2u(o.y) != 0x80000000u && rt_f2u(o.z) != 0x80000000u;
         a.raygenNoDefocus = (a.defocus == 0.0f && fin && noNegZero && std::isfinite(a.rcpW)) ? 1 : 0;
+        /* the same value is the FLAT kernels' camera-ray origin (raygen) and the origin of the table of per-launch constants
+         * (rt_primary.h), rebuilt here for every launch from the host mirrors of what the stream holds at that launch: the
+         * update calls flush the frames held back before they change a mirror */
+        const bool allowed = withTable && ctx->haveScene &&
+                             primary_allowed(ctx->primaryOn, a.raygenNoDefocus != 0, ctx->flatScene, ctx->nSpheres, ctx->nModels, ctx->primaryTris);
+        std::vector<float> sph;
+        DModel dm[RT_PRIMARY_MAX_MODELS];
+        if (allowed) {
+            float bound; /* (== ctx->sphereBound: the same function over the same mirror) */
+            pack_spheres(ctx->hSpheres.data(), ctx->nSpheres, sph, &bound);
+            for (int i = 0; i < ctx->nModels; i++) pack_model(ctx->hModels[i], ctx->hRootCodes[i], ctx->hTriBase[i], dm[i]);
+        }
+        primary_fill(a.primary, allowed, o, sph.data(), ctx->nSpheres, ctx->sphereBound, dm, ctx->nModels, ctx->primaryTris);
+        if (withTable) ctx->lastPrimaryOn = a.primary.on;
     }
     a.counters = ctx->dCounters;
     a.travLimit = ctx->travLimit;
@@ -1362,7 +1394,7 @@ int HipOrder::accumulate(int s)
 static int launch_frames(RtContext* ctx, int frame0, int nFrames)
 {
     KArgs a;
-    fill_args(ctx, frame0, nFrames, a);
+    fill_args(ctx, frame0, nFrames, a, true);
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
     LaunchPlan plan;
@@ -1689,6 +1721,7 @@ struct DevScratch {
 };
 
 int rt_debug_fused_frames_cap(const RtContext* ctx) { return ctx ? ctx->fuseCap : RT_ERR_INVALID_ARG; }
+int rt_debug_primary_table(const RtContext* ctx) { return ctx ? ctx->lastPrimaryOn : RT_ERR_INVALID_ARG; }
 
 int rt_debug_intersect(RtContext* ctx, const float* origins, const float* dirs, int n, float* out10)
 {
@@ -1999,7 +2032,7 @@ static int adaptive_launch(RtContext* ctx, int frame0, int nFrames, bool* unstag
 {
     *unstaged = false;
     KArgs a;
-    fill_args(ctx, frame0, nFrames, a);
+    fill_args(ctx, frame0, nFrames, a, true);
     LaunchPlan plan;
     int rc = choose_variant(ctx, a, plan);
     if (rc) return rc;

@@ -29,6 +29,7 @@
 #define RT_DEVICE_H
 
 #include "rt_records.h"
+#include "rt_primary.h"
 
 struct KArgs {
     /* scene */
@@ -100,6 +101,8 @@ struct KArgs {
                                   * hotUnits then = the pool region's size in 16-byte units (the wave regions start behind it) */
     int32_t frameGroupShift;     /* floor(log2(frameGroup)): the tile cost's per-frame figure without a division */
     uint32_t poolSpinLimit;      /* polls of a cell's sequence word before the chain pool's watchdog gives up (65,536); top bit: the RT_POOL_FAULT test hook */
+    /* (behind everything else, for the same reason; read through cold_args() where it is used) */
+    PrimaryTable primary;        /* the FLAT variant's per-launch ray-origin constants (rt_primary.h); primary.on = 0: not in use */
 };
 
 #endif

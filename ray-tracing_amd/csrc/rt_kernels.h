@@ -194,8 +194,11 @@ __device__ __forceinline__ rt_f3 material_colour(const DMaterial& mat, rt_f3 pos
 
 /* RayTriangle — RC:188-215 on a pre-differenced triangle. Updates the closest
  * hit with the reference's strict '<' (RC:256). */
+/* PRIMARY (rt_primary.h): every active lane's ray starts at the launch's camera origin, so pos - A and its dot with the face normal are
+ * the wave-uniform record `pr` the host computed with these very operations; `pos` is then not read.  The default is the per-ray form. */
+template <bool PRIMARY = false>
 __device__ __forceinline__ void tri_test(const DTri* __restrict__ tris, int triUnit, rt_f3 pos, rt_f3 dir, bool cull,
-                                         float& bestDst, int& bestTri, float& bu, float& bv, float& bdet)
+                                         float& bestDst, int& bestTri, float& bu, float& bv, float& bdet, const RT_CAS float* pr = nullptr)
 {
     /* A triangle is named by the 16-byte UNIT its record starts at (rt_device.h: three units per record, the host's layout
      * decides where the runs of a leaf lie): a 32-bit byte offset from the uniform array base (SGPR base + VGPR offset
@@ -206,11 +209,11 @@ __device__ __forceinline__ void tri_test(const DTri* __restrict__ tris, int triU
     rt_f3 edgeAB = rt_v3(q0.w, q1.x, q1.y);
     rt_f3 edgeAC = rt_v3(q1.z, q1.w, q2.x);
     rt_f3 face = rt_v3(q2.y, q2.z, q2.w);
-    rt_f3 vertRayOffset = pos - A;
+    rt_f3 vertRayOffset = PRIMARY ? rt_v3(pr[0], pr[1], pr[2]) : pos - A;
     rt_f3 rayOffsetPerp = rt_cross(vertRayOffset, dir);
     float determinant = -rt_dot(dir, face);
     float invDet = rt_rcp(determinant);
-    float dst = rt_dot(vertRayOffset, face) * invDet;
+    float dst = (PRIMARY ? pr[3] : rt_dot(vertRayOffset, face)) * invDet;
     float u = rt_dot(edgeAC, rayOffsetPerp) * invDet;
     float v = -rt_dot(edgeAB, rayOffsetPerp) * invDet;
     float w = 1 - u - v;
@@ -245,8 +248,13 @@ struct Trav {
 /* ANY (include/rt_query.h, occlusion): a lane whose ray has an accepted hit with dst < tmax needs no more of the walk — the closest-hit
  * walk accepts that hit too and only lowers dst afterwards — so it tests no further sphere here and leaves parked in RT_CODE_DONE.  The
  * default (false) is the closest-hit walk every other caller gets: tmax is then not read. */
-template <bool STATS, bool FLAT, bool MANY, bool ANY = false>
-__device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f)
+/* PRIMARY (rt_primary.h; the FLAT trace kernel only): every active lane of the wave holds a fresh camera ray of a launch without defocus,
+ * so rpos is the launch's camOrigin in all of them and the terms below that depend on rpos and the scene alone — oo, c.o and ct of the
+ * pre-test, off and qc of the exact test — come from the table `pt` the host filled with the same fp32 operations: same bits, computed
+ * once per launch instead of once per lane.  The table holds at most one block of 32 spheres. */
+template <bool STATS, bool FLAT, bool MANY, bool ANY = false, bool PRIMARY = false>
+__device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f,
+                                                const RT_CAS PrimaryTable* pt = nullptr)
 {
     h.dst = RT_INF;
     h.obj = -1;
@@ -275,8 +283,8 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
     const RT_CAS float* sphq = (const RT_CAS float*)a.sphereQuick;
     const float qa = rt_dot(rdir, rdir);
     const float od = __builtin_fmaf(rpos.x, rdir.x, __builtin_fmaf(rpos.y, rdir.y, rpos.z * rdir.z));
-    const float oo = __builtin_fmaf(rpos.x, rpos.x, __builtin_fmaf(rpos.y, rpos.y, rpos.z * rpos.z));
-    const float negMargin = -(7.62939453125e-06f * qa * (oo + a.sphereBound)); /* 2^-17 */
+    const float oo = PRIMARY ? 0.0f : __builtin_fmaf(rpos.x, rpos.x, __builtin_fmaf(rpos.y, rpos.y, rpos.z * rpos.z));
+    const float negMargin = -(7.62939453125e-06f * qa * (PRIMARY ? pt->ooBound : oo + a.sphereBound)); /* 2^-17 */
     /* Two spheres per step, side by side in packed fp32 instructions: the sphere data sits in SGPRs, and on gfx950 a VALU
      * instruction with an SGPR source issues at the slow rate (4.5 cycles against 2.9, profiles/r03_valu_op_rates.txt) while
      * v_pk_fma/mul/add_f32 take an SGPR pair at no extra cost (5.0 cycles for both halves) — the same operations on the same
@@ -289,12 +297,15 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
         const int n = (a.nSpheres - base) < 32 ? (a.nSpheres - base) : 32;
         uint32_t cand = 0;
         for (int k = 0; k < n; k += 2) {
-            const RT_CAS float* q = sphq + 4 * (base + k); /* pair record (base + k) / 2, eight floats each */
-            const rt_f2v cx = {q[0], q[1]}, cy = {q[2], q[3]}, cz = {q[4], q[5]}, kk = {q[6], q[7]};
+            const RT_CAS float* q = PRIMARY ? &pt->pair[0][0] + 4 * (base + k) : sphq + 4 * (base + k); /* pair record (base + k) / 2, eight floats each */
+            const rt_f2v cx = {q[0], q[1]}, cy = {q[2], q[3]}, cz = {q[4], q[5]}, kk = {q[6], q[7]}; /* (PRIMARY: the last two are ct itself) */
             const rt_f2v cd = __builtin_elementwise_fma(cx, dx2, __builtin_elementwise_fma(cy, dy2, cz * dz2));
-            const rt_f2v co = __builtin_elementwise_fma(cx, ox2, __builtin_elementwise_fma(cy, oy2, cz * oz2));
             const rt_f2v b = od2 - cd;
-            const rt_f2v ct = __builtin_elementwise_fma(m2, co, oo2) + kk;
+            rt_f2v ct = kk;
+            if (!PRIMARY) {
+                const rt_f2v co = __builtin_elementwise_fma(cx, ox2, __builtin_elementwise_fma(cy, oy2, cz * oz2));
+                ct = __builtin_elementwise_fma(m2, co, oo2) + kk;
+            }
             const rt_f2v dq = __builtin_elementwise_fma(b, b, -(qa2 * ct));
             const bool keep0 = !(dq.x < negMargin);
             const bool keep1 = (k + 1 < n) && !(dq.y < negMargin);
@@ -316,10 +327,17 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
             const int k = __builtin_ctz(cand);
             cand &= cand - 1;
             const int s = base + k;
-            const float4 sp = *reinterpret_cast<const float4*>(a.spheres + 4 * s);
-            rt_f3 off = rpos - rt_v3(sp.x, sp.y, sp.z);
+            /* (PRIMARY: the record is (off, qc) already) */
+            float4 sp;
+            if (PRIMARY) {
+                typedef float rt_f4v __attribute__((ext_vector_type(4)));
+                const rt_f4v v = *reinterpret_cast<const RT_CAS rt_f4v*>(&pt->sph[s][0]);
+                sp = make_float4(v.x, v.y, v.z, v.w);
+            }
+            else sp = *reinterpret_cast<const float4*>(a.spheres + 4 * s);
+            rt_f3 off = PRIMARY ? rt_v3(sp.x, sp.y, sp.z) : rpos - rt_v3(sp.x, sp.y, sp.z);
             float qb = 2 * rt_dot(off, rdir);
-            float qc = rt_dot(off, off) - sp.w;
+            float qc = PRIMARY ? sp.w : rt_dot(off, off) - sp.w;
             float disc = qb * qb - 4 * qa * qc;
             if (!(disc >= 0)) continue; /* RC:304: a false positive of phase 1 ends here */
             float sq = rt_sqrt(disc);
@@ -705,17 +723,22 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
  * SGPRs, the root leaf's triangles tested in order; no stack, no suspension. */
 /* ANY (begin_intersect): a lane whose answer is known tests no further triangle, and the wave leaves the model loop once that holds for
  * all of its lanes (a vote: the loop stays wave-uniform). */
-template <bool STATS, bool ANY = false>
-__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st, const float tmax = 0.0f)
+/* PRIMARY (begin_intersect): the origin in each model's space and the per-triangle terms of tri_test come from the table, whose
+ * triangle records lie in the order this loop meets them (the host decodes the root leaves the same way, within the table's caps). */
+template <bool STATS, bool ANY = false, bool PRIMARY = false>
+__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st, const float tmax = 0.0f, const RT_CAS PrimaryTable* pt = nullptr)
 {
     const RT_CAS DModel* cm = (const RT_CAS DModel*)a.models;
     const DTri* __restrict__ tris = a.tris;
+    const RT_CAS float* pr = PRIMARY ? &pt->tri[0][0] : nullptr; /* the next triangle's record */
     for (int m = 0; m < a.nModels; m++) {
         if (ANY && __ballot(!(h.dst < tmax)) == 0ull) break;
         const RT_CAS DModel& M = cm[m];
-        rt_f3 lpos = rt_v3(M.w2l[0] * rpos.x + M.w2l[1] * rpos.y + M.w2l[2] * rpos.z + M.w2l[3] * 1.0f,
-                           M.w2l[4] * rpos.x + M.w2l[5] * rpos.y + M.w2l[6] * rpos.z + M.w2l[7] * 1.0f,
-                           M.w2l[8] * rpos.x + M.w2l[9] * rpos.y + M.w2l[10] * rpos.z + M.w2l[11] * 1.0f);
+        rt_f3 lpos;
+        if (PRIMARY) lpos = rt_v3(pt->lpos[m][0], pt->lpos[m][1], pt->lpos[m][2]);
+        else lpos = rt_v3(M.w2l[0] * rpos.x + M.w2l[1] * rpos.y + M.w2l[2] * rpos.z + M.w2l[3] * 1.0f,
+                          M.w2l[4] * rpos.x + M.w2l[5] * rpos.y + M.w2l[6] * rpos.z + M.w2l[7] * 1.0f,
+                          M.w2l[8] * rpos.x + M.w2l[9] * rpos.y + M.w2l[10] * rpos.z + M.w2l[11] * 1.0f);
         rt_f3 ldir = rt_v3(M.w2l[0] * rdir.x + M.w2l[1] * rdir.y + M.w2l[2] * rdir.z + M.w2l[3] * 0.0f,
                            M.w2l[4] * rdir.x + M.w2l[5] * rdir.y + M.w2l[6] * rdir.z + M.w2l[7] * 0.0f,
                            M.w2l[8] * rdir.x + M.w2l[9] * rdir.y + M.w2l[10] * rdir.z + M.w2l[11] * 0.0f);
@@ -733,7 +756,8 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
             phase_mark<STATS>(st, PH_TRI);
             if (ANY && h.dst < tmax) break;
             const float before = h.dst;
-            tri_test(tris, first + 3 * (int)i, lpos, ldir, cull, h.dst, h.tri, h.u, h.v, h.det);
+            tri_test<PRIMARY>(tris, first + 3 * (int)i, lpos, ldir, cull, h.dst, h.tri, h.u, h.v, h.det, pr);
+            if (PRIMARY) pr += 4;
             if (h.dst < before) {
                 h.obj = a.nSpheres + m;
                 h.backface = h.det < 0;
@@ -1239,7 +1263,12 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
                     /* camera constants — RC:547,557-558 */
                     float cam[16];
                     for (int k = 0; k < 16; k++) cam[k] = c.cam[k];
-                    const rt_f3 camOrigin = rt_mul_point(cam, rt_v3(0.0f, 0.0f, 0.0f), 1.0f);
+                    /* (the FLAT trace kernels take the no-defocus origin from the argument block, where the host left the value of this
+                     * very function for a finite camera — fill_args; mul of the zero vector cannot be folded and cost every camera ray
+                     * 18 instructions with scalar operands.  The BVH variants and the cost kernel keep their code as it was.) */
+                    constexpr bool HOST_ORIGIN = FLAT && !MANY && !COST;
+                    const rt_f3 camOrigin = (HOST_ORIGIN && c.raygenNoDefocus) ? rt_v3(c.primary.camOrigin[0], c.primary.camOrigin[1], c.primary.camOrigin[2])
+                                                                               : rt_mul_point(cam, rt_v3(0.0f, 0.0f, 0.0f), 1.0f);
                     const rt_f3 camRight = rt_v3(cam[0], cam[1], cam[2]);
                     const rt_f3 camUp = rt_v3(cam[4], cam[5], cam[6]);
                     const float invNumPixelsX = c.rcpW; /* x / numPixels.x */
@@ -1280,10 +1309,27 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
             }
             if (pathActive) {
                 phase_mark<STATS>(st, PH_SPHERES);
-                begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
-                segments++;
-                inTrav = true;
-                if (FLAT) traverse_flat<STATS>(a, rpos, rdir, h, st);
+                /* A wave whose active lanes are ALL at bounce 0 holds nothing but fresh camera rays (chains change lanes only behind the
+                 * intersection, and a bounce counts up before its ray comes here), each with rpos == camOrigin bit for bit when the launch
+                 * has no defocus: it may take the launch's table of origin constants (rt_primary.h) for what every lane would otherwise
+                 * compute from rpos.  One vote; a wave with any other ray runs the per-ray code, as does every other kernel. */
+                if constexpr (FLAT && !MANY && !COST) {
+                    const RT_CAS PrimaryTable* const pt = &cold_args().primary;
+                    if (pt->on != 0 && __ballot(bounce != 0) == 0ull) {
+                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt);
+                        traverse_flat<STATS, false, true>(a, rpos, rdir, h, st, 0.0f, pt);
+                    } else {
+                        begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
+                        traverse_flat<STATS>(a, rpos, rdir, h, st);
+                    }
+                    segments++;
+                    inTrav = true;
+                } else { /* (every other kernel: the code as it always was) */
+                    begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
+                    segments++;
+                    inTrav = true;
+                    if (FLAT) traverse_flat<STATS>(a, rpos, rdir, h, st);
+                }
             }
         }
         if constexpr (!POOL) {

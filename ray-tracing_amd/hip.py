@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
 ]
 # every symbol include/rt_cost.h declares (kept apart: ABI_SYMBOLS mirrors rt_abi.h alone)
 COST_SYMBOLS = ["rt_render_cost"]
+# include/rt_primary.h
+PRIMARY_SYMBOLS = ["rt_debug_primary_table"]
 # every symbol include/rt_aov.h declares
 AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
 # every symbol include/rt_denoise.h declares
@@ -520,6 +522,13 @@ class HipTracer(abi.Tracer):
 
     def fused_frames_cap(self):
         return self.api.debug_fused_frames_cap(self.h)
+
+    def primary_table(self):
+        """rt_debug_primary_table: 1 / 0 = the last trace launch carried its table of ray-origin constants switched on / off, -1 = no launch yet"""
+        # bound on first use: tools/ab_libs.py loads libraries of earlier commits, which do not have it, through this class
+        fn = self.api.lib.rt_debug_primary_table
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return fn(self.h)
 
     def synchronize(self):
         self._check(self.api.synchronize(self.h))
