@@ -1,0 +1,30 @@
+/*
+ * rt_tile_cand.h — the per-tile sphere candidates of the FLAT trace kernel, seen from outside (exported by libraytrace_hip.so, plain C).
+ *
+ * In a launch that carries the table of ray-origin constants (rt_primary.h), a wave that holds nothing but fresh camera rays reads which
+ * spheres its rays can meet from a table with one mask per 8 x 8 tile, filled on the GPU when the camera, the image or the spheres have
+ * changed (ray-tracing_amd/csrc/rt_tile_cand.h), instead of deciding it per ray.  Results never depend on it;
+ * RT_TILE_CAND=0 in the environment of rt_create keeps it off.  This header adds the one call that says whether a launch read it: a
+ * table that silently stayed off would cost its speed-up and change nothing else.
+ *
+ * Kept apart from rt_abi.h, whose text is pinned: this header includes it and adds one call.
+ */
+#ifndef RT_TILE_CAND_ABI_H
+#define RT_TILE_CAND_ABI_H
+
+#include "rt_abi.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* 1 if the trace kernels of the context's most recent rt_render_frame / rt_render_frames launch read the per-tile table — the table of
+ * ray-origin constants was on (rt_debug_primary_table) and RT_TILE_CAND was not 0 — 0 if they did not (rt_adaptive_render_frames
+ * never does), -1 before the first launch; RT_ERR_INVALID_ARG for a null context. */
+int rt_debug_tile_cand(const RtContext* ctx);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif

@@ -27,6 +27,7 @@
 #include "rt_kernels.h"
 #include "../../include/rt_cost.h"
 #include "../../include/rt_primary.h"
+#include "../../include/rt_tile_cand.h"
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
 #include "../../include/rt_reproject.h"
@@ -48,6 +49,7 @@
 #include "rt_launch_plan.h"
 #include "rt_scene_prep.h"
 #include "rt_primary.h"
+#include "rt_tile_cand.h"
 #define RT_VERSION_STRING "raytrace_hip gfx950 abi=1"
 
 static thread_local char g_err[512] = "";
@@ -126,6 +128,18 @@ struct RtContext {
     PrimaryTris primaryTris;       /* FLAT scenes within rt_primary.h's caps: the root leaves' triangles, for the per-launch table of origin constants */
     bool primaryOn = true;         /* RT_PRIMARY=0: the table stays off (A/B runs, tests) */
     int lastPrimaryOn = -1;        /* the table's flag in the most recent trace launch's arguments (rt_debug_primary_table); -1 = none yet */
+    /* the per-tile sphere candidates of the all-camera-ray waves (rt_tile_cand.h): one table per render stream (0 main, 1 side), each
+     * written (rt_tile_cand_kernel) and read (the trace kernels) on its own stream only, so stream order is all the order they need and no
+     * launch in flight sees its table change.  A table is refilled, in front of the trace kernel that reads it, only when the key it was
+     * made from — camera block, image, partition, diverge, the spheres themselves — is not the launch's */
+    bool tileCandOn = true;        /* RT_TILE_CAND=0: the per-ray pre-test stays (A/B runs, tests) */
+    int lastTileCand = -1;         /* whether the most recent trace launch read a table (rt_debug_tile_cand); -1 = none yet */
+    uint32_t* dTileCand[2] = {nullptr, nullptr};
+    int tileCandTiles = 0;         /* tiles the two tables are sized for; 0 = none */
+    bool tileCandValid[2] = {false, false};
+    TileCandKey tileCandKey[2];    /* what each stream's table holds */
+    bool tileCandWanted = false;   /* the launch fill_args last prepared may read a table ... */
+    TileCandKey tileCandWant;      /* ... made from this key */
 
     /* uniforms */
     RtParams params;
@@ -494,6 +508,7 @@ int rt_create(int device_id, RtContext** out)
     if (const char* g = getenv("RT_GRID")) ctx->gridOverride = atoi(g); /* tuning hook */
     if (const char* g = getenv("RT_POOL_MIN_ITEMS")) ctx->poolMinItems = atoi(g);
     if (const char* g = getenv("RT_PRIMARY")) ctx->primaryOn = atoi(g) != 0;
+    if (const char* g = getenv("RT_TILE_CAND")) ctx->tileCandOn = atoi(g) != 0;
     if (const char* g = getenv("RT_POOL_FAULT")) { if (atoi(g)) ctx->poolSpinLimit = 64u | 0x80000000u; }
     if (getenv("RT_VERBOSE")) ctx->verbose = true;
     if (const char* f = getenv("RT_FUSE_FRAMES")) ctx->fuseFrames = atoi(f) != 0;
@@ -541,6 +556,8 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dTileOrder[0]);
     hipFree(ctx->dTileOrder[1]);
     hipFree(ctx->dTileKey);
+    hipFree(ctx->dTileCand[0]);
+    hipFree(ctx->dTileCand[1]);
     hipFree(ctx->dDisplay);
     hipFree(ctx->dAovOut);
     hipFree(ctx->dAovWords);
@@ -1059,7 +1076,25 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool wi
             for (int i = 0; i < ctx->nModels; i++) pack_model(ctx->hModels[i], ctx->hRootCodes[i], ctx->hTriBase[i], dm[i]);
         }
         primary_fill(a.primary, allowed, o, sph.data(), ctx->nSpheres, ctx->sphereBound, dm, ctx->nModels, ctx->primaryTris);
-        if (withTable) ctx->lastPrimaryOn = a.primary.on;
+        if (withTable) {
+            ctx->lastPrimaryOn = a.primary.on;
+            /* the per-tile sphere candidates ride on the table: the same launches, the same caps, the same mirror of the spheres */
+            ctx->lastTileCand = 0;
+            ctx->tileCandWanted = ctx->tileCandOn && a.primary.on != 0;
+            if (ctx->tileCandWanted) {
+                TileCandKey& k = ctx->tileCandWant;
+                tile_cand_key_init(k);
+                memcpy(k.cam, a.cam, sizeof(k.cam));
+                memcpy(k.viewParams, a.viewParams, sizeof(k.viewParams));
+                k.rcpWm1 = a.rcpWm1; k.rcpHm1 = a.rcpHm1; k.rcpW = a.rcpW; k.diverge = a.diverge;
+                k.camOrigin[0] = o.x; k.camOrigin[1] = o.y; k.camOrigin[2] = o.z;
+                k.W = (int32_t)a.W; k.H = (int32_t)a.H;
+                k.tilesX = a.tilesX; k.tiles = a.tilesX * a.tilesY;
+                k.stripRows = a.stripRows; k.partIndex = a.partIndex; k.partCount = a.partCount;
+                k.nSpheres = ctx->nSpheres;
+                memcpy(k.sph, sph.data(), sizeof(float) * 4 * (size_t)ctx->nSpheres); /* pack_spheres' exact records; primary.on: at most 32 */
+            }
+        }
     }
     a.counters = ctx->dCounters;
     a.travLimit = ctx->travLimit;
@@ -1174,6 +1209,28 @@ static int prepare_tile_order(RtContext* ctx, KArgs& a, int tiles)
         ctx->order.forget_order();
     }
     a.tileCost = ctx->dTileCost;
+    return RT_OK;
+}
+
+/* ---- prepare buffers: the two streams' tables of per-tile sphere candidates (rt_tile_cand.h), when the launch may read one.  A launch
+ * that finds no memory for them runs with the per-ray pre-test: results do not depend on the table. */
+static int prepare_tile_cand(RtContext* ctx, int tiles)
+{
+    if (!ctx->tileCandWanted || ctx->tileCandTiles == tiles) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx))); /* kernels in flight read the old tables */
+    ctx->tileCandTiles = 0;
+    for (int s = 0; s < 2; s++) {
+        hipFree(ctx->dTileCand[s]); ctx->dTileCand[s] = nullptr;
+        ctx->tileCandValid[s] = false;
+    }
+    for (int s = 0; s < 2; s++)
+        if (hipMalloc(&ctx->dTileCand[s], sizeof(uint32_t) * (size_t)tiles) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->dTileCand[s] = nullptr;
+            ctx->tileCandWanted = false;
+            return RT_OK;
+        }
+    ctx->tileCandTiles = tiles;
     return RT_OK;
 }
 
@@ -1369,6 +1426,19 @@ int HipOrder::trace(int s, int p, int parts)
     a.pxCold = (float4*)((char*)ctx->dPxCold + (size_t)s * ctx->pxColdWaves * RT_COLD_STRIDE_BYTES);
     a.tileQueue = ctx->dTileQueue + s;
     a.tileQueueBase = pp.tileQueueBase;
+    /* this stream's table of per-tile sphere candidates: refilled here, in stream order in front of its reader, when it holds another key's masks */
+    a.tileCand = nullptr;
+    if (ctx->tileCandWanted && ctx->tileCandTiles == job->tiles && ctx->tileCandWant.tiles == job->tiles) {
+        if (!ctx->tileCandValid[s] || memcmp(&ctx->tileCandKey[s], &ctx->tileCandWant, sizeof(TileCandKey)) != 0) {
+            ctx->tileCandValid[s] = false;
+            hipLaunchKernelGGL(rtk::rt_tile_cand_kernel, dim3((unsigned)((job->tiles + 255) / 256)), dim3(256), 0, st, ctx->tileCandWant, ctx->dTileCand[s]);
+            HIP_TRY(ctx, hipGetLastError());
+            ctx->tileCandKey[s] = ctx->tileCandWant;
+            ctx->tileCandValid[s] = true;
+        }
+        a.tileCand = ctx->dTileCand[s];
+        ctx->lastTileCand = 1;
+    }
     RtContext::Tuner::Probe* probe = job->probe;
     const int fuseSlot = nFrames > 1 ? mark_fused_launch_begin(ctx, st) : -1;
     if (probe) hipEventRecord(probe->start, st);
@@ -1402,6 +1472,7 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
     if (rc) return rc;
     if ((rc = prepare_records(ctx, plan))) return rc;
     if ((rc = prepare_tile_order(ctx, a, tiles))) return rc;
+    if ((rc = prepare_tile_cand(ctx, tiles))) return rc;
     /* Fused launches (several frames: (tile, frame) items, per-frame colours staged and summed in frame order afterwards) alternate
      * between the context's two streams (own streams only), each with its own staging slab: the trace kernel of launch k+1 — other
      * frames, nothing shared but the scene — starts while launch k drains, and only the rt_accumulate_kernels, which add into the
@@ -1722,6 +1793,7 @@ struct DevScratch {
 
 int rt_debug_fused_frames_cap(const RtContext* ctx) { return ctx ? ctx->fuseCap : RT_ERR_INVALID_ARG; }
 int rt_debug_primary_table(const RtContext* ctx) { return ctx ? ctx->lastPrimaryOn : RT_ERR_INVALID_ARG; }
+int rt_debug_tile_cand(const RtContext* ctx) { return ctx ? ctx->lastTileCand : RT_ERR_INVALID_ARG; }
 
 int rt_debug_intersect(RtContext* ctx, const float* origins, const float* dirs, int n, float* out10)
 {

@@ -33,6 +33,7 @@
 #include "../../include/rt_abi.h"
 #include "../../include/rt_math.h"
 #include "rt_device.h"
+#include "rt_tile_cand.h"
 
 /* Tuning knobs (values measured on MI355X). */
 /* traverse() is left once active <= entered * NUM/DEN lanes are still traversing */
@@ -252,9 +253,12 @@ struct Trav {
  * so rpos is the launch's camOrigin in all of them and the terms below that depend on rpos and the scene alone — oo, c.o and ct of the
  * pre-test, off and qc of the exact test — come from the table `pt` the host filled with the same fp32 operations: same bits, computed
  * once per launch instead of once per lane.  The table holds at most one block of 32 spheres. */
+/* tileCand (PRIMARY only; rt_tile_cand.h): when the launch carries the table of per-tile sphere candidates, the conservative per-ray
+ * pre-test below is replaced by another conservative filter, decided once per tile: the lane reads the mask of its pixel's tile (`tile`,
+ * the fourth word of its record) and goes straight to the unchanged exact loop.  The stats build audits it like the pre-test. */
 template <bool STATS, bool FLAT, bool MANY, bool ANY = false, bool PRIMARY = false>
 __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f,
-                                                const RT_CAS PrimaryTable* pt = nullptr)
+                                                const RT_CAS PrimaryTable* pt = nullptr, const uint32_t* tileCand = nullptr, const uint32_t tile = 0u)
 {
     h.dst = RT_INF;
     h.obj = -1;
@@ -296,6 +300,18 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
     for (int base = 0; base < a.nSpheres; base += 32) {
         const int n = (a.nSpheres - base) < 32 ? (a.nSpheres - base) : 32;
         uint32_t cand = 0;
+        if (PRIMARY && tileCand != nullptr) { /* (wave-uniform; the table holds one block: base == 0) */
+            cand = tileCand[tile];
+            if (STATS) { /* audit: no sphere whose bit is clear may be accepted by the exact test */
+                for (uint32_t rest = ~cand & (n >= 32 ? 0xffffffffu : (1u << n) - 1u); rest; rest &= rest - 1) {
+                    const int s = base + __builtin_ctz(rest);
+                    const rt_f3 off = rt_v3(pt->sph[s][0], pt->sph[s][1], pt->sph[s][2]);
+                    const float qb = 2 * rt_dot(off, rdir);
+                    const float disc = qb * qb - 4 * qa * pt->sph[s][3];
+                    if (disc >= 0 && (-qb + rt_sqrt(disc)) * rt_rcp(2 * qa) >= 0) st.filterViolations++;
+                }
+            }
+        } else
         for (int k = 0; k < n; k += 2) {
             const RT_CAS float* q = PRIMARY ? &pt->pair[0][0] + 4 * (base + k) : sphq + 4 * (base + k); /* pair record (base + k) / 2, eight floats each */
             const rt_f2v cx = {q[0], q[1]}, cy = {q[2], q[3]}, cz = {q[4], q[5]}, kk = {q[6], q[7]}; /* (PRIMARY: the last two are ct itself) */
@@ -1316,7 +1332,10 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
                 if constexpr (FLAT && !MANY && !COST) {
                     const RT_CAS PrimaryTable* const pt = &cold_args().primary;
                     if (pt->on != 0 && __ballot(bounce != 0) == 0ull) {
-                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt);
+                        /* (the lane's tile: the fourth word of its record, written at set-up for the tile cost; it travels with the chain) */
+                        const uint32_t* const tileCand = cold_args().tileCand;
+                        const uint32_t tile = tileCand ? __float_as_uint(PX_COLD(cold_args())[RT_WAVE].w) : 0u;
+                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt, tileCand, tile);
                         traverse_flat<STATS, false, true>(a, rpos, rdir, h, st, 0.0f, pt);
                     } else {
                         begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
@@ -1753,6 +1772,18 @@ __global__ void __launch_bounds__(1024) rt_order_kernel(const uint32_t* cost, ui
     __syncthreads();
     /* stable within a bucket is not needed; keep tile order roughly spatial by walking in index order per thread */
     for (int i = t; i < nTiles; i += 1024) order[atomicAdd(&base[key[i]], 1u)] = (uint32_t)i;
+}
+
+/* The per-tile sphere candidates of the FLAT trace kernel's all-camera-ray waves (rt_tile_cand.h): one thread per tile of this context,
+ * out[tile] = the tile's mask.  Launched in front of a trace kernel, on its stream, only when that stream's table was made from another
+ * key (another camera, image, partition, diverge or set of spheres). */
+__global__ void __launch_bounds__(256) rt_tile_cand_kernel(const TileCandKey k, uint32_t* out)
+{
+    const int tile = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (tile >= k.tiles) return;
+    int x0, y0;
+    tile_cand_origin(k, tile, &x0, &y0);
+    out[tile] = tile_cand_mask(k, x0, y0);
 }
 
 /* Display pass — Display.shader:42-47: col = tex / Frame (the blit of RayTraceDisplay.cs:9-23).

@@ -33,6 +33,8 @@ ABI_SYMBOLS = [
 COST_SYMBOLS = ["rt_render_cost"]
 # include/rt_primary.h
 PRIMARY_SYMBOLS = ["rt_debug_primary_table"]
+# include/rt_tile_cand.h
+TILE_CAND_SYMBOLS = ["rt_debug_tile_cand"]
 # every symbol include/rt_aov.h declares
 AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
 # every symbol include/rt_denoise.h declares
@@ -527,6 +529,12 @@ class HipTracer(abi.Tracer):
         """rt_debug_primary_table: 1 / 0 = the last trace launch carried its table of ray-origin constants switched on / off, -1 = no launch yet"""
         # bound on first use: tools/ab_libs.py loads libraries of earlier commits, which do not have it, through this class
         fn = self.api.lib.rt_debug_primary_table
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return fn(self.h)
+
+    def tile_cand(self):
+        """rt_debug_tile_cand: 1 / 0 = the last trace launch read / did not read the per-tile table of sphere candidates, -1 = no launch yet"""
+        fn = self.api.lib.rt_debug_tile_cand  # bound on first use, like primary_table
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
         return fn(self.h)
 

@@ -1,0 +1,190 @@
+"""The FLAT trace kernel's per-tile sphere candidates (ray-tracing_amd/csrc/rt_tile_cand.h) on the GPU.
+
+A wave whose active lanes are all fresh camera rays reads the spheres its rays can meet from a table with one mask per 8 x 8 tile, filled
+on the GPU in front of the trace kernel whenever the camera, the image or the spheres have changed, instead of running the conservative
+pre-test per ray.  One conservative filter replaces another in front of the same exact arithmetic, so the image and the exact counters
+must not move by a bit.  Every case here is rendered EIGHT ways — table on / RT_TILE_CAND=0, as pooled workgroups (RT_POOL_MIN_ITEMS=0:
+also at these small sizes) / as single waves (RT_POOL=0), by the shipped and by the STATS instantiation — and each image is compared bit
+for bit with ONE render of the CPU oracle, the segment counters (and, in the STATS build, all exact counters) with the oracle's, the
+audit of the filters (filter_violations: in the STATS build every sphere whose bit is clear goes through the exact test) with 0, and
+rt_debug_tile_cand with what the caps say: a table that silently stayed off would pass everything else.
+
+The sequences are the ones in which a stale table would show: a sphere moved across the image between frames, a camera move, single
+frames (two parts, one per stream) alternating with fused launches (which alternate between the streams themselves)."""
+import contextlib
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+KEYS = ["segments", "innerSteps", "leafSteps", "triTests", "sphereTests", "modelVisits", "pixelFrames"]
+WAYS = [("table, pooled", {"RT_TILE_CAND": "1", "RT_POOL_MIN_ITEMS": "0"}), ("no table, pooled", {"RT_TILE_CAND": "0", "RT_POOL_MIN_ITEMS": "0"}),
+        ("table, single waves", {"RT_TILE_CAND": "1", "RT_POOL": "0"}), ("no table, single waves", {"RT_TILE_CAND": "0", "RT_POOL": "0"})]
+
+
+@contextlib.contextmanager
+def environment(env):
+    """RT_TILE_CAND and RT_POOL_MIN_ITEMS are read when a context is made, RT_POOL when a scene is uploaded"""
+    names = ("RT_TILE_CAND", "RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")
+    old = {k: os.environ.get(k) for k in names}
+    for k in names:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def check(pkg, api, orc, drive, table=True, part=None):
+    """drive(lib, tracer) renders the case; the tracer holds the result.  table: whether the case's last launch is within the caps.
+    part = (strip_rows, index, count): the GPU contexts render that part of the image and are compared with its rows of the oracle's
+    whole image; their counters (a part's share, which the oracle does not have) must then agree among the eight ways."""
+    c = orc.create_tracer(8)
+    drive(orc, c)
+    want, wantCounters = c.read_accumulated(), c.counters()
+    c.close()
+    first = None
+    for name, env in WAYS:
+        with environment(env):
+            for stats in (False, True):
+                g = api.create_tracer(0)
+                if part:
+                    g.set_partition(*part)
+                g.enable_stats(stats)
+                drive(api, g)
+                got, counters = g.read_accumulated(), g.counters()
+                violations = g.phase_profile()["filter_violations"][0] if stats else 0
+                on, primary = g.tile_cand(), g.primary_table()
+                g.close()
+                what = f"{name}, stats={stats}"
+                assert primary == (1 if table else 0), f"{what}: rt_debug_primary_table() = {primary}"
+                assert on == (1 if table and env["RT_TILE_CAND"] == "1" else 0), f"{what}: rt_debug_tile_cand() = {on}"
+                if part:
+                    rows = pkg.dist.global_rows_of(part[1], part[2], want.shape[0], part[0])
+                    assert np.array_equal(bits(got), bits(want[rows])), f"{what}: image differs from the oracle's rows"
+                    first = first or counters
+                    for k in ("segments", "pixelFrames"):
+                        assert counters[k] == first[k], (what, k)
+                else:
+                    assert got.shape == want.shape and np.array_equal(bits(got), bits(want)), f"{what}: image differs from the oracle's"
+                    assert counters["segments"] == wantCounters["segments"] and counters["pixelFrames"] == wantCounters["pixelFrames"], what
+                    if stats:
+                        assert [counters[k] for k in KEYS] == [wantCounters[k] for k in KEYS], what
+                if stats:
+                    assert violations == 0, what
+
+
+def scene_driver(pkg, cfg, w, h, steps, change_scene=None, tweak=None):
+    def drive(lib, tr):
+        sc = pkg.scenes.get(cfg)
+        if change_scene:
+            change_scene(sc)
+        mgr = sc.make_manager(tr, lib, w, h)
+        if tweak:
+            tweak(mgr)
+        mgr.OnEnable(renderSeed=1)
+        steps(mgr, tr)
+    return drive
+
+
+def frames(n):
+    return lambda mgr, tr: mgr.RenderFrames(n)
+
+
+@pytest.mark.parametrize("cfg,w,h", [(2, 96, 54), (2, 37, 23), (1, 64, 64)])
+def test_config_scenes(pkg, api, orc, cfg, w, h):
+    check(pkg, api, orc, scene_driver(pkg, cfg, w, h, frames(9)))
+
+
+def _spheres(pkg, n):
+    """n spheres on a grid over the ground, a third of them glass"""
+    mod = pkg.manager
+    rnd = pkg.meshes._lcg(11)
+    out = []
+    for i in range(n):
+        r = 0.25 + 0.35 * rnd()
+        kw = dict(diffuseCol=(0.3 + 0.6 * rnd(), 0.3 + 0.6 * rnd(), 0.3 + 0.6 * rnd(), 1.0))
+        if i % 3 == 2:
+            kw = dict(flag=pkg.abi.MATERIAL_GLASS, ior=1.5, smoothness=1.0, specularProbability=1.0, absorption=(0.2, 0.4, 0.1, 1), absorptionMultiplier=0.6)
+        out.append(mod.Sphere(((i % 7 - 3) * 1.4 + 0.3 * rnd(), r, (i // 7 - 2) * 1.5 + 0.3 * rnd()), r, mod.RayTracingMaterial(**kw)))
+    return out
+
+
+@pytest.mark.parametrize("n", [32, 33])
+def test_sphere_count_at_and_over_the_cap(pkg, api, orc, n):
+    """32: every bit of the mask word in use; 33: a second block of the pre-test, no table"""
+    def change(sc):
+        sc.spheres = _spheres(pkg, n)
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(9), change_scene=change), table=n <= 32)
+
+
+def test_defocus_keeps_the_table_off(pkg, api, orc):
+    def tweak(mgr):
+        mgr.defocusStrength = 120.0
+        mgr.focusDistance = 7.0
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(9), tweak=tweak), table=False)
+
+
+def test_camera_inside_a_sphere(pkg, api, orc):
+    """the camera sits inside glass sphere 2: every tile must keep it, and sees the others through it"""
+    def change(sc):
+        sc.spheres[2].centre = (0.1, 2.5, -8.6)
+        sc.spheres[2].radius = 0.8
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(9), change_scene=change))
+
+
+def test_strip_partition_two_of_three(pkg, api, orc):
+    """local tile rows are not global rows: part 1 of 3 at 96x54 owns rows 8-15 and 32-39"""
+    check(pkg, api, orc, scene_driver(pkg, 2, 96, 54, frames(9)), part=(8, 1, 3))
+
+
+def test_a_sphere_moved_across_the_image_between_frames(pkg, api, orc):
+    """a table made for the old spheres would drop the moved one from the tiles it now covers"""
+    def steps(mgr, tr):
+        mgr.RenderFrames(3)
+        x, y, z = mgr.spheres[5].centre
+        try:
+            for dx in (-4.0, 4.0):
+                mgr.spheres[5].centre = (x + dx, y + 0.6, z - 2.0)
+                tr.update_spheres(mgr._pack_spheres())
+                mgr.RenderFrames(3)
+        finally:
+            mgr.spheres[5].centre = (x, y, z)
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, steps))
+
+
+def test_camera_move_between_frames(pkg, api, orc):
+    def steps(mgr, tr):
+        mgr.RenderFrames(3)
+        t = mgr.camera.transform
+        mgr.camera.transform = type(t)(position=(1.25, 3.5, -7.0), euler=(18, -9, 0))
+        try:
+            mgr.RenderFrame()
+            mgr.RenderFrames(5)
+        finally:
+            mgr.camera.transform = t   # (the scene description's camera object is shared)
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, steps))
+
+
+def test_single_frames_and_fused_launches_on_both_streams(pkg, api, orc):
+    """a single frame runs as two parts, one per stream; fused launches alternate between the streams: each stream's table is filled
+    once, by whichever launch first needs it, and read by all of them"""
+    def steps(mgr, tr):
+        idle = getattr(tr, "synchronize", lambda: None)   # (an idle GPU starts a single frame at once instead of holding it back)
+        mgr.RenderFrame()
+        idle()
+        mgr.RenderFrames(5)
+        idle()
+        mgr.RenderFrame()
+        idle()
+        mgr.RenderFrames(2)
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, steps))

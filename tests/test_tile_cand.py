@@ -1,0 +1,123 @@
+"""The per-tile sphere candidates (ray-tracing_amd/csrc/rt_tile_cand.h) on their own, without a device and without the kernels.
+
+tests/tile_cand_driver.cpp is built against the header with the host compiler, twice: plainly (-O2 -Wall -Wextra -Werror) and with the
+address and undefined-behaviour sanitizers, as a stand-alone executable with the runtimes linked into it (nothing sanitized is loaded into
+python; a report ends the program with a non-zero exit, which fails the test).  Both are built without contraction, the arithmetic
+contract of include/rt_math.h.
+
+What the driver checks: for every tile it visits, every camera ray built with the kernel's own raygen formulas — all 64 pixels clipped at
+W / H, the jitter at the centre, at 16 points of the unit circle and at 16 random interior points — goes through the exact sphere test of
+begin_intersect, and every sphere that ACCEPTS a ray (disc >= 0 and dstFar >= 0) must have its bit in the tile's mask: 0 misses.  Cases:
+seeded random cameras with 1 ... 32 spheres (one enclosing the camera, some behind it, some touching the frustum's edge) at 37x23 and 96x54
+over every tile, whole images and the 2-of-3 strip partition, diverge 0 / 1.5 / 50; and the cameras and spheres of configs 1 and 2 at
+37x23, 96x54 and 1920x1080 (every 50th tile plus all edge tiles).
+
+Selectivity keeps a mask of all ones from passing: on config 2 at 1920x1080 the mean number of bits of the mask may exceed the mean number
+of spheres the tile's sampled rays were really accepted by (a function of the scene alone, and a lower bound of what any correct mask
+holds) by at most 1.0 — and that bound lies far below the 16 bits of an all-ones mask, which the test checks too."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cxx():
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    return cxx
+
+
+@pytest.fixture(scope="module")
+def drivers(tmp_path_factory):
+    d = tmp_path_factory.mktemp("tile_cand")
+    src = os.path.join(ROOT, "tests", "tile_cand_driver.cpp")
+    plain, san = str(d / "driver"), str(d / "driver_san")
+    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
+    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", src, "-o", san])
+    return {"plain": plain, "san": san, "dir": d}
+
+
+def run(exe, *args):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RT_")}
+    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, env=env, timeout=600)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0, (p.returncode, out[-3000:], p.stderr.decode(errors="replace")[-3000:])
+    last = out.strip().splitlines()[-1]
+    assert last.startswith("ok ") and " misses=0 " in last + " ", out[-3000:]
+    return {k: float(v) for k, v in re.findall(r"(\w+)=([-0-9.e+]+)", last)}
+
+
+class _NoTracer:
+    """make_manager wants a tracer; params() never calls it"""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the tracer is not to be called ({name})")
+
+
+def scene_file(pkg, api, d, cfg, w, h, part=(8, 0, 1)):
+    """the camera block and spheres of a config as the manager hands them to the library, in the driver's text form"""
+    mgr = pkg.scenes.get(cfg).make_manager(_NoTracer(), api, w, h)
+    p = mgr.params()
+    assert p.defocusStrength == 0.0
+    lines = [f"{w} {h} {part[0]} {part[1]} {part[2]} {p.divergeStrength!r}",
+             " ".join(repr(float(v)) for v in p.camLocalToWorld),
+             " ".join(repr(float(v)) for v in p.viewParams),
+             str(len(mgr.spheres))]
+    import numpy as np
+    for s in mgr.spheres:
+        lines.append(" ".join(repr(float(np.float32(v))) for v in (*s.centre, s.radius)))
+    path = str(d / f"config{cfg}_{w}x{h}_{part[1]}of{part[2]}.txt")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return path
+
+
+@pytest.mark.parametrize("seed", [1, 2, 20261018])
+def test_no_accepted_sphere_is_missing_from_a_tile_mask(drivers, seed):
+    r = run(drivers["san"], "random", seed, 48)
+    assert r["cases"] == 48 and r["rays"] > 1e6
+
+
+def test_plain_build_agrees(drivers):
+    """-O2 without the sanitizers: the optimiser must not make the mask less conservative either"""
+    run(drivers["plain"], "random", 1, 48)
+
+
+@pytest.mark.parametrize("cfg", [1, 2])
+@pytest.mark.parametrize("size,part", [((37, 23), (8, 0, 1)), ((96, 54), (8, 0, 1)), ((96, 54), (8, 1, 3))])
+def test_config_cameras_small(pkg, api, drivers, cfg, size, part):
+    run(drivers["san"], "scene", scene_file(pkg, api, drivers["dir"], cfg, *size, part), 1)
+
+
+def test_config1_full_size(pkg, api, drivers):
+    run(drivers["plain"], "scene", scene_file(pkg, api, drivers["dir"], 1, 1920, 1080), 50)
+
+
+def test_config2_full_size_and_selectivity(pkg, api, drivers):
+    """every 50th tile plus all edge tiles of the headline image: 0 misses; and the mask is nearly as tight as the scene allows"""
+    r = run(drivers["plain"], "scene", scene_file(pkg, api, drivers["dir"], 2, 1920, 1080), 50)
+    print("config 2 at 1920x1080:", r)
+    assert r["tiles"] == 240 * 135 and r["spheres"] == 16
+    assert r["mean_brute"] + 1.0 < 8.0, "the bound leaves no room: an all-ones mask (16 bits) must be far above it"
+    assert r["mean_mask"] <= r["mean_brute"] + 1.0
+
+
+def test_config2_full_size_partition(pkg, api, drivers):
+    run(drivers["plain"], "scene", scene_file(pkg, api, drivers["dir"], 2, 1920, 1080, (8, 1, 3)), 50)
+
+
+def test_public_header_symbol_is_exported(pkg, api):
+    """include/rt_tile_cand.h declares one call; hip.TILE_CAND_SYMBOLS mirrors it and the library exports it"""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rt_tile_cand.h")).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(rt_[a-z_0-9]+)\s*\(", text)))
+    assert names == sorted(pkg.hip.TILE_CAND_SYMBOLS) == ["rt_debug_tile_cand"]
+    assert not set(names) & set(pkg.hip.ABI_SYMBOLS)
+    for n in names:
+        assert hasattr(api.lib, n), f"libraytrace_hip.so does not export {n}"
+    assert api.lib.rt_debug_tile_cand(None) == pkg.abi.RT_ERR_INVALID_ARG
