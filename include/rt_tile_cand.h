@@ -13,6 +13,7 @@
 #define RT_TILE_CAND_ABI_H
 
 #include "rt_abi.h"
+#include "rt_tile_tri.h" /* the table's triangle half: RT_TILE_TRI, and the one call that says whether a launch read triangle masks */
 
 #ifdef __cplusplus
 extern "C" {

@@ -134,6 +134,8 @@ struct RtContext {
      * made from — camera block, image, partition, diverge, the spheres themselves — is not the launch's */
     bool tileCandOn = true;        /* RT_TILE_CAND=0: the per-ray pre-test stays (A/B runs, tests) */
     int lastTileCand = -1;         /* whether the most recent trace launch read a table (rt_debug_tile_cand); -1 = none yet */
+    bool tileTriOn = true;         /* RT_TILE_TRI=0: the table's triangle half stays off alone: every triangle mask is all ones (A/B runs, tests) */
+    int lastTileTri = -1;          /* whether that launch's table held triangle masks (rt_debug_tile_tri); -1 = none yet */
     uint32_t* dTileCand[2] = {nullptr, nullptr};
     int tileCandTiles = 0;         /* tiles the two tables are sized for; 0 = none */
     bool tileCandValid[2] = {false, false};
@@ -509,6 +511,7 @@ int rt_create(int device_id, RtContext** out)
     if (const char* g = getenv("RT_POOL_MIN_ITEMS")) ctx->poolMinItems = atoi(g);
     if (const char* g = getenv("RT_PRIMARY")) ctx->primaryOn = atoi(g) != 0;
     if (const char* g = getenv("RT_TILE_CAND")) ctx->tileCandOn = atoi(g) != 0;
+    if (const char* g = getenv("RT_TILE_TRI")) ctx->tileTriOn = atoi(g) != 0;
     if (const char* g = getenv("RT_POOL_FAULT")) { if (atoi(g)) ctx->poolSpinLimit = 64u | 0x80000000u; }
     if (getenv("RT_VERBOSE")) ctx->verbose = true;
     if (const char* f = getenv("RT_FUSE_FRAMES")) ctx->fuseFrames = atoi(f) != 0;
@@ -1080,6 +1083,7 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool wi
             ctx->lastPrimaryOn = a.primary.on;
             /* the per-tile sphere candidates ride on the table: the same launches, the same caps, the same mirror of the spheres */
             ctx->lastTileCand = 0;
+            ctx->lastTileTri = 0;
             ctx->tileCandWanted = ctx->tileCandOn && a.primary.on != 0;
             if (ctx->tileCandWanted) {
                 TileCandKey& k = ctx->tileCandWant;
@@ -1093,6 +1097,23 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool wi
                 k.stripRows = a.stripRows; k.partIndex = a.partIndex; k.partCount = a.partCount;
                 k.nSpheres = ctx->nSpheres;
                 memcpy(k.sph, sph.data(), sizeof(float) * 4 * (size_t)ctx->nSpheres); /* pack_spheres' exact records; primary.on: at most 32 */
+                /* the triangle half: what traverse_flat and tri_test read in these waves — the packed w2l rows, the table's lpos and the
+                 * laid-out local records (primary.on: within RT_PRIMARY_MAX_MODELS / RT_PRIMARY_MAX_TRIS, the caps of the mask) */
+                const PrimaryTris& pt = ctx->primaryTris;
+                k.triOn = ctx->tileTriOn ? 1 : 0;
+                if (k.triOn) {
+                    k.nTriModels = ctx->nModels;
+                    int t = 0;
+                    for (int m = 0; m < ctx->nModels; m++) {
+                        k.triCount[m] = pt.count[m];
+                        memcpy(k.w2l[m], dm[m].w2l, sizeof(k.w2l[m]));
+                        memcpy(k.lpos[m], a.primary.lpos[m], sizeof(k.lpos[m]));
+                        for (int i = 0; i < pt.count[m]; i++, t++) {
+                            memcpy(&k.tri[t][0], pt.a[t], 12); memcpy(&k.tri[t][3], pt.ab[t], 12);
+                            memcpy(&k.tri[t][6], pt.ac[t], 12); memcpy(&k.tri[t][9], pt.face[t], 12);
+                        }
+                    }
+                }
             }
         }
     }
@@ -1224,7 +1245,7 @@ static int prepare_tile_cand(RtContext* ctx, int tiles)
         ctx->tileCandValid[s] = false;
     }
     for (int s = 0; s < 2; s++)
-        if (hipMalloc(&ctx->dTileCand[s], sizeof(uint32_t) * (size_t)tiles) != hipSuccess) {
+        if (hipMalloc(&ctx->dTileCand[s], 2 * sizeof(uint32_t) * (size_t)tiles) != hipSuccess) { /* (sphere mask, triangle mask) per tile */
             (void)hipGetLastError();
             ctx->dTileCand[s] = nullptr;
             ctx->tileCandWanted = false;
@@ -1438,6 +1459,7 @@ int HipOrder::trace(int s, int p, int parts)
         }
         a.tileCand = ctx->dTileCand[s];
         ctx->lastTileCand = 1;
+        ctx->lastTileTri = ctx->tileCandWant.triOn;
     }
     RtContext::Tuner::Probe* probe = job->probe;
     const int fuseSlot = nFrames > 1 ? mark_fused_launch_begin(ctx, st) : -1;
@@ -1794,6 +1816,7 @@ struct DevScratch {
 int rt_debug_fused_frames_cap(const RtContext* ctx) { return ctx ? ctx->fuseCap : RT_ERR_INVALID_ARG; }
 int rt_debug_primary_table(const RtContext* ctx) { return ctx ? ctx->lastPrimaryOn : RT_ERR_INVALID_ARG; }
 int rt_debug_tile_cand(const RtContext* ctx) { return ctx ? ctx->lastTileCand : RT_ERR_INVALID_ARG; }
+int rt_debug_tile_tri(const RtContext* ctx) { return ctx ? ctx->lastTileTri : RT_ERR_INVALID_ARG; }
 
 int rt_debug_intersect(RtContext* ctx, const float* origins, const float* dirs, int n, float* out10)
 {

@@ -103,7 +103,7 @@ struct KArgs {
     uint32_t poolSpinLimit;      /* polls of a cell's sequence word before the chain pool's watchdog gives up (65,536); top bit: the RT_POOL_FAULT test hook */
     /* (behind everything else, for the same reason; read through cold_args() where it is used) */
     PrimaryTable primary;        /* the FLAT variant's per-launch ray-origin constants (rt_primary.h); primary.on = 0: not in use */
-    const uint32_t* tileCand;    /* the FLAT variant's per-tile sphere candidates (rt_tile_cand.h), one mask per tile of this context, indexed like
+    const uint32_t* tileCand;    /* the FLAT variant's per-tile candidates (rt_tile_cand.h), (sphere mask, triangle mask) per tile of this context, indexed like
                                   * tileCost; null = not in use.  Non-null only with primary.on: its readers are the all-camera-ray waves */
 };
 

@@ -256,9 +256,17 @@ struct Trav {
 /* tileCand (PRIMARY only; rt_tile_cand.h): when the launch carries the table of per-tile sphere candidates, the conservative per-ray
  * pre-test below is replaced by another conservative filter, decided once per tile: the lane reads the mask of its pixel's tile (`tile`,
  * the fourth word of its record) and goes straight to the unchanged exact loop.  The stats build audits it like the pre-test. */
+/* tw (with tileCand): the table's second word per tile is the mask of the root-leaf triangles the tile's camera rays can be accepted by, in
+ * traverse_flat's order.  It is turned into the wave's union here, right behind the load — one ballot, plus a readlane and a ballot per
+ * DISTINCT mask among the lanes; a scalar from then on — so that no vector register lives across the sphere loop; traverse_flat skips what no lane wants. */
+struct TriWant {
+    uint32_t wave; /* wave-uniform: triangles some active lane may be accepted by; all ones = no table */
+    uint32_t lane; /* this lane's own mask (read by the stats build's audit only) */
+};
 template <bool STATS, bool FLAT, bool MANY, bool ANY = false, bool PRIMARY = false>
 __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f,
-                                                const RT_CAS PrimaryTable* pt = nullptr, const uint32_t* tileCand = nullptr, const uint32_t tile = 0u)
+                                                const RT_CAS PrimaryTable* pt = nullptr, const uint32_t* tileCand = nullptr, const uint32_t tile = 0u,
+                                                TriWant* tw = nullptr)
 {
     h.dst = RT_INF;
     h.obj = -1;
@@ -283,91 +291,130 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
      *   the first of equal hits, like the reference's in-order loop) and do the reference's
      *   fp32 operations for that sphere: discriminant, then the roots.
      * 4th float of a sphere record is radius*radius, computed on upload with the same fp32 multiply. */
-    const RT_CAS float* sph = (const RT_CAS float*)a.spheres;
-    const RT_CAS float* sphq = (const RT_CAS float*)a.sphereQuick;
-    const float qa = rt_dot(rdir, rdir);
-    const float od = __builtin_fmaf(rpos.x, rdir.x, __builtin_fmaf(rpos.y, rdir.y, rpos.z * rdir.z));
-    const float oo = PRIMARY ? 0.0f : __builtin_fmaf(rpos.x, rpos.x, __builtin_fmaf(rpos.y, rpos.y, rpos.z * rpos.z));
-    const float negMargin = -(7.62939453125e-06f * qa * (PRIMARY ? pt->ooBound : oo + a.sphereBound)); /* 2^-17 */
-    /* Two spheres per step, side by side in packed fp32 instructions: the sphere data sits in SGPRs, and on gfx950 a VALU
-     * instruction with an SGPR source issues at the slow rate (4.5 cycles against 2.9, profiles/r03_valu_op_rates.txt) while
-     * v_pk_fma/mul/add_f32 take an SGPR pair at no extra cost (5.0 cycles for both halves) — the same operations on the same
-     * values per sphere, so the candidate masks do not change. */
-    typedef float rt_f2v __attribute__((ext_vector_type(2)));
-    const rt_f2v dx2 = {rdir.x, rdir.x}, dy2 = {rdir.y, rdir.y}, dz2 = {rdir.z, rdir.z};
-    const rt_f2v ox2 = {rpos.x, rpos.x}, oy2 = {rpos.y, rpos.y}, oz2 = {rpos.z, rpos.z};
-    const rt_f2v od2 = {od, od}, oo2 = {oo, oo}, qa2 = {qa, qa}, m2 = {-2.0f, -2.0f};
-    for (int base = 0; base < a.nSpheres; base += 32) {
-        const int n = (a.nSpheres - base) < 32 ? (a.nSpheres - base) : 32;
-        uint32_t cand = 0;
-        if (PRIMARY && tileCand != nullptr) { /* (wave-uniform; the table holds one block: base == 0) */
-            cand = tileCand[tile];
-            if (STATS) { /* audit: no sphere whose bit is clear may be accepted by the exact test */
-                for (uint32_t rest = ~cand & (n >= 32 ? 0xffffffffu : (1u << n) - 1u); rest; rest &= rest - 1) {
-                    const int s = base + __builtin_ctz(rest);
-                    const rt_f3 off = rt_v3(pt->sph[s][0], pt->sph[s][1], pt->sph[s][2]);
-                    const float qb = 2 * rt_dot(off, rdir);
-                    const float disc = qb * qb - 4 * qa * pt->sph[s][3];
-                    if (disc >= 0 && (-qb + rt_sqrt(disc)) * rt_rcp(2 * qa) >= 0) st.filterViolations++;
-                }
-            }
-        } else
-        for (int k = 0; k < n; k += 2) {
-            const RT_CAS float* q = PRIMARY ? &pt->pair[0][0] + 4 * (base + k) : sphq + 4 * (base + k); /* pair record (base + k) / 2, eight floats each */
-            const rt_f2v cx = {q[0], q[1]}, cy = {q[2], q[3]}, cz = {q[4], q[5]}, kk = {q[6], q[7]}; /* (PRIMARY: the last two are ct itself) */
-            const rt_f2v cd = __builtin_elementwise_fma(cx, dx2, __builtin_elementwise_fma(cy, dy2, cz * dz2));
-            const rt_f2v b = od2 - cd;
-            rt_f2v ct = kk;
-            if (!PRIMARY) {
-                const rt_f2v co = __builtin_elementwise_fma(cx, ox2, __builtin_elementwise_fma(cy, oy2, cz * oz2));
-                ct = __builtin_elementwise_fma(m2, co, oo2) + kk;
-            }
-            const rt_f2v dq = __builtin_elementwise_fma(b, b, -(qa2 * ct));
-            const bool keep0 = !(dq.x < negMargin);
-            const bool keep1 = (k + 1 < n) && !(dq.y < negMargin);
-            if (STATS) { /* audit against the reference's discriminant */
-                for (int j = 0; j < 2 && k + j < n; j++) {
-                    const int s = base + k + j;
-                    rt_f3 off = rpos - rt_v3(sph[4 * s + 0], sph[4 * s + 1], sph[4 * s + 2]);
-                    float qb = 2 * rt_dot(off, rdir);
-                    float qc = rt_dot(off, off) - sph[4 * s + 3];
-                    float disc = qb * qb - 4 * qa * qc;
-                    if (disc >= 0 && !(j ? keep1 : keep0)) st.filterViolations++;
-                }
-            }
-            cand |= ((keep0 ? 1u : 0u) << k) | ((keep1 ? 1u : 0u) << (k + 1));
+    if (PRIMARY && tileCand != nullptr) {
+        /* (wave-uniform.)  The table holds one block of spheres.  Nothing of the pre-test's per-ray set-up is needed here, and the ray terms
+         * of the exact loop (d.d and its reciprocal) only by the lanes whose tile holds a sphere at all: a wave over sky computes neither. */
+        const uint2 entry = reinterpret_cast<const uint2*>(tileCand)[tile]; /* (sphere mask, triangle mask) */
+        uint32_t cand = entry.x;
+        if (tw != nullptr) {
+            uint32_t want = 0u; /* (tiles of sky: one compare and done) */
+            for (unsigned long long more = __ballot(entry.y != 0u); more != 0ull; more = __ballot((entry.y & ~want) != 0u))
+                want |= (uint32_t)__builtin_amdgcn_readlane((int)entry.y, __builtin_ctzll(more));
+            tw->wave = want;
+            if (STATS) tw->lane = entry.y;
         }
-        if (ANY && h.dst < tmax) cand = 0;
-        while (cand) {
-            phase_mark<STATS>(st, PH_SPHERE_ROOTS);
-            const int k = __builtin_ctz(cand);
-            cand &= cand - 1;
-            const int s = base + k;
-            /* (PRIMARY: the record is (off, qc) already) */
-            float4 sp;
-            if (PRIMARY) {
-                typedef float rt_f4v __attribute__((ext_vector_type(4)));
-                const rt_f4v v = *reinterpret_cast<const RT_CAS rt_f4v*>(&pt->sph[s][0]);
-                sp = make_float4(v.x, v.y, v.z, v.w);
+        if (STATS) { /* audit: no sphere whose bit is clear may be accepted by the exact test */
+            const float qa = rt_dot(rdir, rdir);
+            for (uint32_t rest = ~cand & (a.nSpheres >= 32 ? 0xffffffffu : (1u << a.nSpheres) - 1u); rest; rest &= rest - 1) {
+                const int s = __builtin_ctz(rest);
+                const rt_f3 off = rt_v3(pt->sph[s][0], pt->sph[s][1], pt->sph[s][2]);
+                const float qb = 2 * rt_dot(off, rdir);
+                const float disc = qb * qb - 4 * qa * pt->sph[s][3];
+                if (disc >= 0 && (-qb + rt_sqrt(disc)) * rt_rcp(2 * qa) >= 0) st.filterViolations++;
             }
-            else sp = *reinterpret_cast<const float4*>(a.spheres + 4 * s);
-            rt_f3 off = PRIMARY ? rt_v3(sp.x, sp.y, sp.z) : rpos - rt_v3(sp.x, sp.y, sp.z);
-            float qb = 2 * rt_dot(off, rdir);
-            float qc = PRIMARY ? sp.w : rt_dot(off, off) - sp.w;
-            float disc = qb * qb - 4 * qa * qc;
-            if (!(disc >= 0)) continue; /* RC:304: a false positive of phase 1 ends here */
-            float sq = rt_sqrt(disc);
-            const float inv2a = rt_rcp(2 * qa); /* both roots share the reciprocal (rt_div) */
-            float dstNear = rt_max(0.0f, (-qb - sq) * inv2a);
-            float dstFar = (-qb + sq) * inv2a;
-            if (dstFar >= 0) {
-                bool inside = dstNear == 0;
-                float d = inside ? dstFar : dstNear;
-                if (d < h.dst) {
-                    h.dst = d;
-                    h.obj = s;
-                    h.backface = inside;
-                    if (ANY && d < tmax) cand = 0;
+        }
+        if (cand != 0u) { /* the exact loop of the other branch on the table's (off, qc) records: the same operations in the same order */
+            const float qa = rt_dot(rdir, rdir);
+            const float inv2a = rt_rcp(2 * qa);
+            do {
+                phase_mark<STATS>(st, PH_SPHERE_ROOTS);
+                const int s = __builtin_ctz(cand);
+                cand &= cand - 1;
+                typedef float rt_f4v __attribute__((ext_vector_type(4)));
+                const rt_f4v sp = *reinterpret_cast<const RT_CAS rt_f4v*>(&pt->sph[s][0]);
+                const rt_f3 off = rt_v3(sp.x, sp.y, sp.z);
+                const float qb = 2 * rt_dot(off, rdir);
+                const float disc = qb * qb - 4 * qa * sp.w;
+                if (!(disc >= 0)) continue;
+                const float sq = rt_sqrt(disc);
+                const float dstNear = rt_max(0.0f, (-qb - sq) * inv2a);
+                const float dstFar = (-qb + sq) * inv2a;
+                if (dstFar >= 0) {
+                    const bool inside = dstNear == 0;
+                    const float d = inside ? dstFar : dstNear;
+                    if (d < h.dst) {
+                        h.dst = d;
+                        h.obj = s;
+                        h.backface = inside;
+                    }
+                }
+            } while (cand != 0u);
+        }
+    } else {
+        const RT_CAS float* sph = (const RT_CAS float*)a.spheres;
+        const RT_CAS float* sphq = (const RT_CAS float*)a.sphereQuick;
+        const float qa = rt_dot(rdir, rdir);
+        const float od = __builtin_fmaf(rpos.x, rdir.x, __builtin_fmaf(rpos.y, rdir.y, rpos.z * rdir.z));
+        const float oo = PRIMARY ? 0.0f : __builtin_fmaf(rpos.x, rpos.x, __builtin_fmaf(rpos.y, rpos.y, rpos.z * rpos.z));
+        const float negMargin = -(7.62939453125e-06f * qa * (PRIMARY ? pt->ooBound : oo + a.sphereBound)); /* 2^-17 */
+        /* Two spheres per step, side by side in packed fp32 instructions: the sphere data sits in SGPRs, and on gfx950 a VALU
+         * instruction with an SGPR source issues at the slow rate (4.5 cycles against 2.9, profiles/r03_valu_op_rates.txt) while
+         * v_pk_fma/mul/add_f32 take an SGPR pair at no extra cost (5.0 cycles for both halves) — the same operations on the same
+         * values per sphere, so the candidate masks do not change. */
+        typedef float rt_f2v __attribute__((ext_vector_type(2)));
+        const rt_f2v dx2 = {rdir.x, rdir.x}, dy2 = {rdir.y, rdir.y}, dz2 = {rdir.z, rdir.z};
+        const rt_f2v ox2 = {rpos.x, rpos.x}, oy2 = {rpos.y, rpos.y}, oz2 = {rpos.z, rpos.z};
+        const rt_f2v od2 = {od, od}, oo2 = {oo, oo}, qa2 = {qa, qa}, m2 = {-2.0f, -2.0f};
+        for (int base = 0; base < a.nSpheres; base += 32) {
+            const int n = (a.nSpheres - base) < 32 ? (a.nSpheres - base) : 32;
+            uint32_t cand = 0;
+            for (int k = 0; k < n; k += 2) {
+                const RT_CAS float* q = PRIMARY ? &pt->pair[0][0] + 4 * (base + k) : sphq + 4 * (base + k); /* pair record (base + k) / 2, eight floats each */
+                const rt_f2v cx = {q[0], q[1]}, cy = {q[2], q[3]}, cz = {q[4], q[5]}, kk = {q[6], q[7]}; /* (PRIMARY: the last two are ct itself) */
+                const rt_f2v cd = __builtin_elementwise_fma(cx, dx2, __builtin_elementwise_fma(cy, dy2, cz * dz2));
+                const rt_f2v b = od2 - cd;
+                rt_f2v ct = kk;
+                if (!PRIMARY) {
+                    const rt_f2v co = __builtin_elementwise_fma(cx, ox2, __builtin_elementwise_fma(cy, oy2, cz * oz2));
+                    ct = __builtin_elementwise_fma(m2, co, oo2) + kk;
+                }
+                const rt_f2v dq = __builtin_elementwise_fma(b, b, -(qa2 * ct));
+                const bool keep0 = !(dq.x < negMargin);
+                const bool keep1 = (k + 1 < n) && !(dq.y < negMargin);
+                if (STATS) { /* audit against the reference's discriminant */
+                    for (int j = 0; j < 2 && k + j < n; j++) {
+                        const int s = base + k + j;
+                        rt_f3 off = rpos - rt_v3(sph[4 * s + 0], sph[4 * s + 1], sph[4 * s + 2]);
+                        float qb = 2 * rt_dot(off, rdir);
+                        float qc = rt_dot(off, off) - sph[4 * s + 3];
+                        float disc = qb * qb - 4 * qa * qc;
+                        if (disc >= 0 && !(j ? keep1 : keep0)) st.filterViolations++;
+                    }
+                }
+                cand |= ((keep0 ? 1u : 0u) << k) | ((keep1 ? 1u : 0u) << (k + 1));
+            }
+            if (ANY && h.dst < tmax) cand = 0;
+            while (cand) {
+                phase_mark<STATS>(st, PH_SPHERE_ROOTS);
+                const int k = __builtin_ctz(cand);
+                cand &= cand - 1;
+                const int s = base + k;
+                /* (PRIMARY: the record is (off, qc) already) */
+                float4 sp;
+                if (PRIMARY) {
+                    typedef float rt_f4v __attribute__((ext_vector_type(4)));
+                    const rt_f4v v = *reinterpret_cast<const RT_CAS rt_f4v*>(&pt->sph[s][0]);
+                    sp = make_float4(v.x, v.y, v.z, v.w);
+                }
+                else sp = *reinterpret_cast<const float4*>(a.spheres + 4 * s);
+                rt_f3 off = PRIMARY ? rt_v3(sp.x, sp.y, sp.z) : rpos - rt_v3(sp.x, sp.y, sp.z);
+                float qb = 2 * rt_dot(off, rdir);
+                float qc = PRIMARY ? sp.w : rt_dot(off, off) - sp.w;
+                float disc = qb * qb - 4 * qa * qc;
+                if (!(disc >= 0)) continue; /* RC:304: a false positive of phase 1 ends here */
+                float sq = rt_sqrt(disc);
+                const float inv2a = rt_rcp(2 * qa); /* both roots share the reciprocal (rt_div) */
+                float dstNear = rt_max(0.0f, (-qb - sq) * inv2a);
+                float dstFar = (-qb + sq) * inv2a;
+                if (dstFar >= 0) {
+                    bool inside = dstNear == 0;
+                    float d = inside ? dstFar : dstNear;
+                    if (d < h.dst) {
+                        h.dst = d;
+                        h.obj = s;
+                        h.backface = inside;
+                        if (ANY && d < tmax) cand = 0;
+                    }
                 }
             }
         }
@@ -741,12 +788,19 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
  * all of its lanes (a vote: the loop stays wave-uniform). */
 /* PRIMARY (begin_intersect): the origin in each model's space and the per-triangle terms of tri_test come from the table, whose
  * triangle records lie in the order this loop meets them (the host decodes the root leaves the same way, within the table's caps). */
+/* triWant / triLane (PRIMARY; TriWant of begin_intersect): a triangle no active lane's tile mask holds is not tested — no lane's ray can be
+ * accepted by it, so h does not change — and a model none of whose triangles is wanted is left before its direction is transformed (the
+ * caller does not come here at all when no triangle of any model is wanted).  The loop stays wave-uniform, the counters count as before,
+ * and the stats build puts every triangle a LANE's mask dropped through the exact test on a scratch hit: an acceptance is a filter
+ * violation. */
 template <bool STATS, bool ANY = false, bool PRIMARY = false>
-__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st, const float tmax = 0.0f, const RT_CAS PrimaryTable* pt = nullptr)
+__device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 rdir, SceneHit& h, Stats& st, const float tmax = 0.0f, const RT_CAS PrimaryTable* pt = nullptr,
+                                              const uint32_t triWant = 0xffffffffu, const uint32_t triLane = 0xffffffffu)
 {
     const RT_CAS DModel* cm = (const RT_CAS DModel*)a.models;
     const DTri* __restrict__ tris = a.tris;
     const RT_CAS float* pr = PRIMARY ? &pt->tri[0][0] : nullptr; /* the next triangle's record */
+    uint32_t tk = 0u;                                            /* ... and its index in the table's order (PRIMARY) */
     for (int m = 0; m < a.nModels; m++) {
         if (ANY && __ballot(!(h.dst < tmax)) == 0ull) break;
         const RT_CAS DModel& M = cm[m];
@@ -755,9 +809,13 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
         else lpos = rt_v3(M.w2l[0] * rpos.x + M.w2l[1] * rpos.y + M.w2l[2] * rpos.z + M.w2l[3] * 1.0f,
                           M.w2l[4] * rpos.x + M.w2l[5] * rpos.y + M.w2l[6] * rpos.z + M.w2l[7] * 1.0f,
                           M.w2l[8] * rpos.x + M.w2l[9] * rpos.y + M.w2l[10] * rpos.z + M.w2l[11] * 1.0f);
-        rt_f3 ldir = rt_v3(M.w2l[0] * rdir.x + M.w2l[1] * rdir.y + M.w2l[2] * rdir.z + M.w2l[3] * 0.0f,
-                           M.w2l[4] * rdir.x + M.w2l[5] * rdir.y + M.w2l[6] * rdir.z + M.w2l[7] * 0.0f,
-                           M.w2l[8] * rdir.x + M.w2l[9] * rdir.y + M.w2l[10] * rdir.z + M.w2l[11] * 0.0f);
+        auto local_dir = [&]() {
+            return rt_v3(M.w2l[0] * rdir.x + M.w2l[1] * rdir.y + M.w2l[2] * rdir.z + M.w2l[3] * 0.0f,
+                         M.w2l[4] * rdir.x + M.w2l[5] * rdir.y + M.w2l[6] * rdir.z + M.w2l[7] * 0.0f,
+                         M.w2l[8] * rdir.x + M.w2l[9] * rdir.y + M.w2l[10] * rdir.z + M.w2l[11] * 0.0f);
+        };
+        rt_f3 ldir;
+        if (!PRIMARY) ldir = local_dir();
         const uint32_t code = M.rootCode;
         uint32_t count = (code >> 24) & 0x7fu;
         uint32_t start = code & RT_CODE_MAX_INLINE_START;
@@ -766,9 +824,31 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
             start = a.bigLeaves[2 * start];
         }
         if (STATS) { st.leaf++; st.tri += count; }
+        uint32_t wantM = 0xffffffffu; /* bit i: triangle i of this model's root leaf is wanted */
+        if (PRIMARY) {
+            wantM = (triWant >> tk) & ((1u << count) - 1u); /* (the table is on: at most RT_PRIMARY_MAX_TRIS in all) */
+            if (!STATS && wantM == 0u) { /* (the stats build goes on: it audits triangle by triangle) */
+                tk += count;
+                pr += 4 * count;
+                continue;
+            }
+            ldir = local_dir();
+        }
         const int first = M.triBase + (int)start;
         const bool cull = M.cullBackface != 0;
         for (uint32_t i = 0; i < count; i++) {
+            if (PRIMARY) {
+                if (STATS && !((triLane >> (tk + i)) & 1u)) { /* audit: this lane's tile dropped the triangle */
+                    float best = RT_INF, bu, bv, bdet;
+                    int btri = -1;
+                    tri_test<PRIMARY>(tris, first + 3 * (int)i, lpos, ldir, cull, best, btri, bu, bv, bdet, pr);
+                    if (btri >= 0) st.filterViolations++;
+                }
+                if (!((wantM >> i) & 1u)) {
+                    pr += 4;
+                    continue;
+                }
+            }
             phase_mark<STATS>(st, PH_TRI);
             if (ANY && h.dst < tmax) break;
             const float before = h.dst;
@@ -779,6 +859,7 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
                 h.backface = h.det < 0;
             }
         }
+        if (PRIMARY) tk += count;
     }
 }
 
@@ -1335,8 +1416,10 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
                         /* (the lane's tile: the fourth word of its record, written at set-up for the tile cost; it travels with the chain) */
                         const uint32_t* const tileCand = cold_args().tileCand;
                         const uint32_t tile = tileCand ? __float_as_uint(PX_COLD(cold_args())[RT_WAVE].w) : 0u;
-                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt, tileCand, tile);
-                        traverse_flat<STATS, false, true>(a, rpos, rdir, h, st, 0.0f, pt);
+                        TriWant tw = {0xffffffffu, 0xffffffffu}; /* (no table: every triangle) */
+                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt, tileCand, tile, &tw);
+                        if (STATS || tw.wave != 0u) /* (no lane's tile meets a triangle: sky; the stats build goes in to count and audit) */
+                            traverse_flat<STATS, false, true>(a, rpos, rdir, h, st, 0.0f, pt, tw.wave, tw.lane);
                     } else {
                         begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
                         traverse_flat<STATS>(a, rpos, rdir, h, st);
@@ -1774,16 +1857,18 @@ __global__ void __launch_bounds__(1024) rt_order_kernel(const uint32_t* cost, ui
     for (int i = t; i < nTiles; i += 1024) order[atomicAdd(&base[key[i]], 1u)] = (uint32_t)i;
 }
 
-/* The per-tile sphere candidates of the FLAT trace kernel's all-camera-ray waves (rt_tile_cand.h): one thread per tile of this context,
- * out[tile] = the tile's mask.  Launched in front of a trace kernel, on its stream, only when that stream's table was made from another
- * key (another camera, image, partition, diverge or set of spheres). */
+/* The per-tile sphere and triangle candidates of the FLAT trace kernel's all-camera-ray waves (rt_tile_cand.h): one thread per tile of this
+ * context, out[2 tile] = the tile's sphere mask, out[2 tile + 1] = its triangle mask (one 8-byte load in the reader).  Launched in front
+ * of a trace kernel, on its stream, only when that stream's table was made from another key (another camera, image, partition, diverge,
+ * set of spheres, model matrices or root-leaf triangles). */
 __global__ void __launch_bounds__(256) rt_tile_cand_kernel(const TileCandKey k, uint32_t* out)
 {
     const int tile = (int)(blockIdx.x * 256u + threadIdx.x);
     if (tile >= k.tiles) return;
     int x0, y0;
     tile_cand_origin(k, tile, &x0, &y0);
-    out[tile] = tile_cand_mask(k, x0, y0);
+    out[2 * tile] = tile_cand_mask(k, x0, y0);
+    out[2 * tile + 1] = k.triOn ? tile_tri_mask(k, x0, y0) : 0xffffffffu; /* (the triangle half off: every triangle is wanted) */
 }
 
 /* Display pass — Display.shader:42-47: col = tex / Frame (the blit of RayTraceDisplay.cs:9-23).

@@ -46,6 +46,8 @@ struct PrimaryTris {
     int count[RT_PRIMARY_MAX_MODELS] = {0, 0, 0, 0};
     float a[RT_PRIMARY_MAX_TRIS][3];
     float face[RT_PRIMARY_MAX_TRIS][3];
+    float ab[RT_PRIMARY_MAX_TRIS][3];   /* edgeAB and edgeAC of the same records: what the per-tile triangle masks need besides (rt_tile_cand.h) */
+    float ac[RT_PRIMARY_MAX_TRIS][3];
 };
 
 static inline void primary_collect_tris(bool flat, const DModel* models, int nModels, const unsigned char* triSpace, size_t triSpaceBytes,
@@ -71,6 +73,8 @@ static inline void primary_collect_tris(bool flat, const DModel* models, int nMo
             memcpy(&t, triSpace + (size_t)unit * 16, sizeof(t));
             out.a[total][0] = t.ax; out.a[total][1] = t.ay; out.a[total][2] = t.az;
             out.face[total][0] = t.fx; out.face[total][1] = t.fy; out.face[total][2] = t.fz;
+            out.ab[total][0] = t.abx; out.ab[total][1] = t.aby; out.ab[total][2] = t.abz;
+            out.ac[total][0] = t.acx; out.ac[total][1] = t.acy; out.ac[total][2] = t.acz;
             total++;
         }
         out.count[m] = (int)count;

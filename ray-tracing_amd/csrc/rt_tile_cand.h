@@ -26,6 +26,25 @@
  *      (|a| <= Rt: sin(alpha) >= 1), alpha + beta near 90 degrees or beyond (sin^2(alpha) + sin^2(beta) >= 0.98), any value that is not
  *      finite.  The angles are compared through the cross product (sines), which keeps its relative accuracy for small angles.
  * tests/tile_cand_driver.cpp is the proof by exhaustion: the kernel's own raygen formulas, the exact test, 0 misses.
+ *
+ * The per-tile TRIANGLE candidates (tile_tri_mask; FLAT scenes within the caps of rt_primary.h): one bit per root-leaf triangle, in the
+ * order traverse_flat meets them.  A bit may be clear only when no camera ray of the tile can satisfy dst > 0 && u >= 0 && v >= 0 && w >= 0
+ * in tri_test's own arithmetic (the keep / cull condition is ignored: that keeps more).  With the table's p = lpos - A and e = dot(p, face),
+ * and for a local direction d, tri_test forms det = -d.face, U = d.(AC x p), V = d.(p x AB) and accepts only if e / det > 0, U / det >= 0,
+ * V / det >= 0 and 1 - U / det - V / det >= 0.  With s = sign(e) that needs s det > 0, s U >= 0, s V >= 0 and s (det - U - V) >= 0: four
+ * functions LINEAR in d, taken from the very records the kernel reads (w2l, the table's lpos, A, edgeAB, edgeAC and the stored face — not
+ * l2w, not a recomputed normal, no assumption on winding or on the sign of w2l's determinant).
+ *   Every unnormalised direction o -> target of the tile is R s + U t + F vz with (s, t) in a rectangle: 4 pixels to either side of the
+ *   tile's centre plus the jitter bound, as above.  It is a convex combination of the rectangle's four corners g_j, w2l's 3 x 3 part is
+ *   linear and normalising scales by a positive number, so a function that is negative at all four corners is negative for every ray.
+ * Why this is conservative in fp32:
+ *   1. A function counts as negative only below -2^-14 N |w2l| (|o| + max |g_j|), N = (|lpos| + |A|) |edge| resp. |face| resp. their sum
+ *      bounding the normal: the rounding of the raygen, of w2l x d and of tri_test's products is 2^-24 per operation relative to the
+ *      COORDINATES (|o| + |target|, |lpos| + |A|), a thousand times less.
+ *   2. Everything that is not clearly inside these assumptions keeps the triangle: W or H of 1, any value that is not finite, lengths
+ *      outside 2^-16 ... 2^16 (no product may leave fp32's normal range), e within the margin of 0 (lpos in the plane or on a vertex),
+ *      a normal within the margin of 0 (lpos on an edge line, a degenerate triangle), corners on both sides of a plane.
+ * tests/tile_tri_driver.cpp is the proof by exhaustion, as for the spheres.
  */
 #ifndef RT_TILE_CAND_H
 #define RT_TILE_CAND_H
@@ -36,6 +55,8 @@
 #include "../../include/rt_math.h"
 
 #define RT_TILE_CAND_MAX_SPHERES 32 /* one mask word = one 32-sphere block of begin_intersect (== RT_PRIMARY_MAX_SPHERES) */
+#define RT_TILE_TRI_MAX_MODELS 4    /* == RT_PRIMARY_MAX_MODELS */
+#define RT_TILE_TRI_MAX_TRIS 16     /* == RT_PRIMARY_MAX_TRIS */
 
 /* What the masks of a context's tiles depend on, and nothing else: the argument block of the fill kernel, passed by value, and at the
  * same time the KEY of a filled table (compared bytewise: make it with tile_cand_key_init, which clears the padding).  The camera fields
@@ -50,6 +71,13 @@ struct TileCandKey {
     int32_t stripRows, partIndex, partCount;    /* local tile row -> global row, as RT_SET_POOL of trace_body */
     int32_t nSpheres;
     float sph[RT_TILE_CAND_MAX_SPHERES][4];
+    /* the triangle half (tile_tri_mask); triOn = 0: not in use, the fill kernel writes all ones */
+    int32_t triOn;
+    int32_t nTriModels;
+    int32_t triCount[RT_TILE_TRI_MAX_MODELS];   /* root-leaf triangles per model, as primary_collect_tris decodes them */
+    float w2l[RT_TILE_TRI_MAX_MODELS][12];      /* DModel::w2l: what traverse_flat multiplies the direction with */
+    float lpos[RT_TILE_TRI_MAX_MODELS][4];      /* PrimaryTable::lpos */
+    float tri[RT_TILE_TRI_MAX_TRIS][12];        /* (A, edgeAB, edgeAC, face) of the laid-out record, local space, in traverse_flat's order */
 };
 
 static inline void tile_cand_key_init(TileCandKey& k) { memset(&k, 0, sizeof(k)); }
@@ -109,6 +137,78 @@ RT_HD uint32_t tile_cand_mask(const TileCandKey& k, int x0, int y0)
         if (!drop) mask |= 1u << s;
     }
     return mask;
+}
+
+/* Bit i set: the i-th root-leaf triangle traverse_flat meets may be accepted by a camera ray of a pixel of the tile at (x0, y0). */
+RT_HD uint32_t tile_tri_mask(const TileCandKey& k, int x0, int y0)
+{
+    const int nm = k.nTriModels < RT_TILE_TRI_MAX_MODELS ? k.nTriModels : RT_TILE_TRI_MAX_MODELS;
+    int n = 0;
+    for (int m = 0; m < nm; m++) n += k.triCount[m] > 0 ? k.triCount[m] : 0;
+    if (n > RT_TILE_TRI_MAX_TRIS) n = RT_TILE_TRI_MAX_TRIS;
+    const uint32_t all = (1u << n) - 1u;
+    if (k.W <= 1 || k.H <= 1) return all;
+    const float eps = 6.103515625e-05f; /* 2^-14 */
+    const float lo = 1.52587890625e-05f, hi = 65536.0f; /* 2^-16, 2^16 */
+    const rt_f3 o = rt_v3(k.camOrigin[0], k.camOrigin[1], k.camOrigin[2]);
+    const rt_f3 R = rt_v3(k.cam[0], k.cam[1], k.cam[2]), U = rt_v3(k.cam[4], k.cam[5], k.cam[6]), F = rt_v3(k.cam[8], k.cam[9], k.cam[10]);
+    const float fx = (((float)x0 + 3.5f) * k.rcpWm1 - 0.5f) * k.viewParams[0];
+    const float fy = (((float)y0 + 3.5f) * k.rcpHm1 - 0.5f) * k.viewParams[1];
+    const float jit = 1.01f * rt_abs(k.diverge * k.rcpW);
+    const float ex = 4.0f * rt_abs(k.rcpWm1 * k.viewParams[0]) + jit, ey = 4.0f * rt_abs(k.rcpHm1 * k.viewParams[1]) + jit;
+    rt_f3 g[4];
+    float gmax = 0.0f;
+    for (int j = 0; j < 4; j++) {
+        g[j] = F * k.viewParams[2] + R * ((j & 1) ? fx + ex : fx - ex) + U * ((j & 2) ? fy + ey : fy - ey);
+        const float len = rt_sqrt(rt_dot(g[j], g[j]));
+        if (!tile_cand_finite(len)) return all;
+        gmax = rt_max(gmax, len);
+    }
+    const float lenO = rt_sqrt(rt_dot(o, o));
+    if (!(tile_cand_finite(lenO) && lenO <= hi && gmax >= lo && gmax <= hi)) return all;
+    uint32_t mask = 0;
+    int t = 0;
+    for (int m = 0; m < nm; m++) {
+        const float* w = k.w2l[m];
+        const float wn = rt_abs(w[0]) + rt_abs(w[1]) + rt_abs(w[2]) + rt_abs(w[4]) + rt_abs(w[5]) + rt_abs(w[6]) + rt_abs(w[8]) + rt_abs(w[9]) + rt_abs(w[10]);
+        rt_f3 c[4];
+        for (int j = 0; j < 4; j++)
+            c[j] = rt_v3(w[0] * g[j].x + w[1] * g[j].y + w[2] * g[j].z, w[4] * g[j].x + w[5] * g[j].y + w[6] * g[j].z, w[8] * g[j].x + w[9] * g[j].y + w[10] * g[j].z);
+        const float dirScale = wn * (lenO + gmax); /* bounds |w2l x (o -> target)| and the coordinates its rounding is relative to */
+        const rt_f3 lpos = rt_v3(k.lpos[m][0], k.lpos[m][1], k.lpos[m][2]);
+        const float lenL = rt_sqrt(rt_dot(lpos, lpos));
+        const bool modelOk = wn >= lo && wn <= hi && tile_cand_finite(lenL);
+        for (int i = 0; i < k.triCount[m] && t < n; i++, t++) {
+            const float* q = k.tri[t];
+            const rt_f3 A = rt_v3(q[0], q[1], q[2]), AB = rt_v3(q[3], q[4], q[5]), AC = rt_v3(q[6], q[7], q[8]), face = rt_v3(q[9], q[10], q[11]);
+            const rt_f3 p = lpos - A; /* tri_test's vertRayOffset, as primary_fill forms it */
+            const float e = rt_dot(p, face);
+            const float lenP = lenL + rt_sqrt(rt_dot(A, A));
+            const float nab = rt_sqrt(rt_dot(AB, AB)), nac = rt_sqrt(rt_dot(AC, AC)), nf = rt_sqrt(rt_dot(face, face));
+            const float NU = lenP * nac, NV = lenP * nab, ND = nf, NW = ND + NU + NV;
+            bool drop = false;
+            if (modelOk && lenP >= lo && lenP <= hi && nab >= lo && nab <= hi && nac >= lo && nac <= hi && nf >= lo * lo && nf <= hi * hi &&
+                tile_cand_finite(e) && rt_abs(e) > eps * lenP * nf) {
+                const float s = e > 0.0f ? 1.0f : -1.0f;
+                const rt_f3 nD = face * (-s), nU = rt_cross(AC, p) * s, nV = rt_cross(p, AB) * s, nW = nD - nU - nV;
+                const rt_f3 nrm[4] = {nD, nU, nV, nW};
+                const float bound[4] = {ND, NU, NV, NW};
+                bool sound = true;
+                for (int f = 0; f < 4; f++) { /* a normal within the margin of zero: lpos on an edge line, a degenerate triangle */
+                    const float l2 = rt_dot(nrm[f], nrm[f]), z = eps * bound[f];
+                    sound = sound && tile_cand_finite(l2) && l2 > z * z;
+                }
+                for (int f = 0; f < 4 && sound && !drop; f++) {
+                    const float margin = eps * bound[f] * dirScale;
+                    bool out = tile_cand_finite(margin);
+                    for (int j = 0; j < 4; j++) out = out && rt_dot(nrm[f], c[j]) < -margin; /* (false for NaN) */
+                    drop = out;
+                }
+            }
+            if (!drop) mask |= 1u << t;
+        }
+    }
+    return mask | (all & ~((t >= 32 ? 0u : (1u << t)) - 1u)); /* (triangles the loop did not reach stay set) */
 }
 
 #endif

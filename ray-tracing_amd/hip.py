@@ -35,6 +35,8 @@ COST_SYMBOLS = ["rt_render_cost"]
 PRIMARY_SYMBOLS = ["rt_debug_primary_table"]
 # include/rt_tile_cand.h
 TILE_CAND_SYMBOLS = ["rt_debug_tile_cand"]
+# include/rt_tile_tri.h (which include/rt_tile_cand.h includes)
+TILE_TRI_SYMBOLS = ["rt_debug_tile_tri"]
 # every symbol include/rt_aov.h declares
 AOV_SYMBOLS = ["rt_render_aov", "rt_render_aov_to_device"]
 # every symbol include/rt_denoise.h declares
@@ -535,6 +537,12 @@ class HipTracer(abi.Tracer):
     def tile_cand(self):
         """rt_debug_tile_cand: 1 / 0 = the last trace launch read / did not read the per-tile table of sphere candidates, -1 = no launch yet"""
         fn = self.api.lib.rt_debug_tile_cand  # bound on first use, like primary_table
+        fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
+        return fn(self.h)
+
+    def tile_tri(self):
+        """rt_debug_tile_tri: 1 / 0 = the table the last trace launch read held / did not hold per-tile triangle masks, -1 = no launch yet"""
+        fn = self.api.lib.rt_debug_tile_tri  # bound on first use, like primary_table
         fn.restype, fn.argtypes = C.c_int, [C.c_void_p]
         return fn(self.h)
 

@@ -1,0 +1,166 @@
+"""The per-tile triangle candidates (tile_tri_mask of ray-tracing_amd/csrc/rt_tile_cand.h) on their own, without a device and without the kernels.
+
+tests/tile_tri_driver.cpp is built against the header with the host compiler, twice: plainly (-O2 -Wall -Wextra -Werror) and with the
+address and undefined-behaviour sanitizers, as a stand-alone executable with the runtimes linked into it (nothing sanitized is loaded into
+python; a report ends the program with a non-zero exit, which fails the test).  Both are built without contraction, the arithmetic
+contract of include/rt_math.h.
+
+What the driver checks: for every tile it visits, every camera ray built with the kernel's own raygen formulas — all 64 pixels clipped at
+W / H, the jitter at the centre, at 16 points of the unit circle and at 16 random interior points — goes through traverse_flat's transform
+and tri_test's PRIMARY form in the kernel's operation order, and every triangle that ACCEPTS a ray must have its bit in the tile's mask:
+0 misses.  Cases: seeded random cameras with 1 ... 4 models and up to 16 triangles (every fourth case 4 models with 16 triangles) — rotated,
+non-uniformly scaled and mirrored models, triangles across the frustum's edges, behind the camera, degenerate ones, the camera in a
+triangle's plane and on a vertex, cull on and off — at 37x23 and 96x54 over every tile, whole images and the 2-of-3 strip partition,
+diverge 0 / 1.5 / 50; and config 2's camera and ground quad (horizon, diagonal and far edge cross tiles) at 96x54, 37x23, as partition
+1 of 3 and at 1920x1080 (every 50th tile plus all edge tiles), also with the quad small, rotated, non-uniformly and mirror scaled, with
+culling off, and with the camera under the ground.
+
+Selectivity keeps a mask of all ones from passing: on config 2 at 1920x1080 the mean number of bits of the mask may exceed the mean number
+of triangles the tile's sampled rays were really accepted by (a function of the scene alone, and a lower bound of what any correct mask
+holds) by at most 0.15 — the sphere masks sit 0.015 above theirs — and that bound lies far below the 2 bits of an all-ones mask.  The
+same run is the measurement the kernel path rests on: at least a quarter of the headline image's tiles must get an empty mask."""
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cxx():
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if not cxx:
+        pytest.fail("no host C++ compiler")
+    return cxx
+
+
+@pytest.fixture(scope="module")
+def drivers(tmp_path_factory):
+    d = tmp_path_factory.mktemp("tile_tri")
+    src = os.path.join(ROOT, "tests", "tile_tri_driver.cpp")
+    plain, san = str(d / "driver"), str(d / "driver_san")
+    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
+    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-static-libasan", "-static-libubsan", src, "-o", san])
+    return {"plain": plain, "san": san, "dir": d}
+
+
+def run(exe, *args):
+    env = {k: v for k, v in os.environ.items() if not k.startswith("RT_")}
+    p = subprocess.run([exe] + [str(a) for a in args], capture_output=True, env=env, timeout=600)
+    out = p.stdout.decode(errors="replace")
+    assert p.returncode == 0, (p.returncode, out[-3000:], p.stderr.decode(errors="replace")[-3000:])
+    last = out.strip().splitlines()[-1]
+    assert last.startswith("ok ") and " misses=0 " in last + " ", out[-3000:]
+    return {k: float(v) for k, v in re.findall(r"(\w+)=([-0-9.e+]+)", last)}
+
+
+class _NoTracer:
+    """make_manager wants a tracer; params() never calls it"""
+
+    def __getattr__(self, name):
+        raise AssertionError(f"the tracer is not to be called ({name})")
+
+
+def scene_file(pkg, api, d, cfg, w, h, part=(8, 0, 1), change=None, tag=""):
+    """the camera block and the models' root leaves of a config as the manager hands them to the library, in the driver's text form:
+    per model the worldToLocal rows as pack_model lays them out, cull (RC:355), and the root leaf's triangles in the builder's order"""
+    sc = pkg.scenes.get(cfg)
+    if change:
+        change(sc)
+    mgr = sc.make_manager(_NoTracer(), api, w, h)
+    p = mgr.params()
+    assert p.defocusStrength == 0.0
+    data = mgr.CreateAllMeshData(mgr.models)
+    info, tris, nodes = data["meshInfo"], data["triangles"], data["nodes"]
+    lines = [f"{w} {h} {part[0]} {part[1]} {part[2]} {p.divergeStrength!r}",
+             " ".join(repr(float(v)) for v in p.camLocalToWorld),
+             " ".join(repr(float(v)) for v in p.viewParams),
+             str(len(mgr.models))]
+    for i, model in enumerate(mgr.models):
+        m = info[i]["worldToLocal"]
+        root = nodes[int(info[i]["nodeOffset"])]
+        n = int(root["triangleCount"])
+        assert n > 0, "the driver's scenes are FLAT: every model's root is a leaf"
+        lines.append(" ".join(repr(float(m[c * 4 + r])) for r in range(3) for c in range(4)))
+        lines.append(f"{int(model.material.flag != pkg.abi.MATERIAL_GLASS)} {n}")
+        first = int(info[i]["triOffset"]) + int(root["startIndex"])
+        for t in tris[first:first + n]:
+            lines.append(" ".join(repr(float(v)) for v in (*t["posA"], *t["posB"], *t["posC"])))
+    path = str(d / f"config{cfg}{tag}_{w}x{h}_{part[1]}of{part[2]}.txt")
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    return path
+
+
+@pytest.mark.parametrize("seed", [1, 2, 20261019])
+def test_no_accepted_triangle_is_missing_from_a_tile_mask(drivers, seed):
+    r = run(drivers["san"], "random", seed, 48)
+    assert r["cases"] == 48 and r["rays"] > 1e6
+
+
+def test_plain_build_agrees(drivers):
+    """-O2 without the sanitizers: the optimiser must not make the mask less conservative either"""
+    run(drivers["plain"], "random", 1, 48)
+
+
+@pytest.mark.parametrize("size,part", [((37, 23), (8, 0, 1)), ((96, 54), (8, 0, 1)), ((96, 54), (8, 1, 3))])
+def test_config2_small(pkg, api, drivers, size, part):
+    r = run(drivers["san"], "scene", scene_file(pkg, api, drivers["dir"], 2, *size, part), 1)
+    assert r["triangles"] == 2
+
+
+def _ground(pkg, **kw):
+    def change(sc):
+        t = sc.models[0].transform
+        sc.models[0].transform = type(t)(position=kw.get("position", (0, 0, 0)), euler=kw.get("euler", (90, 0, 0)), scale=kw.get("scale", (40, 40, 1)))
+        if kw.get("glass"):
+            sc.models[0].material.flag = pkg.abi.MATERIAL_GLASS   # RC:355: no backface culling
+        if "camera" in kw:
+            c = sc.camera.transform
+            sc.camera.transform = type(c)(position=kw["camera"][0], euler=kw["camera"][1])
+    return change
+
+
+VARIANTS = {
+    "small_quad_all_edges_in_view": dict(scale=(6, 9, 1), position=(0.5, 0, 1.0)),
+    "rotated_nonuniform": dict(scale=(30, 7, 1), euler=(84, 25, 10), position=(0.5, -0.25, 1.0)),
+    "mirrored": dict(scale=(-12, 8, 1), euler=(78, -30, 5)),
+    "cull_off": dict(scale=(10, 10, 1), glass=True),
+    "camera_under_the_ground": dict(camera=((0, -2.0, -8.8), (-12, 0, 0))),
+    "camera_under_the_ground_cull_off": dict(camera=((0, -2.0, -8.8), (-12, 0, 0)), glass=True),
+}
+
+
+@pytest.mark.parametrize("name", sorted(VARIANTS))
+def test_config2_ground_variants(pkg, api, drivers, name):
+    run(drivers["san"], "scene", scene_file(pkg, api, drivers["dir"], 2, 96, 54, change=_ground(pkg, **VARIANTS[name]), tag="_" + name), 1)
+
+
+def test_config2_full_size_and_selectivity(pkg, api, drivers):
+    """every 50th tile plus all edge tiles of the headline image: 0 misses; the mask is nearly as tight as the scene allows; and the premise
+    of the kernel path: at least a quarter of the tiles meet no triangle at all"""
+    r = run(drivers["plain"], "scene", scene_file(pkg, api, drivers["dir"], 2, 1920, 1080), 50)
+    print("config 2 at 1920x1080:", r)
+    assert r["tiles"] == 240 * 135 and r["triangles"] == 2
+    assert r["mean_brute"] + 0.15 < 1.0, "the bound leaves no room: an all-ones mask (2 bits) must be far above it"
+    assert r["mean_mask"] <= r["mean_brute"] + 0.15
+    assert r["share0"] >= 0.25
+
+
+def test_config2_full_size_partition(pkg, api, drivers):
+    run(drivers["plain"], "scene", scene_file(pkg, api, drivers["dir"], 2, 1920, 1080, (8, 1, 3)), 50)
+
+
+def test_public_header_symbol_is_exported(pkg, api):
+    """include/rt_tile_tri.h (included by include/rt_tile_cand.h) declares one call; hip.TILE_TRI_SYMBOLS mirrors it and the library exports it"""
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rt_tile_tri.h")).read(), flags=re.S)
+    names = sorted(set(re.findall(r"\b(rt_[a-z_0-9]+)\s*\(", text)))
+    assert names == sorted(pkg.hip.TILE_TRI_SYMBOLS) == ["rt_debug_tile_tri"]
+    assert not set(names) & (set(pkg.hip.ABI_SYMBOLS) | set(pkg.hip.TILE_CAND_SYMBOLS))
+    assert '#include "rt_tile_tri.h"' in open(os.path.join(ROOT, "include", "rt_tile_cand.h")).read()
+    for n in names:
+        assert hasattr(api.lib, n), f"libraytrace_hip.so does not export {n}"
+    assert api.lib.rt_debug_tile_tri(None) == pkg.abi.RT_ERR_INVALID_ARG
