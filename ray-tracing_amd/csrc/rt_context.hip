@@ -70,6 +70,19 @@ struct HipOrder final : rt_order::Backend {
     int accumulate(int s) override;
 };
 
+/* A side pass — a launch that traces outside the render launches, with a counter slot of its own (see "the side passes" above
+ * rt_render_aov).  The context has three, in the order rt_synchronize reports them.  words: the slot, RT_COUNTER_FIELDS words made on
+ * first use, of which the kernels write the watchdog word alone (the radiance pass also counts its blocks in word 0); unreported: a
+ * device-form pass whose watchdog word has not been read back yet; whose / what: the two places where the deferred report differs by
+ * pass. */
+struct SidePass {
+    unsigned long long* words;
+    bool unreported;
+    const char* whose;
+    const char* what;
+};
+enum { SIDE_AOV, SIDE_QUERY, SIDE_RADIANCE, SIDE_COUNT };
+
 struct RtContext {
     int device = 0;
     hipStream_t ownStream = nullptr;
@@ -209,28 +222,22 @@ struct RtContext {
     int lastLaunched = 0;            /* frames the last launch_frames call really enqueued (flush_pending rolls back the rest) */
     void* dDisplay = nullptr;  /* scratch of the display pass and of the other host reads, kept between calls (grows on demand) */
     size_t displayBytes = 0;
-    /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand); the pass's own counter
-     * slot (only its watchdog word is ever written); a device pass whose watchdog word has not been read back yet */
+    /* the side passes (SidePass, above): AOV, ray query, radiance */
+    SidePass side[SIDE_COUNT] = {
+        {nullptr, false, "the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call (or its centre / moving form)", "records or denoised image"},
+        {nullptr, false, "the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call", "records or answers"},
+        {nullptr, false, "the pass of an rt_radiance_trace_buffers call", "records"},
+    };
+    /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand) */
     void* dAovOut = nullptr;
     size_t aovOutBytes = 0;
-    unsigned long long* dAovWords = nullptr;
-    bool aovUnreported = false;
-    /* rt_query_* (include/rt_query.h): the host forms' device rays and results, kept between calls (grow on demand); the pass's own counter
-     * slot (only its watchdog word is ever written); a buffer-form pass whose watchdog word has not been read back yet */
-    void* dQueryRays = nullptr;
-    size_t queryRaysBytes = 0;
-    void* dQueryOut = nullptr;
-    size_t queryOutBytes = 0;
-    unsigned long long* dQueryWords = nullptr;
-    bool queryUnreported = false;
-    /* rt_radiance_* (include/rt_radiance.h): the same for the radiance pass — the host form's device rays and records, the pass's own
-     * counter slot (word 0: the block counter of the launch, word 7: its watchdog word), a buffer-form pass not yet reported */
-    void* dRadianceRays = nullptr;
-    size_t radianceRaysBytes = 0;
-    void* dRadianceOut = nullptr;
-    size_t radianceOutBytes = 0;
-    unsigned long long* dRadianceWords = nullptr;
-    bool radianceUnreported = false;
+    /* the host forms of rt_query_* and rt_radiance_trace: their device rays and results, kept between calls (grow on demand).  One pair
+     * for both: a host form synchronises before it returns and a buffer form uses the caller's memory, so nothing here is live across
+     * calls */
+    void* dRays = nullptr;
+    size_t raysBytes = 0;
+    void* dRayOut = nullptr;
+    size_t rayOutBytes = 0;
     /* rt_denoise (include/rt_denoise.h): the filter's two colour images and packed guide image, and the AOV records of the two context
      * calls' internal pass; kept between calls (grow on demand) */
     void* dDnScratch = nullptr;
@@ -314,6 +321,37 @@ static int check_watchdog(RtContext* ctx, RtContext* report, const char* call)
     return fired ? watchdog_failure(report, call, fired) : RT_OK;
 }
 
+/* ---- the watchdog word of a side pass (SidePass): read by the host forms when they return, handed over by the device forms --
+ * A device-form pass is reported exactly once, by whichever comes first: rt_synchronize, a host read behind it that says so (rt_resolve,
+ * rt_variance_read_moments), or the next call that runs the same pass — side_settle, before that call's own pass clears the word. */
+/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
+static int side_fired(RtContext* ctx, const SidePass& sp, unsigned long long* fired)
+{
+    *fired = 0;
+    HIP_TRY(ctx, hipMemcpy(fired, sp.words + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+/* After a synchronise of the stream: the report of a device-form pass that has not been reported yet */
+static int side_report(RtContext* ctx, SidePass& sp, const char* call)
+{
+    if (!sp.unreported) return RT_OK;
+    sp.unreported = false;
+    unsigned long long fired = 0;
+    if (int rc = side_fired(ctx, sp, &fired)) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in %s: "
+                           "walks were cut short, that call's %s are not valid (the context's images are not affected)", call, fired, sp.whose, sp.what);
+    return RT_OK;
+}
+
+/* a device-form pass still unreported: synchronise and report it before this call's own pass clears the word */
+static int side_settle(RtContext* ctx, SidePass& sp, const char* call)
+{
+    if (!sp.unreported) return RT_OK;
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    return side_report(ctx, sp, call);
+}
+
 static int local_rows_for(int H, int stripRows, int partIndex, int partCount)
 {
     int rows = 0;
@@ -384,6 +422,16 @@ static int check_rows_buffer(RtContext* ctx, const char* call, size_t perPixel, 
     if (bytes != want || (!p && (bytes || nullIsError)))
         return fail(ctx, RT_ERR_INVALID_ARG, "%s: need exactly %zu bytes (%d rows x %d x %zu), got %zu%s", call, want, ctx->localRows, ctx->W, perPixel, bytes,
                     p ? "" : " and a null pointer");
+    return RT_OK;
+}
+
+/* d_rgba of a *_to_device image call, `bytes` bytes: device memory that does not overlap `other` (named `otherName`; nullptr: no such
+ * test) — or, without bytes, a pointer that is aligned all the same */
+static int check_image_out(RtContext* ctx, const char* call, const void* d_rgba, size_t bytes, const void* other, const char* otherName)
+{
+    if (!bytes) return ((uintptr_t)d_rgba & 15) ? fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call) : RT_OK;
+    if (int rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes)) return rc;
+    if (other && ranges_overlap(d_rgba, bytes, other, bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps %s", call, otherName);
     return RT_OK;
 }
 
@@ -563,13 +611,9 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dTileCand[1]);
     hipFree(ctx->dDisplay);
     hipFree(ctx->dAovOut);
-    hipFree(ctx->dAovWords);
-    hipFree(ctx->dQueryRays);
-    hipFree(ctx->dQueryOut);
-    hipFree(ctx->dQueryWords);
-    hipFree(ctx->dRadianceRays);
-    hipFree(ctx->dRadianceOut);
-    hipFree(ctx->dRadianceWords);
+    hipFree(ctx->dRays);
+    hipFree(ctx->dRayOut);
+    for (SidePass& sp : ctx->side) hipFree(sp.words);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
@@ -1538,10 +1582,6 @@ static int launch_frames(RtContext* ctx, int frame0, int nFrames)
 
 extern "C" {
 
-static int aov_report(RtContext* ctx, const char* call);
-static int query_report(RtContext* ctx, const char* call);
-static int radiance_report(RtContext* ctx, const char* call);
-
 static int check_renderable(RtContext* ctx)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
@@ -1630,9 +1670,9 @@ int rt_synchronize(RtContext* ctx)
     RT_FLUSH(ctx);
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
-    if (int rc = aov_report(ctx, "rt_synchronize")) return rc; /* a device AOV pass completes here: so does its watchdog report (no-op otherwise) */
-    if (int rc = query_report(ctx, "rt_synchronize")) return rc; /* and that of a buffer-form ray query (include/rt_query.h) */
-    return radiance_report(ctx, "rt_synchronize"); /* and that of a buffer-form radiance pass (include/rt_radiance.h) */
+    for (SidePass& sp : ctx->side) /* a device-form side pass completes here: so does its watchdog report (no-op otherwise) */
+        if (int rc = side_report(ctx, sp, "rt_synchronize")) return rc;
+    return RT_OK;
 }
 
 int rt_get_frame(const RtContext* ctx) { return ctx ? ctx->frame : RT_ERR_INVALID_ARG; }
@@ -1861,10 +1901,10 @@ int rt_debug_math_eval(RtContext* ctx, int op, const float* x, const float* y, f
     return RT_OK;
 }
 
-/* ---- the passes that trace as single waves (rt_render_cost, the AOV pass): no top-of-tree cache, no chain pool --------------------
+/* ---- the passes that trace as single waves (rt_render_cost, the side passes): no top-of-tree cache, no chain pool ----------------
  * The KArgs fields of that form, the LDS attribute a wave region above 48 KB needs, and *residentWaves = every wave the device keeps
  * resident.  waveLdsBytes is the caller's: the cost kernel's FLAT form keeps its pixel records in LDS (rt_plan::launch_shape adds them),
- * the AOV kernel has none (rt_plan::wave_lds_bytes). */
+ * the side passes' kernels have none (rt_plan::wave_lds_bytes). */
 static int single_wave_pass(RtContext* ctx, const void* kern, size_t waveLdsBytes, KArgs& a, long long* residentWaves)
 {
     a.wavesPerGroup = 1;
@@ -1878,6 +1918,13 @@ static int single_wave_pass(RtContext* ctx, const void* kern, size_t waveLdsByte
     *residentWaves = (long long)(perCU > 0 ? perCU : 1) * ctx->numCUs;
     return RT_OK;
 }
+
+/* The instantiation of a single-wave kernel K<FLAT, MANY, ...> for the context's scene: MANY (more than 64 models), FLAT (every root a
+ * leaf) or the plain BVH form; further template arguments follow K */
+#define RT_SCENE_KERNEL(ctx, K, ...)                                                                      \
+    (rt_plan::many_models((ctx)->nChunks, (ctx)->flatScene) ? K<false, true, ##__VA_ARGS__>               \
+     : (ctx)->flatScene                                     ? K<true, false, ##__VA_ARGS__>               \
+                                                            : K<false, false, ##__VA_ARGS__>)
 
 /* ---- rt_render_cost (include/rt_cost.h): per-pixel work of one frame ----------------------
  * The stats build of the trace kernel in its single-wave, unpooled form without the top-of-tree cache (rt_kernels.h, rt_cost_kernel):
@@ -1906,7 +1953,7 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     sc.nChunks = ctx->nChunks;
     sc.numCUs = ctx->numCUs;
     const rt_plan::LaunchShape sh = rt_plan::launch_shape(sc, tiles, 1);
-    void (*kern)(const KArgs, uint32_t*) = sh.many ? rtk::rt_cost_kernel<false, true> : ctx->flatScene ? rtk::rt_cost_kernel<true, false> : rtk::rt_cost_kernel<false, false>;
+    void (*kern)(const KArgs, uint32_t*) = RT_SCENE_KERNEL(ctx, rtk::rt_cost_kernel); /* (sh.many is the same rt_plan::many_models) */
     a.suspendNum = ctx->tuner.decided; /* scheduling only: the counts of a ray do not depend on it */
     long long resident = 0;
     if ((rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), sh.ldsBytes, a, &resident))) return rc; /* (one wave per group: the group's LDS is the wave's) */
@@ -2207,28 +2254,20 @@ int rt_adaptive_render_frames(RtContext* ctx, int n)
     return RT_OK;
 }
 
-/* ---- rt_render_aov / rt_render_aov_to_device (include/rt_aov.h): what camera ray 0 of a frame finds, per pixel -------------
- * One launch of rt_aov_kernel (rt_kernels.h) on the joined main stream — behind every frame already requested, like every use of the
- * stream that is not a render launch.  The pass is the context's in nothing but the scene, the parameters and the stream: KArgs as for
- * frame `frame`, a counter slot of its own (ctx->dAovWords; traverse() only ever writes its watchdog word), no render target, no tile
- * queue, no pixel records.  So RtCounters and the context's watchdog word stay as they are, and a watchdog that fires here fails this
- * pass only.  frame == RT_AOV_CENTRE (0) selects the pixel-centre ray of include/rt_motion.h, which reads nothing of a frame: the KArgs
- * are then those of frame 1. */
-static int aov_enqueue(RtContext* ctx, int frame, void* dOut)
+/* ---- the side passes: the AOV pass, the ray queries and the radiance pass -------------------------------------------------------------
+ * Each is ONE launch of a single-wave kernel (rt_kernels.h) on the joined main stream — behind every frame already requested, like every
+ * use of the stream that is not a render launch.  A pass is the context's in nothing but the scene, the stream and, where it reads them,
+ * the parameters: KArgs from fill_args, the FLAT / MANY / BVH instantiation of its kernel (RT_SCENE_KERNEL), a wave region of the trace
+ * kernel as its LDS, and no render target, tile order, tile costs, pixel records or staging slab.  Its counter slot is its own
+ * (SidePass; traverse() only ever writes the slot's watchdog word), so RtCounters and the context's watchdog word stay as they
+ * are, and a watchdog that fires in a pass fails that pass only.  The protocol, once:
+ *     side_begin    the KArgs fields of that form, the slot (made on first use), LDS bytes and resident waves
+ *     side_submit   the slot cleared, the launch and its error, in stream order
+ *     side_fired / side_report / side_settle (above, with check_watchdog)   a host form reads the word when it returns; a device form
+ *                   sets `unreported` and the word is handed over as described there
+ * What each pass adds is stated at its enqueue function. */
+static int side_begin(RtContext* ctx, SidePass& sp, const void* kern, KArgs& a, size_t* ldsBytes, long long* residentWaves)
 {
-    const bool centre = frame == RT_AOV_CENTRE;
-    if (centre) frame = 1;
-    KArgs a;
-    fill_args(ctx, frame, 1, a);
-    const int tiles = a.tilesX * a.tilesY;
-    if (tiles == 0) return RT_OK;
-    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
-    void (*kern)(const KArgs, float4*, const uint32_t*) =
-        centre ? (many ? rtk::rt_aov_kernel<false, true, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false, true> : rtk::rt_aov_kernel<false, false, true>)
-               : (many ? rtk::rt_aov_kernel<false, true> : ctx->flatScene ? rtk::rt_aov_kernel<true, false> : rtk::rt_aov_kernel<false, false>);
-    /* a wave region of the trace kernel, single waves, no cache, no pool */
-    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
-    a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
     a.frameRender = nullptr;
     a.accumulated = nullptr;
     a.tileQueue = nullptr;
@@ -2236,36 +2275,45 @@ static int aov_enqueue(RtContext* ctx, int frame, void* dOut)
     a.tileCost = nullptr;
     a.pxCold = nullptr;
     a.staging = nullptr;
-    if (!ctx->dAovWords) HIP_TRY(ctx, hipMalloc(&ctx->dAovWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
-    a.counters = ctx->dAovWords;
-    long long grid = 0; /* every wave the device keeps resident; the tiles are strided over them */
-    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &grid)) return rc;
-    if (grid > tiles) grid = tiles;
+    if (!sp.words) HIP_TRY(ctx, hipMalloc(&sp.words, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
+    a.counters = sp.words;
+    *ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords); /* a wave region of the trace kernel, single waves, no cache, no pool */
+    return single_wave_pass(ctx, kern, *ldsBytes, a, residentWaves);
+}
+
+} /* extern "C" */
+
+/* `grid` single-wave workgroups of `kern`(a, args...) */
+template <class Kern, class... Args>
+static int side_submit(RtContext* ctx, SidePass& sp, Kern kern, long long grid, size_t ldsBytes, const KArgs& a, Args... args)
+{
     hipStream_t st = joined(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dAovWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (float4*)dOut, (const uint32_t*)ctx->dUnitTri);
+    HIP_TRY(ctx, hipMemsetAsync(sp.words, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, args...);
     HIP_TRY(ctx, hipGetLastError());
     return RT_OK;
 }
 
-/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
-static int aov_fired(RtContext* ctx, unsigned long long* fired)
-{
-    *fired = 0;
-    HIP_TRY(ctx, hipMemcpy(fired, ctx->dAovWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
+extern "C" {
 
-/* After a synchronise of the stream: the report of a device pass that has not been reported yet */
-static int aov_report(RtContext* ctx, const char* call)
+/* ---- rt_render_aov / rt_render_aov_to_device (include/rt_aov.h): what camera ray 0 of a frame finds, per pixel -------------
+ * The side pass of rt_aov_kernel: KArgs as for frame `frame`, the tiles strided over the resident waves.  frame == RT_AOV_CENTRE (0)
+ * selects the pixel-centre ray of include/rt_motion.h, which reads nothing of a frame: the KArgs are then those of frame 1. */
+static int aov_enqueue(RtContext* ctx, int frame, void* dOut)
 {
-    if (!ctx->aovUnreported) return RT_OK;
-    ctx->aovUnreported = false;
-    unsigned long long fired = 0;
-    if (int rc = aov_fired(ctx, &fired)) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call (or its centre / moving form): "
-                           "walks were cut short, that call's records or denoised image are not valid (the context's images are not affected)", call, fired);
-    return RT_OK;
+    const bool centre = frame == RT_AOV_CENTRE;
+    KArgs a;
+    fill_args(ctx, centre ? 1 : frame, 1, a);
+    const int tiles = a.tilesX * a.tilesY;
+    if (tiles == 0) return RT_OK;
+    void (*kern)(const KArgs, float4*, const uint32_t*) = centre ? RT_SCENE_KERNEL(ctx, rtk::rt_aov_kernel, true) : RT_SCENE_KERNEL(ctx, rtk::rt_aov_kernel, false);
+    a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
+    SidePass& sp = ctx->side[SIDE_AOV];
+    size_t ldsBytes = 0;
+    long long grid = 0; /* every wave the device keeps resident; the tiles are strided over them */
+    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &grid)) return rc;
+    if (grid > tiles) grid = tiles;
+    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (float4*)dOut, (const uint32_t*)ctx->dUnitTri);
 }
 
 /* the frame number of the public frame calls (the centre calls pass RT_AOV_CENTRE to the shared bodies instead) */
@@ -2284,14 +2332,6 @@ static int aov_check_args(RtContext* ctx, const char* call, const void* out, siz
     return check_rows_buffer(ctx, call, sizeof(RtPixelAov), out, bytes);
 }
 
-/* a device pass still unreported: synchronise and report it before this call's own pass clears the word */
-static int aov_settle(RtContext* ctx, const char* call)
-{
-    if (!ctx->aovUnreported) return RT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    return aov_report(ctx, call);
-}
-
 /* the host and the device variant; `frame`: >= 1 (checked by the caller), or RT_AOV_CENTRE from the centre calls */
 static int aov_to_host(RtContext* ctx, const char* call, int frame, RtPixelAov* out, size_t bytes)
 {
@@ -2299,13 +2339,14 @@ static int aov_to_host(RtContext* ctx, const char* call, int frame, RtPixelAov* 
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    SidePass& sp = ctx->side[SIDE_AOV];
+    if ((rc = side_settle(ctx, sp, call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = grow_scratch(ctx, &ctx->dAovOut, &ctx->aovOutBytes, bytes))) return rc;
     if ((rc = aov_enqueue(ctx, frame, ctx->dAovOut))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     unsigned long long fired = 0;
-    if ((rc = aov_fired(ctx, &fired))) return rc;
+    if ((rc = side_fired(ctx, sp, &fired))) return rc;
     if (fired) return watchdog_failure(ctx, call, fired);
     HIP_TRY(ctx, hipMemcpy(out, ctx->dAovOut, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -2319,10 +2360,11 @@ static int aov_to_device(RtContext* ctx, const char* call, int frame, void* d_ou
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (bytes && (rc = check_device_range(ctx, call, "d_out", d_out, bytes))) return rc; /* the kernel writes through this pointer */
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    SidePass& sp = ctx->side[SIDE_AOV];
+    if ((rc = side_settle(ctx, sp, call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = aov_enqueue(ctx, frame, d_out))) return rc;
-    ctx->aovUnreported = true;
+    sp.unreported = true;
     return RT_OK;
 }
 
@@ -2343,241 +2385,121 @@ int rt_render_aov_centre(RtContext* ctx, RtPixelAov* out, size_t bytes) { return
 int rt_render_aov_centre_to_device(RtContext* ctx, void* d_out, size_t bytes) { return aov_to_device(ctx, "rt_render_aov_centre_to_device", RT_AOV_CENTRE, d_out, bytes); }
 
 /* ---- rt_query_closest / rt_query_occluded and their *_buffers forms (include/rt_query.h): caller-made rays against the scene ----------
- * One launch of rt_query_kernel (rt_kernels.h) on the joined main stream, built like the AOV pass: the context's in nothing but the scene
- * and the stream.  It needs neither an image nor parameters — fill_args as rt_debug_intersect calls it; the kernel reads the scene fields,
- * stackEntries and travLimit alone — a counter slot of its own (ctx->dQueryWords), no render target, no tile queue, no pixel records.
- * The checks and the block and grid arithmetic are rt_query_launch.h's. */
+ * The side pass of rt_query_kernel.  It needs neither an image nor parameters — fill_args as rt_debug_intersect calls it; the kernel
+ * reads the scene fields, stackEntries and travLimit alone.  The blocks of 64 rays are strided over the resident waves; the block and
+ * grid arithmetic is rt_query_launch.h's. */
 static int query_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut, bool any)
 {
     KArgs a;
     fill_args(ctx, 1, 1, a);
-    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
-    void (*kern)(const KArgs, const float4*, int, void*, const uint32_t*) =
-        any ? (many ? rtk::rt_query_kernel<false, true, true> : ctx->flatScene ? rtk::rt_query_kernel<true, false, true> : rtk::rt_query_kernel<false, false, true>)
-            : (many ? rtk::rt_query_kernel<false, true, false> : ctx->flatScene ? rtk::rt_query_kernel<true, false, false> : rtk::rt_query_kernel<false, false, false>);
-    /* a wave region of the trace kernel, single waves, no cache, no pool */
-    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
+    void (*kern)(const KArgs, const float4*, int, void*, const uint32_t*) = any ? RT_SCENE_KERNEL(ctx, rtk::rt_query_kernel, true) : RT_SCENE_KERNEL(ctx, rtk::rt_query_kernel, false);
     a.suspendNum = RT_SUSPEND_NUM; /* (unused: the traversal of a pass runs to completion) */
-    a.frameRender = nullptr;
-    a.accumulated = nullptr;
-    a.tileQueue = nullptr;
-    a.tileOrder = nullptr;
-    a.tileCost = nullptr;
-    a.pxCold = nullptr;
-    a.staging = nullptr;
-    if (!ctx->dQueryWords) HIP_TRY(ctx, hipMalloc(&ctx->dQueryWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
-    a.counters = ctx->dQueryWords;
+    SidePass& sp = ctx->side[SIDE_QUERY];
+    size_t ldsBytes = 0;
     long long resident = 0; /* every wave the device keeps resident; the blocks are strided over them */
-    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &resident)) return rc;
+    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
     const long long grid = rt_qr::grid(rt_qr::blocks(n), resident, ctx->gridOverride);
-    hipStream_t st = joined(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dQueryWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (const float4*)dRays, n, dOut, (const uint32_t*)ctx->dUnitTri);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, dOut, (const uint32_t*)ctx->dUnitTri);
 }
-
-/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
-static int query_fired(RtContext* ctx, unsigned long long* fired)
-{
-    *fired = 0;
-    HIP_TRY(ctx, hipMemcpy(fired, ctx->dQueryWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-/* After a synchronise of the stream: the report of a buffer-form pass that has not been reported yet */
-static int query_report(RtContext* ctx, const char* call)
-{
-    if (!ctx->queryUnreported) return RT_OK;
-    ctx->queryUnreported = false;
-    unsigned long long fired = 0;
-    if (int rc = query_fired(ctx, &fired)) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call: "
-                           "walks were cut short, that call's records or answers are not valid (the context's images are not affected)", call, fired);
-    return RT_OK;
-}
-
-/* what the four calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch */
-static int query_check(RtContext* ctx, const char* call, const void* rays, int n, const void* out, size_t outPerRay, size_t* rayBytes, size_t* outBytes)
-{
-    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
-    const char* why = "";
-    if (int rc = rt_qr::check_batch(rays, n, out, outPerRay, rayBytes, outBytes, &why)) return fail(ctx, rc, "%s: %s", call, why);
-    if (!ctx->haveScene) return fail(ctx, RT_ERR_STATE, "%s before rt_upload_scene", call);
-    return RT_OK;
-}
-
-/* a buffer-form pass still unreported: synchronise and report it before this call's own pass clears the word */
-static int query_settle(RtContext* ctx, const char* call)
-{
-    if (!ctx->queryUnreported) return RT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    return query_report(ctx, call);
-}
-
-static int query_to_host(RtContext* ctx, const char* call, const RtRay* rays, int n, void* out, size_t outPerRay, bool any)
-{
-    size_t rayBytes = 0, outBytes = 0;
-    int rc = query_check(ctx, call, rays, n, out, outPerRay, &rayBytes, &outBytes);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    RT_FLUSH(ctx);
-    if ((rc = query_settle(ctx, call))) return rc;
-    if (n == 0) return RT_OK;
-    if ((rc = grow_scratch(ctx, &ctx->dQueryRays, &ctx->queryRaysBytes, rayBytes))) return rc;
-    if ((rc = grow_scratch(ctx, &ctx->dQueryOut, &ctx->queryOutBytes, outBytes))) return rc;
-    hipStream_t st = joined(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dQueryRays, rays, rayBytes, hipMemcpyHostToDevice, st));
-    if ((rc = query_enqueue(ctx, ctx->dQueryRays, n, ctx->dQueryOut, any))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    unsigned long long fired = 0;
-    if ((rc = query_fired(ctx, &fired))) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in this pass: walks were cut short, the %s are not valid "
-                           "(the context's images are not affected)", call, fired, any ? "answers" : "records");
-    HIP_TRY(ctx, hipMemcpy(out, ctx->dQueryOut, outBytes, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-static int query_to_device(RtContext* ctx, const char* call, const void* d_rays, int n, void* d_out, size_t outPerRay, bool any)
-{
-    size_t rayBytes = 0, outBytes = 0;
-    int rc = query_check(ctx, call, d_rays, n, d_out, outPerRay, &rayBytes, &outBytes);
-    if (rc) return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (n > 0) { /* the kernel reads and writes through these pointers */
-        if ((rc = check_device_range(ctx, call, "d_rays", d_rays, rayBytes))) return rc;
-        if ((rc = check_device_range(ctx, call, any ? "d_occluded" : "d_hits", d_out, outBytes))) return rc;
-    }
-    RT_FLUSH(ctx);
-    if ((rc = query_settle(ctx, call))) return rc;
-    if (n == 0) return RT_OK;
-    if ((rc = query_enqueue(ctx, d_rays, n, d_out, any))) return rc;
-    ctx->queryUnreported = true;
-    return RT_OK;
-}
-
-int rt_query_closest(RtContext* ctx, const RtRay* rays, int n, RtRayHit* hits) { return query_to_host(ctx, "rt_query_closest", rays, n, hits, sizeof(RtRayHit), false); }
-int rt_query_closest_buffers(RtContext* ctx, const void* d_rays, int n, void* d_hits) { return query_to_device(ctx, "rt_query_closest_buffers", d_rays, n, d_hits, sizeof(RtRayHit), false); }
-int rt_query_occluded(RtContext* ctx, const RtRay* rays, int n, uint32_t* occluded) { return query_to_host(ctx, "rt_query_occluded", rays, n, occluded, sizeof(uint32_t), true); }
-int rt_query_occluded_buffers(RtContext* ctx, const void* d_rays, int n, void* d_occluded) { return query_to_device(ctx, "rt_query_occluded_buffers", d_rays, n, d_occluded, sizeof(uint32_t), true); }
+static int closest_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut) { return query_enqueue(ctx, dRays, n, dOut, false); }
+static int occluded_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut) { return query_enqueue(ctx, dRays, n, dOut, true); }
 
 /* ---- rt_radiance_trace / rt_radiance_trace_buffers (include/rt_radiance.h): Trace for caller-made rays -------------------------------
- * One launch of rt_radiance_kernel (rt_kernels.h) on the joined main stream, built like the query pass above: the context's in nothing
- * but the scene, the parameters and the stream.  fill_args with the parameters present (the kernel reads maxBounce, useSky and the sun's
- * fields besides the scene), the variant as choose_variant would choose it (FLAT / BVH / MANY) in its single-wave form, a counter slot of
- * the pass's own (ctx->dRadianceWords: word 0 hands out the blocks, word 7 is the watchdog's), no render target, no tile order, no pixel
- * records.  The checks and the block and grid arithmetic are rt_radiance_launch.h's. */
+ * The side pass of rt_radiance_kernel.  fill_args with the parameters present (the kernel reads maxBounce, useSky and the sun's fields
+ * besides the scene) and the tuner's suspension threshold; word 0 of the pass's slot hands out the blocks of 64 rays to the resident
+ * waves (word 7 is the watchdog's).  The block and grid arithmetic is rt_radiance_launch.h's. */
 static int radiance_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut)
 {
     KArgs a;
     fill_args(ctx, 1, 1, a);
-    const bool many = rt_plan::many_models(ctx->nChunks, ctx->flatScene);
-    void (*kern)(const KArgs, const float4*, int, float4*) =
-        many ? rtk::rt_radiance_kernel<false, true> : ctx->flatScene ? rtk::rt_radiance_kernel<true, false> : rtk::rt_radiance_kernel<false, false>;
-    /* a wave region of the trace kernel, single waves, no cache, no pool */
-    const size_t ldsBytes = rt_plan::wave_lds_bytes(ctx->stackEntries, ctx->extWords);
+    void (*kern)(const KArgs, const float4*, int, float4*) = RT_SCENE_KERNEL(ctx, rtk::rt_radiance_kernel);
     a.suspendNum = ctx->tuner.decided; /* scheduling only: a path's bits do not depend on it */
-    a.frameRender = nullptr;
-    a.accumulated = nullptr;
-    a.tileOrder = nullptr;
-    a.tileCost = nullptr;
-    a.pxCold = nullptr;
-    a.staging = nullptr;
-    if (!ctx->dRadianceWords) HIP_TRY(ctx, hipMalloc(&ctx->dRadianceWords, sizeof(unsigned long long) * RT_COUNTER_FIELDS));
-    a.counters = ctx->dRadianceWords;
-    a.tileQueue = ctx->dRadianceWords; /* word 0: a launch of this pass counts no segments there */
-    a.tileQueueBase = 0;
+    SidePass& sp = ctx->side[SIDE_RADIANCE];
+    size_t ldsBytes = 0;
     long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
-    if (int rc = single_wave_pass(ctx, reinterpret_cast<const void*>(kern), ldsBytes, a, &resident)) return rc;
+    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
+    a.tileQueue = sp.words; /* word 0: a launch of this pass counts no segments there */
+    a.tileQueueBase = 0;
     const long long grid = rt_rd::grid(rt_rd::blocks(n), resident, ctx->gridOverride);
-    hipStream_t st = joined(ctx);
-    HIP_TRY(ctx, hipMemsetAsync(ctx->dRadianceWords, 0, sizeof(unsigned long long) * RT_COUNTER_FIELDS, st));
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(RT_WAVE), ldsBytes, st, a, (const float4*)dRays, n, (float4*)dOut);
-    HIP_TRY(ctx, hipGetLastError());
-    return RT_OK;
+    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, (float4*)dOut);
 }
 
-/* After a synchronise of the stream: the pass's own watchdog word (8 bytes read back) */
-static int radiance_fired(RtContext* ctx, unsigned long long* fired)
-{
-    *fired = 0;
-    HIP_TRY(ctx, hipMemcpy(fired, ctx->dRadianceWords + kWatchdogWord, sizeof(*fired), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
+/* ---- the host form and the buffer form of the six ray-batch calls ----------------------------------------------------------------------
+ * What tells the three kinds of batch apart: the pass and its enqueue function, the size of a ray's output, the buffer form's name for
+ * the output pointer, the host form's word for the output, and whether the pass reads the parameters. */
+struct RayBatch {
+    int pass;
+    int (*enqueue)(RtContext* ctx, const void* dRays, int n, void* dOut);
+    size_t outPerRay;
+    const char* outName;
+    const char* noun;
+    bool needParams;
+};
+static const RayBatch kClosest = {SIDE_QUERY, closest_enqueue, sizeof(RtRayHit), "d_hits", "records", false};
+static const RayBatch kOccluded = {SIDE_QUERY, occluded_enqueue, sizeof(uint32_t), "d_occluded", "answers", false};
+static const RayBatch kRadiance = {SIDE_RADIANCE, radiance_enqueue, sizeof(RtRadiance), "d_out", "records", true};
 
-/* After a synchronise of the stream: the report of a buffer-form pass that has not been reported yet */
-static int radiance_report(RtContext* ctx, const char* call)
-{
-    if (!ctx->radianceUnreported) return RT_OK;
-    ctx->radianceUnreported = false;
-    unsigned long long fired = 0;
-    if (int rc = radiance_fired(ctx, &fired)) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in the pass of an rt_radiance_trace_buffers call: "
-                           "walks were cut short, that call's records are not valid (the context's images are not affected)", call, fired);
-    return RT_OK;
-}
-
-/* what the two calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch */
-static int radiance_check(RtContext* ctx, const char* call, const void* rays, int n, const void* out, size_t* rayBytes, size_t* outBytes)
+/* what the calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch (rt_rd::check_batch is
+ * rt_qr::check_batch with an RtRadiance per ray) */
+static int rays_check(RtContext* ctx, const char* call, const RayBatch& b, const void* rays, int n, const void* out, size_t* rayBytes, size_t* outBytes)
 {
     if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
     const char* why = "";
-    if (int rc = rt_rd::check_batch(rays, n, out, rayBytes, outBytes, &why)) return fail(ctx, rc, "%s: %s", call, why);
+    if (int rc = rt_qr::check_batch(rays, n, out, b.outPerRay, rayBytes, outBytes, &why)) return fail(ctx, rc, "%s: %s", call, why);
     if (!ctx->haveScene) return fail(ctx, RT_ERR_STATE, "%s before rt_upload_scene", call);
-    if (!ctx->haveParams) return fail(ctx, RT_ERR_STATE, "%s before rt_set_params", call);
+    if (b.needParams && !ctx->haveParams) return fail(ctx, RT_ERR_STATE, "%s before rt_set_params", call);
     return RT_OK;
 }
 
-/* a buffer-form pass still unreported: synchronise and report it before this call's own pass clears the word */
-static int radiance_settle(RtContext* ctx, const char* call)
+static int rays_to_host(RtContext* ctx, const char* call, const RayBatch& b, const void* rays, int n, void* out)
 {
-    if (!ctx->radianceUnreported) return RT_OK;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    return radiance_report(ctx, call);
-}
-
-int rt_radiance_trace(RtContext* ctx, const RtPathRay* rays, int n, RtRadiance* out)
-{
-    const char* const call = "rt_radiance_trace";
     size_t rayBytes = 0, outBytes = 0;
-    int rc = radiance_check(ctx, call, rays, n, out, &rayBytes, &outBytes);
+    int rc = rays_check(ctx, call, b, rays, n, out, &rayBytes, &outBytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    if ((rc = radiance_settle(ctx, call))) return rc;
+    SidePass& sp = ctx->side[b.pass];
+    if ((rc = side_settle(ctx, sp, call))) return rc;
     if (n == 0) return RT_OK;
-    if ((rc = grow_scratch(ctx, &ctx->dRadianceRays, &ctx->radianceRaysBytes, rayBytes))) return rc;
-    if ((rc = grow_scratch(ctx, &ctx->dRadianceOut, &ctx->radianceOutBytes, outBytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dRays, &ctx->raysBytes, rayBytes))) return rc;
+    if ((rc = grow_scratch(ctx, &ctx->dRayOut, &ctx->rayOutBytes, outBytes))) return rc;
     hipStream_t st = joined(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->dRadianceRays, rays, rayBytes, hipMemcpyHostToDevice, st));
-    if ((rc = radiance_enqueue(ctx, ctx->dRadianceRays, n, ctx->dRadianceOut))) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->dRays, rays, rayBytes, hipMemcpyHostToDevice, st));
+    if ((rc = b.enqueue(ctx, ctx->dRays, n, ctx->dRayOut))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     unsigned long long fired = 0;
-    if ((rc = radiance_fired(ctx, &fired))) return rc;
-    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in this pass: walks were cut short, the records are not valid "
-                           "(the context's images are not affected)", call, fired);
-    HIP_TRY(ctx, hipMemcpy(out, ctx->dRadianceOut, outBytes, hipMemcpyDeviceToHost));
+    if ((rc = side_fired(ctx, sp, &fired))) return rc;
+    if (fired) return fail(ctx, RT_ERR_HIP, "%s: the traversal watchdog fired %llu times in this pass: walks were cut short, the %s are not valid "
+                           "(the context's images are not affected)", call, fired, b.noun);
+    HIP_TRY(ctx, hipMemcpy(out, ctx->dRayOut, outBytes, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
-int rt_radiance_trace_buffers(RtContext* ctx, const void* d_rays, int n, void* d_out)
+static int rays_to_device(RtContext* ctx, const char* call, const RayBatch& b, const void* d_rays, int n, void* d_out)
 {
-    const char* const call = "rt_radiance_trace_buffers";
     size_t rayBytes = 0, outBytes = 0;
-    int rc = radiance_check(ctx, call, d_rays, n, d_out, &rayBytes, &outBytes);
+    int rc = rays_check(ctx, call, b, d_rays, n, d_out, &rayBytes, &outBytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (n > 0) { /* the kernel reads and writes through these pointers */
         if ((rc = check_device_range(ctx, call, "d_rays", d_rays, rayBytes))) return rc;
-        if ((rc = check_device_range(ctx, call, "d_out", d_out, outBytes))) return rc;
+        if ((rc = check_device_range(ctx, call, b.outName, d_out, outBytes))) return rc;
     }
     RT_FLUSH(ctx);
-    if ((rc = radiance_settle(ctx, call))) return rc;
+    SidePass& sp = ctx->side[b.pass];
+    if ((rc = side_settle(ctx, sp, call))) return rc;
     if (n == 0) return RT_OK;
-    if ((rc = radiance_enqueue(ctx, d_rays, n, d_out))) return rc;
-    ctx->radianceUnreported = true;
+    if ((rc = b.enqueue(ctx, d_rays, n, d_out))) return rc;
+    sp.unreported = true;
     return RT_OK;
 }
+
+int rt_query_closest(RtContext* ctx, const RtRay* rays, int n, RtRayHit* hits) { return rays_to_host(ctx, "rt_query_closest", kClosest, rays, n, hits); }
+int rt_query_closest_buffers(RtContext* ctx, const void* d_rays, int n, void* d_hits) { return rays_to_device(ctx, "rt_query_closest_buffers", kClosest, d_rays, n, d_hits); }
+int rt_query_occluded(RtContext* ctx, const RtRay* rays, int n, uint32_t* occluded) { return rays_to_host(ctx, "rt_query_occluded", kOccluded, rays, n, occluded); }
+int rt_query_occluded_buffers(RtContext* ctx, const void* d_rays, int n, void* d_occluded) { return rays_to_device(ctx, "rt_query_occluded_buffers", kOccluded, d_rays, n, d_occluded); }
+int rt_radiance_trace(RtContext* ctx, const RtPathRay* rays, int n, RtRadiance* out) { return rays_to_host(ctx, "rt_radiance_trace", kRadiance, rays, n, out); }
+int rt_radiance_trace_buffers(RtContext* ctx, const void* d_rays, int n, void* d_out) { return rays_to_device(ctx, "rt_radiance_trace_buffers", kRadiance, d_rays, n, d_out); }
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main
@@ -2645,6 +2567,20 @@ int rt_denoise_buffers(RtContext* ctx, const RtDenoiseParams* p, int width, int 
     return RT_OK;
 }
 
+/* how rt_denoise and rt_denoise_variance end, their filter enqueued into ctx->dDisplay behind its AOV pass: the pass's word, then the
+ * context's, then the image */
+static int filtered_to_host(RtContext* ctx, const char* call, float* rgba, size_t bytes)
+{
+    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
+    flush_timer(ctx);
+    unsigned long long fired = 0;
+    if (int rc = side_fired(ctx, ctx->side[SIDE_AOV], &fired)) return rc;
+    if (fired) return watchdog_failure(ctx, call, fired);
+    if (int rc = check_watchdog(ctx, ctx, call)) return rc;
+    HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 /* what rt_denoise and rt_denoise_to_device share: checks, the AOV pass, the filter from the context's image into dOut (device) */
 static int denoise_check_context_call(RtContext* ctx, const char* call, const RtDenoiseParams* p, int aov_frame, const void* out, size_t bytes, rt_dn::Job* job)
 {
@@ -2679,18 +2615,11 @@ int rt_denoise(RtContext* ctx, const RtDenoiseParams* p, int use_accumulated, in
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    if ((rc = side_settle(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
     if ((rc = denoise_enqueue_context_call(ctx, job, use_accumulated, aov_frame, ctx->dDisplay))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    flush_timer(ctx);
-    unsigned long long fired = 0;
-    if ((rc = aov_fired(ctx, &fired))) return rc;
-    if (fired) return watchdog_failure(ctx, call, fired);
-    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return filtered_to_host(ctx, call, rgba, bytes);
 }
 
 int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accumulated, int aov_frame, void* d_rgba, size_t bytes)
@@ -2700,17 +2629,12 @@ int rt_denoise_to_device(RtContext* ctx, const RtDenoiseParams* p, int use_accum
     int rc = denoise_check_context_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes) {
-        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
-        if (ranges_overlap(d_rgba, bytes, image_target(ctx, use_accumulated), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the source image", call);
-    } else if ((uintptr_t)d_rgba & 15) {
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
-    }
+    if ((rc = check_image_out(ctx, call, d_rgba, bytes, image_target(ctx, use_accumulated), "the source image"))) return rc;
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    if ((rc = side_settle(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = denoise_enqueue_context_call(ctx, job, use_accumulated, aov_frame, d_rgba))) return rc;
-    ctx->aovUnreported = true;
+    ctx->side[SIDE_AOV].unreported = true;
     return RT_OK;
 }
 
@@ -2854,17 +2778,17 @@ static int reproject_accumulated_call(RtContext* ctx, const char* call, const Rt
     }
     if ((rc = check_motion_table(ctx, call, mo, accum, n * 16, d_cur_aov_out, recBytes))) return rc;
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    if ((rc = side_settle(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if (!n) return RT_OK;
     if ((rc = grow_scratch(ctx, &ctx->dDnScratch, &ctx->dnScratchBytes, n * 16))) return rc;
     if ((rc = grow_scratch(ctx, &ctx->dDnAov, &ctx->dnAovBytes, recBytes))) return rc;
     if ((rc = aov_enqueue(ctx, aov_frame, ctx->dDnAov))) return rc;
-    ctx->aovUnreported = true;
+    ctx->side[SIDE_AOV].unreported = true;
     hipStream_t st = joined(ctx);
     if (d_cur_aov_out) HIP_TRY(ctx, hipMemcpyAsync(d_cur_aov_out, ctx->dDnAov, recBytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, reproject_enqueue(st, job, accum, d_prev_aov, ctx->dDnAov, mo, ctx->dDnScratch));
     /* over the accumulator, unless the pass's watchdog fired: the device reads the pass's own word, the host reports it later */
-    HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, accum, n, ctx->dAovWords + kWatchdogWord));
+    HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, accum, n, ctx->side[SIDE_AOV].words + kWatchdogWord));
     return RT_OK;
 }
 
@@ -2932,7 +2856,7 @@ int rt_resolve(RtContext* ctx, float* rgba, size_t bytes)
     flush_timer(ctx);
     /* a device AOV pass completes here: a watchdog that fired in rt_reproject_accumulated's pass left the accumulator as it was, and the
      * caller of this host read must not take its resolve for the reprojected image */
-    if ((rc = aov_report(ctx, call))) return rc;
+    if ((rc = side_report(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if ((rc = check_watchdog(ctx, ctx, call))) return rc;
     if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -2944,12 +2868,7 @@ int rt_resolve_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
     int rc = resolve_check_call(ctx, call, d_rgba, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes) {
-        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
-        if (ranges_overlap(d_rgba, bytes, accum_target(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
-    } else if ((uintptr_t)d_rgba & 15) {
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
-    }
+    if ((rc = check_image_out(ctx, call, d_rgba, bytes, accum_target(ctx), "AccumulatedRender"))) return rc;
     RT_FLUSH(ctx);
     if (!bytes) return RT_OK;
     HIP_TRY(ctx, rt_rp::enqueue_resolve(joined(ctx), accum_target(ctx), d_rgba, bytes / 16));
@@ -3122,8 +3041,8 @@ int rt_variance_carry(RtContext* ctx, const RtReprojectParams* p, const void* d_
     HIP_TRY(ctx, reproject_enqueue(st, job, ctx->dMoments, d_prev_aov, d_cur_aov, mo, ctx->dDnScratch));
     /* over the moments, unless the watchdog of the AOV pass that wrote d_cur_aov fired — rt_reproject_accumulated's commit read the same
      * word and then left the sum alone.  Before any AOV pass of this context there is no such word and nothing to skip for. */
-    if (ctx->dAovWords)
-        HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, ctx->dMoments, n, ctx->dAovWords + kWatchdogWord));
+    if (ctx->side[SIDE_AOV].words)
+        HIP_TRY(ctx, rt_rp::enqueue_commit(st, ctx->dDnScratch, ctx->dMoments, n, ctx->side[SIDE_AOV].words + kWatchdogWord));
     else
         HIP_TRY(ctx, hipMemcpyAsync(ctx->dMoments, ctx->dDnScratch, n * 16, hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, rt_vr::enqueue_update(st, accum_target(ctx), ctx->dSnapshot, ctx->dMoments, n, 1));
@@ -3146,7 +3065,7 @@ int rt_variance_read_moments(RtContext* ctx, float* rgba, size_t bytes)
     if ((rc = variance_images(ctx))) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
     flush_timer(ctx);
-    if ((rc = aov_report(ctx, call))) return rc; /* as rt_resolve: a carry behind a pass whose watchdog fired carried nothing */
+    if ((rc = side_report(ctx, ctx->side[SIDE_AOV], call))) return rc; /* as rt_resolve: a carry behind a pass whose watchdog fired carried nothing */
     if ((rc = check_watchdog(ctx, ctx, call))) return rc;
     if (bytes) HIP_TRY(ctx, hipMemcpy(rgba, ctx->dMoments, bytes, hipMemcpyDeviceToHost));
     return RT_OK;
@@ -3158,11 +3077,8 @@ int rt_variance_moments_to_device(RtContext* ctx, void* d_rgba, size_t bytes)
     int rc = variance_check_moments_call(ctx, call, d_rgba, bytes);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (!bytes) {
-        if ((uintptr_t)d_rgba & 15) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
-        return RT_OK;
-    }
-    if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
+    if ((rc = check_image_out(ctx, call, d_rgba, bytes, nullptr, nullptr))) return rc; /* (against the moments below: they may not exist yet) */
+    if (!bytes) return RT_OK;
     RT_FLUSH(ctx);
     if ((rc = variance_images(ctx))) return rc;
     if (ranges_overlap(d_rgba, bytes, ctx->dMoments, bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the moments", call);
@@ -3208,18 +3124,11 @@ int rt_denoise_variance(RtContext* ctx, const RtVarianceDenoiseParams* p, int ao
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    if ((rc = side_settle(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = grow_scratch(ctx, &ctx->dDisplay, &ctx->displayBytes, bytes))) return rc;
     if ((rc = variance_enqueue_filter_call(ctx, job, aov_frame, ctx->dDisplay))) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(joined(ctx)));
-    flush_timer(ctx);
-    unsigned long long fired = 0;
-    if ((rc = aov_fired(ctx, &fired))) return rc;
-    if (fired) return watchdog_failure(ctx, call, fired);
-    if ((rc = check_watchdog(ctx, ctx, call))) return rc;
-    HIP_TRY(ctx, hipMemcpy(rgba, ctx->dDisplay, bytes, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return filtered_to_host(ctx, call, rgba, bytes);
 }
 
 int rt_denoise_variance_to_device(RtContext* ctx, const RtVarianceDenoiseParams* p, int aov_frame, void* d_rgba, size_t bytes)
@@ -3229,19 +3138,14 @@ int rt_denoise_variance_to_device(RtContext* ctx, const RtVarianceDenoiseParams*
     int rc = variance_check_filter_call(ctx, call, p, aov_frame, d_rgba, bytes, &job);
     if (rc) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (bytes) {
-        if ((rc = check_device_range(ctx, call, "d_rgba", d_rgba, bytes))) return rc;
-        if (ranges_overlap(d_rgba, bytes, accum_target(ctx), bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps AccumulatedRender", call);
-    } else if ((uintptr_t)d_rgba & 15) {
-        return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba must be 16-byte aligned", call);
-    }
+    if ((rc = check_image_out(ctx, call, d_rgba, bytes, accum_target(ctx), "AccumulatedRender"))) return rc;
     RT_FLUSH(ctx);
-    if ((rc = aov_settle(ctx, call))) return rc;
+    if ((rc = side_settle(ctx, ctx->side[SIDE_AOV], call))) return rc;
     if (!bytes) return RT_OK;
     if ((rc = variance_images(ctx))) return rc;
     if (ranges_overlap(d_rgba, bytes, ctx->dMoments, bytes)) return fail(ctx, RT_ERR_INVALID_ARG, "%s: d_rgba overlaps the moments", call);
     if ((rc = variance_enqueue_filter_call(ctx, job, aov_frame, d_rgba))) return rc;
-    ctx->aovUnreported = true;
+    ctx->side[SIDE_AOV].unreported = true;
     return RT_OK;
 }
 

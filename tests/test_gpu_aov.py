@@ -563,21 +563,56 @@ def test_errors(pkg, api):
 def test_watchdog_fails_the_pass_not_the_context(pkg, api, monkeypatch):
     """RT_TRAV_LIMIT=4 (read at rt_upload_scene; the step limit is a software counter, nothing can hang): the pass's walks are cut short.
     The host variant says so when it returns, the device variant at the next rt_synchronize, once — and the context's counters and
-    images, which no frame of it touched, stay readable."""
+    images, which no frame of it touched, stay readable.  Every message names the call that reports and, for a deferred report, the
+    calls whose pass it was; the next AOV call reports in place of rt_synchronize when it comes first; a pass of another kind
+    (rt_query_closest) reports its own word only."""
     tr = api.create_tracer(0)
     t = DevBuf(36 * 64 * 64)
     try:
         monkeypatch.setenv("RT_TRAV_LIMIT", "4")
-        Setup(pkg, api, tr, (3, {}), 64, 36)
+        su = Setup(pkg, api, tr, (3, {}), 64, 36)
         monkeypatch.delenv("RT_TRAV_LIMIT")
-        with pytest.raises(pkg.abi.RtError) as e:
-            tr.render_aov(1)
-        assert e.value.status == pkg.abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+        abi = pkg.abi
+
+        def reported(e, call, *holds):  # the status, the call at the front of the message, and what else it must hold
+            msg = str(e.value)
+            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in msg, msg
+            assert msg.startswith(f"rt status {abi.RT_ERR_HIP}: {call}: "), msg
+            for text in holds:
+                assert text in msg, (text, msg)
+            return msg
+        family = "in the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call"
+        for call, name in ((lambda: tr.render_aov(1), "rt_render_aov"), (tr.render_aov_centre, "rt_render_aov_centre")):
+            with pytest.raises(abi.RtError) as e:
+                call()
+            reported(e, name, "a kernel watchdog fired")
         tr.render_aov_to_device(1, t.ptr, t.nbytes)  # enqueued: RT_OK
-        with pytest.raises(pkg.abi.RtError) as e:
+        with pytest.raises(abi.RtError) as e:
             tr.synchronize()
-        assert e.value.status == pkg.abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+        reported(e, "rt_synchronize", family)
         tr.synchronize()  # reported once
+        tr.render_aov_to_device(1, t.ptr, t.nbytes)
+        with pytest.raises(abi.RtError) as e:  # the next AOV call reports it if it comes first ...
+            tr.render_aov_to_device(1, t.ptr, t.nbytes)
+        reported(e, "rt_render_aov_to_device", family)
+        tr.synchronize()  # ... once (and the call that reported enqueued nothing)
+        tr.render_aov_to_device(1, t.ptr, t.nbytes)
+        with pytest.raises(abi.RtError) as e:  # the host variant reports it as well
+            tr.render_aov(1)
+        reported(e, "rt_render_aov", family)
+        tr.synchronize()
+        # a pass of another kind neither reports it nor is failed by it: a ray query along the camera's axis says what its own pass met,
+        # and the AOV pass is still reported at the next rt_synchronize
+        m = np.array(list(su.params(1).camLocalToWorld), dtype=F)
+        rays = abi.make_rays(np.tile(m[12:15], (64, 1)), np.tile(m[8:11], (64, 1)))
+        tr.render_aov_to_device(1, t.ptr, t.nbytes)
+        with pytest.raises(abi.RtError) as e:
+            tr.query_closest(rays)
+        assert "AOV" not in reported(e, "rt_query_closest", "in this pass", "the records are not valid")
+        with pytest.raises(abi.RtError) as e:
+            tr.synchronize()
+        reported(e, "rt_synchronize", family)
+        tr.synchronize()
         c = tr.counters()  # RT_OK: the context's watchdog word was not set
         assert c["segments"] == 0
         assert not tr.read_accumulated().any()

@@ -624,7 +624,9 @@ def test_errors(pkg, api, orc):
 def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
     """RT_TRAV_LIMIT=4 (read at rt_upload_scene; the step limit is a software counter, nothing can hang): the walks are cut short.  The
     host forms say so when they return, a buffer form at the next rt_synchronize, once — and the context's counters and images, which
-    no frame of it touched, stay readable.  After a re-upload without the variable the same rays equal the oracle again."""
+    no frame of it touched, stay readable.  After a re-upload without the variable the same rays equal the oracle again.  Every message
+    names the call that reports and, for a deferred report, the calls whose pass it was; the next rt_query_* call reports in place of
+    rt_synchronize when it comes first; a pass of another kind (rt_render_aov) reports its own word only."""
     sc, origins, dirs, want10 = case(pkg, api, orc, "config3_bvh")
     abi = pkg.abi
     n = 256
@@ -636,20 +638,44 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
         monkeypatch.setenv("RT_TRAV_LIMIT", "4")
         mgr.OnEnable(renderSeed=1)  # resize, upload, parameters; no frame
         monkeypatch.delenv("RT_TRAV_LIMIT")
-        for call in (tr.query_closest, tr.query_occluded):
+
+        def reported(e, call, *holds):  # the status, the call at the front of the message, and what else it must hold
+            msg = str(e.value)
+            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in msg, msg
+            assert msg.startswith(f"rt status {abi.RT_ERR_HIP}: {call}: "), msg
+            for text in holds:
+                assert text in msg, (text, msg)
+            return msg
+        family = "in the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call"
+        for call, name, noun in ((tr.query_closest, "rt_query_closest", "records"), (tr.query_occluded, "rt_query_occluded", "answers")):
             with pytest.raises(abi.RtError) as e:
                 call(rays)
-            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+            reported(e, name, "in this pass", f"the {noun} are not valid")
         tr.query_closest_buffers(bufs[0].ptr, n, bufs[1].ptr)  # enqueued: RT_OK
         with pytest.raises(abi.RtError) as e:
             tr.synchronize()
-        assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+        reported(e, "rt_synchronize", family)
         tr.synchronize()  # reported once
-        tr.query_occluded_buffers(bufs[0].ptr, n, bufs[2].ptr)
+        tr.query_closest_buffers(bufs[0].ptr, n, bufs[1].ptr)
         with pytest.raises(abi.RtError) as e:  # the next rt_query_* call reports it if it comes first ...
             tr.query_occluded_buffers(bufs[0].ptr, n, bufs[2].ptr)
-        assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
-        tr.synchronize()  # ... once
+        reported(e, "rt_query_occluded_buffers", family)
+        tr.synchronize()  # ... once (and the call that reported enqueued nothing)
+        tr.query_occluded_buffers(bufs[0].ptr, n, bufs[2].ptr)
+        with pytest.raises(abi.RtError) as e:  # a host form reports it as well
+            tr.query_closest(rays)
+        reported(e, "rt_query_closest", family)
+        tr.synchronize()
+        # a pass of another kind neither reports it nor is failed by it: rt_render_aov says what its own pass met, and the query pass
+        # is still reported at the next rt_synchronize
+        tr.query_closest_buffers(bufs[0].ptr, n, bufs[1].ptr)
+        with pytest.raises(abi.RtError) as e:
+            tr.render_aov(1)
+        assert "rt_query" not in reported(e, "rt_render_aov", "a kernel watchdog fired")
+        with pytest.raises(abi.RtError) as e:
+            tr.synchronize()
+        reported(e, "rt_synchronize", family)
+        tr.synchronize()
         c = tr.counters()  # RT_OK: the context's watchdog word was not set
         assert c["segments"] == 0
         assert not tr.read_accumulated().any()

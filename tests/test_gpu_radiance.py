@@ -432,7 +432,8 @@ def test_errors(pkg, api, orc):
 def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
     """RT_TRAV_LIMIT=4 (read at rt_upload_scene; the step limit is a software counter, nothing can hang): the walks of the pass are cut
     short.  The host form says so when it returns, the buffer form at the next rt_synchronize or rt_radiance_* call, once — and the
-    frames the context rendered before stay readable and equal the oracle's."""
+    frames the context rendered before stay readable and equal the oracle's.  Every message names the call that reports and, for a
+    deferred report, the call whose pass it was; a pass of another kind (rt_query_occluded) reports its own word only."""
     abi = pkg.abi
     w, h = 24, 16
     sc, p, origins, dirs, states, want = camera_case(pkg, api, orc, "config3_bvh", w, h, False, None)
@@ -451,19 +452,43 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
             monkeypatch.setenv("RT_TRAV_LIMIT", "4")
             sc.upload(tr)  # the limit of a scene is set when it is uploaded; the images stay
             monkeypatch.delenv("RT_TRAV_LIMIT")
+
+            def reported(e, call, *holds):  # the status, the call at the front of the message, and what else it must hold
+                msg = str(e.value)
+                assert e.value.status == abi.RT_ERR_HIP and "watchdog" in msg, msg
+                assert msg.startswith(f"rt status {abi.RT_ERR_HIP}: {call}: "), msg
+                for text in holds:
+                    assert text in msg, (text, msg)
+                return msg
+            family = "in the pass of an rt_radiance_trace_buffers call"
             with pytest.raises(abi.RtError) as e:
                 tr.radiance_trace(rays)
-            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+            reported(e, "rt_radiance_trace", "in this pass", "the records are not valid")
             tr.radiance_trace_buffers(bufs[0].ptr, n, bufs[1].ptr)  # enqueued: RT_OK
             with pytest.raises(abi.RtError) as e:
                 tr.synchronize()
-            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
+            reported(e, "rt_synchronize", family)
             tr.synchronize()  # reported once
             tr.radiance_trace_buffers(bufs[0].ptr, n, bufs[1].ptr)
             with pytest.raises(abi.RtError) as e:  # the next rt_radiance_* call reports it if it comes first ...
                 tr.radiance_trace_buffers(bufs[0].ptr, n, bufs[1].ptr)
-            assert e.value.status == abi.RT_ERR_HIP and "watchdog" in str(e.value), str(e.value)
-            tr.synchronize()  # ... once
+            reported(e, "rt_radiance_trace_buffers", family)
+            tr.synchronize()  # ... once (and the call that reported enqueued nothing)
+            tr.radiance_trace_buffers(bufs[0].ptr, n, bufs[1].ptr)
+            with pytest.raises(abi.RtError) as e:  # the host form reports it as well
+                tr.radiance_trace(rays)
+            reported(e, "rt_radiance_trace", family)
+            tr.synchronize()
+            # a pass of another kind neither reports it nor is failed by it: a ray query over the same rays says what its own pass
+            # met, and the radiance pass is still reported at the next rt_synchronize
+            tr.radiance_trace_buffers(bufs[0].ptr, n, bufs[1].ptr)
+            with pytest.raises(abi.RtError) as e:
+                tr.query_occluded(abi.make_rays(rays["origin"], rays["dir"]))
+            assert "rt_radiance" not in reported(e, "rt_query_occluded", "in this pass", "the answers are not valid")
+            with pytest.raises(abi.RtError) as e:
+                tr.synchronize()
+            reported(e, "rt_synchronize", family)
+            tr.synchronize()
             assert tr.frame() == 3
             images.append(tr.read_accumulated().tobytes())  # RT_OK: the context's watchdog word was not set
             sc.upload(tr)
