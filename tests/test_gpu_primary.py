@@ -168,15 +168,17 @@ def _boxes(pkg, sc, n_cubes, n_quads):
         sc.models.append(mod.Model(quad, mod.RayTracingMaterial(diffuseCol=(0.2, 0.5, 0.9, 1)), mod.Transform(position=(-3.0 + 2.0 * i, 1.0, 4.0), euler=(0, 20 * i, 0), scale=(1.5, 2.0, 1))))
 
 
-def _one_leaf_per_mesh(mgr):
-    mgr.bvhQuality = 0   # Quality.Disabled: the whole mesh in its root leaf -> a FLAT scene
+def _one_leaf_per_mesh(pkg):
+    def tweak(mgr):
+        mgr.bvhQuality = pkg.abi.BVH_QUALITY_DISABLED   # the whole mesh in its root leaf -> a FLAT scene
+    return tweak
 
 
 @pytest.mark.parametrize("cubes,quads", [(1, 0), (2, 0), (0, 4)])
 def test_leaf_sizes_and_the_caps(pkg, api, orc, cubes, quads):
     """ground + one cube: 2 + 12 triangles in two models, within the caps; + two cubes: 26 triangles, over the triangle cap; + four
     quads: five models, over the model cap"""
-    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(2), change_scene=lambda sc: _boxes(pkg, sc, cubes, quads), tweak=_one_leaf_per_mesh), table=(cubes, quads) == (1, 0))
+    check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(2), change_scene=lambda sc: _boxes(pkg, sc, cubes, quads), tweak=_one_leaf_per_mesh(pkg)), table=(cubes, quads) == (1, 0))
 
 
 def test_no_bounces_every_intersection_is_a_camera_rays(pkg, api, orc):

@@ -125,8 +125,10 @@ def _boxes(pkg, sc, n_cubes, n_quads):
         sc.models.append(mod.Model(quad, mod.RayTracingMaterial(diffuseCol=(0.2, 0.5, 0.9, 1)), mod.Transform(position=(-3.0 + 2.0 * i, 1.0, 4.0), euler=(0, 20 * i, 0), scale=(1.5, 2.0, 1))))
 
 
-def _one_leaf_per_mesh(mgr):
-    mgr.bvhQuality = 0   # Quality.Disabled: the whole mesh in its root leaf -> a FLAT scene
+def _one_leaf_per_mesh(pkg):
+    def tweak(mgr):
+        mgr.bvhQuality = pkg.abi.BVH_QUALITY_DISABLED   # the whole mesh in its root leaf -> a FLAT scene
+    return tweak
 
 
 @pytest.mark.parametrize("cubes,quads", [(1, 0), (0, 3), (2, 0), (0, 4)])
@@ -135,7 +137,7 @@ def test_leaf_sizes_and_the_caps(pkg, api, orc, cubes, quads):
     + two cubes: 26 triangles, over the triangle cap; + four quads: five models, over the model cap.  Over a cap the table of ray-origin
     constants is off (rt_primary.h), the per-tile table rides on it, and so both of its halves stay off, as the sphere half always did."""
     within = (cubes, quads) in ((1, 0), (0, 3))
-    tri = check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(2), change_scene=lambda sc: _boxes(pkg, sc, cubes, quads), tweak=_one_leaf_per_mesh), table=within)
+    tri = check(pkg, api, orc, scene_driver(pkg, 2, 64, 36, frames(2), change_scene=lambda sc: _boxes(pkg, sc, cubes, quads), tweak=_one_leaf_per_mesh(pkg)), table=within)
     if within:
         assert tri["masks, pooled"] < tri["no masks, pooled"]
 

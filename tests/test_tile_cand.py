@@ -22,6 +22,8 @@ import subprocess
 
 import pytest
 
+from capfuzz_scenes import sphere_scene_file as scene_file   # (the driver's text form: shared with tests/test_tile_fuzz.py)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -51,31 +53,6 @@ def run(exe, *args):
     last = out.strip().splitlines()[-1]
     assert last.startswith("ok ") and " misses=0 " in last + " ", out[-3000:]
     return {k: float(v) for k, v in re.findall(r"(\w+)=([-0-9.e+]+)", last)}
-
-
-class _NoTracer:
-    """make_manager wants a tracer; params() never calls it"""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the tracer is not to be called ({name})")
-
-
-def scene_file(pkg, api, d, cfg, w, h, part=(8, 0, 1)):
-    """the camera block and spheres of a config as the manager hands them to the library, in the driver's text form"""
-    mgr = pkg.scenes.get(cfg).make_manager(_NoTracer(), api, w, h)
-    p = mgr.params()
-    assert p.defocusStrength == 0.0
-    lines = [f"{w} {h} {part[0]} {part[1]} {part[2]} {p.divergeStrength!r}",
-             " ".join(repr(float(v)) for v in p.camLocalToWorld),
-             " ".join(repr(float(v)) for v in p.viewParams),
-             str(len(mgr.spheres))]
-    import numpy as np
-    for s in mgr.spheres:
-        lines.append(" ".join(repr(float(np.float32(v))) for v in (*s.centre, s.radius)))
-    path = str(d / f"config{cfg}_{w}x{h}_{part[1]}of{part[2]}.txt")
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return path
 
 
 @pytest.mark.parametrize("seed", [1, 2, 20261018])

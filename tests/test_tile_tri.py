@@ -26,6 +26,8 @@ import subprocess
 
 import pytest
 
+from capfuzz_scenes import triangle_scene_file as scene_file   # (the driver's text form: shared with tests/test_tile_fuzz.py)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -55,44 +57,6 @@ def run(exe, *args):
     last = out.strip().splitlines()[-1]
     assert last.startswith("ok ") and " misses=0 " in last + " ", out[-3000:]
     return {k: float(v) for k, v in re.findall(r"(\w+)=([-0-9.e+]+)", last)}
-
-
-class _NoTracer:
-    """make_manager wants a tracer; params() never calls it"""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"the tracer is not to be called ({name})")
-
-
-def scene_file(pkg, api, d, cfg, w, h, part=(8, 0, 1), change=None, tag=""):
-    """the camera block and the models' root leaves of a config as the manager hands them to the library, in the driver's text form:
-    per model the worldToLocal rows as pack_model lays them out, cull (RC:355), and the root leaf's triangles in the builder's order"""
-    sc = pkg.scenes.get(cfg)
-    if change:
-        change(sc)
-    mgr = sc.make_manager(_NoTracer(), api, w, h)
-    p = mgr.params()
-    assert p.defocusStrength == 0.0
-    data = mgr.CreateAllMeshData(mgr.models)
-    info, tris, nodes = data["meshInfo"], data["triangles"], data["nodes"]
-    lines = [f"{w} {h} {part[0]} {part[1]} {part[2]} {p.divergeStrength!r}",
-             " ".join(repr(float(v)) for v in p.camLocalToWorld),
-             " ".join(repr(float(v)) for v in p.viewParams),
-             str(len(mgr.models))]
-    for i, model in enumerate(mgr.models):
-        m = info[i]["worldToLocal"]
-        root = nodes[int(info[i]["nodeOffset"])]
-        n = int(root["triangleCount"])
-        assert n > 0, "the driver's scenes are FLAT: every model's root is a leaf"
-        lines.append(" ".join(repr(float(m[c * 4 + r])) for r in range(3) for c in range(4)))
-        lines.append(f"{int(model.material.flag != pkg.abi.MATERIAL_GLASS)} {n}")
-        first = int(info[i]["triOffset"]) + int(root["startIndex"])
-        for t in tris[first:first + n]:
-            lines.append(" ".join(repr(float(v)) for v in (*t["posA"], *t["posB"], *t["posC"])))
-    path = str(d / f"config{cfg}{tag}_{w}x{h}_{part[1]}of{part[2]}.txt")
-    with open(path, "w") as f:
-        f.write("\n".join(lines) + "\n")
-    return path
 
 
 @pytest.mark.parametrize("seed", [1, 2, 20261019])
