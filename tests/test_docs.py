@@ -21,6 +21,8 @@ def test_coverage_md_cites_tests_and_files_that_exist():
         assert name in src, name
     for f, fn in set(re.findall(r"`(test_[a-z_0-9]+\.py)::(test_[A-Za-z_0-9]+)", text)):
         assert re.search(r"def %s" % re.escape(fn.rstrip("_")), src[f]), (f, fn)
+    for f, fn in set(re.findall(r"`tests/(test_[a-z_0-9]+\.py)::(test_[A-Za-z_0-9]+)", text)):  # the same, cited with the path
+        assert f in src and re.search(r"def %s" % re.escape(fn.rstrip("_")), src[f]), (f, fn)
     for fn in set(re.findall(r"`(test_[a-z_0-9]+_\*?)`", text)) | set(re.findall(r"`(test_[a-z_0-9]+)`", text)):
         stem = fn.rstrip("*")
         if stem.endswith(".py") or stem + ".py" in src:

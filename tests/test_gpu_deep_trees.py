@@ -1,0 +1,455 @@
+"""The BVH traversal stack at its exact bound, on every kernel that takes its LDS layout from the scene's tree height.
+
+tests/deep_trees.py makes trees in which most camera rays push at EVERY level: a launch with `max_height` stack rows has its last row
+written by them, and the row behind it is pixel-field row 0 (the trace and cost kernels' bookkeeping, the query and radiance kernels' ray
+index), or — behind the pixel fields — the candidate-mask summary of the scenes with more than 64 models.  tests/test_deep_trees.py
+asserts, without a GPU, that the heights are exact and that the rays are there.  Everything here is compared bit for bit with the oracle
+(oracle/rt_oracle.cpp, a stack of 64), and — up to the height the reference's driver lets reach its `int stack[32]`, 30 — with the
+reference's text compiled as C++ where it travelled:
+
+  a. rt_render_frame(s): combs of height 1, 2, 30, 31 and 32, inner child on either side, tied, from behind, with a shared subtree — as
+     single-wave workgroups, as the default groups, with a 16-record cache and with two further group sizes; the launch's own report
+     (RT_DEBUG_LAUNCH) must name exactly H stack entries;
+  b. comb(32) beside a cube, and inside scenes of 65 and 97 models (the > 64-model instantiation), in both model orders;
+  c. rt_render_cost, rt_render_aov, rt_render_aov_centre, rt_query_closest / _occluded, rt_radiance_trace and rt_debug_intersect on
+     comb(32), comb_tied(32) and the 65-model scene, the query batches with a whole wave of witness rays;
+  d. a refused upload (33 levels) leaves the context rendering its previous scene;
+  e. the 40-triangle mesh that the builders take to depth 32: rt_build_bvh_gpu(_batch) against the host builder, and rendered."""
+import ctypes as C
+import re
+import time
+
+import numpy as np
+import pytest
+
+import deep_trees as dt
+import motion_reference as mref
+import radiance_reference as rr
+import test_gpu_aov as ta
+import test_gpu_cost_view as tc
+import test_gpu_fuzz as tf
+import test_gpu_query as tq
+from test_deep_trees import CONE_SCALE, cone_camera, cone_mesh
+from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+F3 = C.c_float * 3
+W, H = dt.W, dt.H_IMG
+FRAME = 3
+WITNESS = (H // 2, W // 2)  # the pixel whose ray fills a whole wave of the query batches
+
+_SCENES, _ORACLE, _REF = {}, {}, {}
+
+
+# ---------------------------------------------------------------- scenes
+def crowd(pkg, n, seed=3):
+    """n small models between the camera and the comb and beside it: cubes, rounded cubes and quads, every fourth glass, every ninth
+    emitting (tests/test_gpu_fuzz.py::crowded_scene's mix, placed for deep_trees.camera)"""
+    rng = np.random.default_rng(seed)
+    M, T = pkg.RayTracingMaterial, pkg.Transform
+    meshes = [pkg.meshes.cube(), pkg.meshes.rounded_cube(3), pkg.meshes.quad()]
+    return [pkg.Model(meshes[i % 3], M(flag=int(i % 4 == 3) * 2, diffuseCol=tuple(rng.uniform(0.2, 1, 3)) + (1,), ior=1.4,
+                                       emissionStrength=float(i % 9 == 0) * 3.0, emissionCol=(1, 0.9, 0.7, 1)),
+                      T((float(rng.uniform(-2.5, 2.5)), float(rng.uniform(-1.6, 1.6)), float(rng.uniform(2.0, 3.6))), tuple(rng.uniform(0, 360, 3)),
+                        float(rng.uniform(0.12, 0.35))))
+            for i in range(n)]
+
+
+def scene(pkg, name):
+    """comb<H><form>[-diffuse] | tied32 | behind32 | shared32 | cube_first | cube_last | crowd<N>_first | crowd<N>_last"""
+    if name in _SCENES:
+        return _SCENES[name]
+    abi = pkg.abi
+    cam = None
+    m = re.fullmatch(r"comb(\d+)(A|B|alternate)(-diffuse)?", name)
+    if m:
+        mesh = dt.HandMesh(name, *dt.comb(abi, int(m.group(1)), m.group(2)))
+        models = dt.tree_models(pkg, mesh, "diffuse" if m.group(3) else "glass")
+    elif name == "tied32":
+        models = dt.tree_models(pkg, dt.HandMesh(name, *dt.comb_tied(abi, 32)))
+    elif name == "behind32":
+        models, cam = dt.tree_models(pkg, dt.HandMesh(name, *dt.comb_behind(abi, 32))), dt.camera(pkg, behind=True)
+    elif name == "shared32":
+        models = dt.tree_models(pkg, dt.HandMesh(name, *dt.shared(abi, 16, 16)))
+    else:
+        comb = pkg.Model(dt.HandMesh("comb32", *dt.comb(abi, 32, "alternate")), dt.materials(pkg)["glass"], pkg.Transform())
+        kind, order = name.split("_")
+        if kind == "cube":
+            others = [pkg.Model(pkg.meshes.cube(), dt.materials(pkg)["diffuse"], pkg.Transform((0.8, -0.5, 3.0), (20, 30, 0), 0.9))]
+        else:
+            others = crowd(pkg, int(kind[5:]) - 1)
+        models = [comb] + others if order == "first" else others[::-1] + [comb]
+    _SCENES[name] = dt.description(pkg, name, models, cam)
+    return _SCENES[name]
+
+
+def height_of(name):
+    m = re.match(r"comb(\d+)", name)
+    return int(m.group(1)) if m else 32
+
+
+def render(lib, tr, desc, stats=False, seed=9):
+    """Two frames, the first with the pixel-centre rays the witness shares were computed for, the second jittered: both render targets,
+    the seven counters, the STATS build's filter audit and cache count.  lib: what builds the ordinary meshes and the view parameters."""
+    if stats:
+        tr.enable_stats(True)
+    mgr = desc.make_manager(tr, lib)
+    mgr.OnEnable(renderSeed=seed)
+    mgr.RenderFrame()
+    mgr.divergeStrength = 0.7
+    mgr.RenderFrame()
+    c = tr.counters()
+    prof = tr.phase_profile() if stats else None
+    out = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in tf.KEYS],
+               viol=prof["filter_violations"][0] if stats else 0, hot=prof["inner_from_lds_cache"][0] if stats else None)
+    tr.close()
+    return out
+
+
+def oracle_render(pkg, orc, name):
+    if name not in _ORACLE:
+        _ORACLE[name] = render(orc, orc.create_tracer(8), scene(pkg, name))
+    return _ORACLE[name]
+
+
+def ref_lib():
+    """The reference's text compiled as C++ (oracle/_ref/libref.so), or None where it did not travel"""
+    if "lib" not in _REF:
+        import __graft_entry__ as graft
+        _REF["lib"] = graft.load_ref()
+    return _REF["lib"]
+
+
+def same(a, b):
+    return np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def assert_render(got, want, what, stats):
+    assert same(got["acc"], want["acc"]), f"{what}: accumulated image differs in {int((got['acc'] != want['acc']).any(axis=-1).sum())} pixels"
+    assert same(got["frame"], want["frame"]), f"{what}: last frame differs in {int((got['frame'] != want['frame']).any(axis=-1).sum())} pixels"
+    if stats:
+        assert got["counters"] == want["counters"], (what, dict(zip(tf.KEYS, got["counters"])), dict(zip(tf.KEYS, want["counters"])))
+        assert got["viol"] == 0, what
+    else:  # the shipped instantiation counts segments and pixel frames only
+        for k in ("segments", "pixelFrames"):
+            assert got["counters"][tf.KEYS.index(k)] == want["counters"][tf.KEYS.index(k)], (what, k)
+
+
+LAUNCH = re.compile(r"kernel variant (\d+): (\d+) stack entries, (\d+) B of LDS per workgroup of (\d+) threads \((\d+) B of it the top-of-tree cache: (\d+) records\)")
+
+
+def launches(capfd):
+    """(variant, stack entries, LDS bytes, threads, cache records) of every launch shape reported since the last call"""
+    return [tuple(int(g) for g in (m.group(1), m.group(2), m.group(3), m.group(4), m.group(6))) for m in LAUNCH.finditer(capfd.readouterr().err)]
+
+
+# ---------------------------------------------------------------- a. the trace kernels
+SHAPES = [("single", {"RT_HOT_KB": "0"}), ("default", {}), ("cache16", {"RT_HOT_KB": "1"}), ("groups8", {"RT_WAVES_PER_GROUP": "8"}),
+          ("groups4", {"RT_WAVES_PER_GROUP": "4"})]
+TRACE_SCENES = ([f"comb{h}{form}" + ("-diffuse" if form == "B" else "") for h in (1, 2, 30, 31, 32) for form in ("A", "B", "alternate")] +
+                ["comb32A-diffuse", "comb32B", "comb32alternate-diffuse", "tied32", "behind32", "shared32"])
+
+
+@pytest.mark.parametrize("name", TRACE_SCENES)
+def test_trace_kernels_fill_the_last_stack_row(pkg, api, orc, name, monkeypatch, capfd):
+    desc, height = scene(pkg, name), height_of(name)
+    want = oracle_render(pkg, orc, name)
+    assert want["counters"][tf.KEYS.index("innerSteps")] > 0 and np.isfinite(want["acc"]).all() and want["acc"][..., :3].any()
+    t0 = time.perf_counter()
+    monkeypatch.setenv("RT_DEBUG_LAUNCH", "1")
+    monkeypatch.delenv("RT_LAYOUT", raising=False)
+    seen = {}
+    for shape, env in SHAPES:
+        for k in ("RT_HOT_KB", "RT_WAVES_PER_GROUP"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        capfd.readouterr()
+        for stats in (False, True):
+            got = render(api, api.create_tracer(0), desc, stats)
+            assert_render(got, want, f"{name}, {shape}, {'stats' if stats else 'shipped'} build", stats)
+        reported = launches(capfd)
+        assert reported and {r[1] for r in reported} == {height}, (name, shape, reported)
+        # what rt_launch_plan.h's arithmetic gives a wave: (stack + 4 pixel fields) x 64 dwords; the rest of a workgroup's LDS is the cache
+        for variant, stack, lds, threads, records in reported:
+            assert lds == records * 64 + (threads // 64) * (stack + 4) * 256, (name, shape, reported)
+        seen[shape] = sorted({(r[3], r[4]) for r in reported})
+        if shape == "single":
+            assert seen[shape] == [(64, 0)], (name, seen)
+        if shape == "cache16" and height == 30:  # 16 records of 30 pairs: a walk alternates between the LDS copy and global memory
+            assert seen[shape][0][1] == 16 and 0 < got["hot"] < want["counters"][tf.KEYS.index("innerSteps")], (name, seen, got["hot"])
+        if shape == "default" and height <= 30:
+            assert seen[shape][0][0] > 64 and got["hot"] > 0, (name, seen, got["hot"])
+    line = f"{name}: height {height}, stack entries reported {height}; (threads, cache records) per shape {seen}"
+    ref = ref_lib() if height <= 31 else None  # never at 32: the reference's int stack[32] stands at H + 1 entries
+    if ref is not None:
+        try:
+            # (the reference's dispatcher has no builder and no view parameters: the oracle's serve the manager)
+            got = render(orc, ref.create_tracer(4), desc)
+        except pkg.abi.RtError as e:
+            # the reference's driver (oracle/ref_driver.h) counts the root as a level and lets at most 31 reach the text: height 31 is its 32nd
+            assert height == 31 and "int stack[32]" in str(e), (name, str(e))
+            line += "; reference text: refused by its driver's guard"
+        else:
+            assert height <= 30
+            assert same(got["acc"], want["acc"]) and same(got["frame"], want["frame"]), f"{name}: the reference's text differs from the oracle"
+            for k in ("segments", "innerSteps", "triTests"):  # its own two statistics (RC:254, RC:271) and the segments
+                assert got["counters"][tf.KEYS.index(k)] == want["counters"][tf.KEYS.index(k)], (name, k)
+            line += "; reference text: same bits"
+    else:
+        line += "; reference text: not compared" + (" (never at 32)" if height == 32 else " (not here)")
+    print(f"{line}; {time.perf_counter() - t0:.1f} s")
+
+
+# ---------------------------------------------------------------- b. mixed heights and more than 64 models
+@pytest.mark.parametrize("kind", ["cube", "crowd65", "crowd97"])
+def test_comb_32_beside_other_models_in_both_orders(pkg, api, orc, kind, monkeypatch, capfd):
+    monkeypatch.setenv("RT_DEBUG_LAUNCH", "1")
+    t0 = time.perf_counter()
+    lines = []  # (printed at the end: reading the launch reports takes what was printed before with it)
+    for order in ("first", "last"):
+        name = f"{kind}_{order}"
+        desc = scene(pkg, name)
+        n_models = len(desc.models)
+        want = oracle_render(pkg, orc, name)
+        assert want["counters"][tf.KEYS.index("modelVisits")] == want["counters"][tf.KEYS.index("segments")] * n_models
+        for shape, env in (("default", {}), ("cache", {"RT_LAYOUT": "pre,arena,cache"}), ("single", {"RT_HOT_KB": "0"})):
+            for k in ("RT_HOT_KB", "RT_LAYOUT"):
+                monkeypatch.delenv(k, raising=False)
+            for k, v in env.items():
+                monkeypatch.setenv(k, v)
+            capfd.readouterr()
+            for stats in (False, True):
+                got = render(api, api.create_tracer(0), desc, stats)
+                assert_render(got, want, f"{name}, {shape}, {'stats' if stats else 'shipped'} build", stats)
+            assert got["counters"][tf.KEYS.index("modelVisits")] == got["counters"][tf.KEYS.index("segments")] * n_models
+            reported = launches(capfd)
+            assert reported and {r[1] for r in reported} == {32}, (name, shape, reported)
+            ext = 0 if n_models <= 64 else (n_models - 63 + 31) // 32
+            for variant, stack, lds, threads, records in reported:
+                assert (variant in (4, 5, 10, 11)) == (n_models > 64), (name, reported)  # the > 64-model instantiations
+                assert lds == records * 64 + (threads // 64) * (32 + 4 + (2 + ext if ext else 0)) * 256, (name, shape, reported)
+            if kind == "crowd65" and shape == "cache":  # the one deep shape with a cache: 8 waves around 16 records (tests/test_launch_plan.py)
+                assert sorted({(r[3], r[4]) for r in reported}) == [(512, 16)] and got["hot"] > 0, (name, reported, got["hot"])
+            lines.append(f"{name}, {shape}: {n_models} models, stack entries reported 32, (variant, threads, cache records) {sorted({(r[0], r[3], r[4]) for r in reported})}")
+    print("\n".join(lines + [f"{kind}: {time.perf_counter() - t0:.1f} s, the oracle's renders included"]))
+
+
+# ---------------------------------------------------------------- c. the other kernels
+SIDE_SCENES = ["comb32alternate", "tied32", "crowd65_first"]
+
+
+@pytest.fixture()
+def named_scenes(pkg, monkeypatch):
+    """tests/test_gpu_aov.py's and tests/test_gpu_cost_view.py's helpers take a scene by name through their scene_of"""
+    monkeypatch.setattr(ta, "scene_of", scene)
+    monkeypatch.setattr(tc, "scene_of", scene)
+
+
+def witness_batch(pkg, api, orc, name, p):
+    """130 of the image's restated camera rays (frame FRAME, no jitter): 33 pixels, the witness pixel 64 times over — a whole wave on the
+    last stack row, whatever block the batch is cut into — and 33 more.  Returns the pixel indices, origins, directions, generator states."""
+    origins, dirs, states = rr.camera_rays(orc, p, W, H, FRAME)
+    flat = np.arange(W * H)
+    wit = WITNESS[0] * W + WITNESS[1]
+    idx = np.concatenate([flat[5::11][:33], np.full(64, wit), flat[2::11][:33]])
+    assert len(idx) == 130
+    o, d, s = origins.reshape(-1, 3)[idx], dirs.reshape(-1, 3)[idx], states.reshape(-1)[idx]
+    mesh = scene(pkg, name).models[0].Mesh  # model 0: the tree, untransformed
+    occ, _ = dt.occupancy(mesh.nodes, o[40], d[40], mesh.tris, cull=False)
+    assert occ == 32, (name, occ)
+    return idx, o, d, s
+
+
+@pytest.mark.parametrize("name", SIDE_SCENES)
+def test_cost_view_of_deep_trees(pkg, api, orc_log, named_scenes, name):  # noqa: F811
+    t0 = time.perf_counter()
+    for frame in (1, 2):
+        got = tc.gpu_cost(pkg, api, name, W, H, frame)
+        want = tc.oracle_cost(pkg, orc_log, name, W, H, frame)
+        tc.assert_cost_equal(got, want, f"{name}, frame {frame}")
+        # a witness ray's first segment: 32 inner steps down model 0's comb at the least
+        assert want[WITNESS][4] >= 32, want[WITNESS].tolist()
+    print(f"{name}: rt_render_cost, {time.perf_counter() - t0:.1f} s")
+
+
+@pytest.mark.parametrize("name", SIDE_SCENES)
+def test_aov_passes_of_deep_trees(pkg, api, orc, named_scenes, name):
+    tr, ot = api.create_tracer(0), orc.create_tracer(1)
+    try:
+        su = ta.Setup(pkg, api, tr, name, W, H)
+        so = ta.Setup(pkg, orc, ot, name, W, H)
+        for which in ("rt_render_aov", "rt_render_aov_centre"):
+            if which == "rt_render_aov":
+                su.mgr.divergeStrength = so.mgr.divergeStrength = 0.7  # jittered rays for the frame's pass, the centre pass has none
+                p = su.params(FRAME)
+                tr.set_params(p)
+                aov = tr.render_aov(FRAME)
+                origins, dirs = ta.camera_rays(orc, p, W, H, FRAME)
+            else:
+                p = su.params(1)
+                aov = tr.render_aov_centre()
+                origins, dirs = mref.centre_rays(orc, p, W, H)
+            assert aov.shape == (H, W) and aov.dtype == pkg.abi.AOV_DTYPE
+            want = ta.oracle_records(pkg, orc, ot, so, p, origins, dirs, aov["object"])
+            want["triangle"] = aov["triangle"]  # (checked below, as tests/test_gpu_aov.py checks it)
+            ta.assert_records_equal(aov, want, f"{name}: {which}")
+            hit = aov["hit"] & 3
+            assert np.array_equal(aov["object"] >= 0, hit != 0) and (hit != 0).mean() > 0.5
+            assert ta.check_triangles(orc, so, aov, origins, dirs) > W * H // 4, "model 0 (untransformed) must be what most pixels see"
+            dbg = tr.debug_intersect(origins.reshape(-1, 3), dirs.reshape(-1, 3)).reshape(H, W, 10)
+            assert dbg[..., 2].view(np.uint32).tolist() == aov["dst"].view(np.uint32).tolist(), which
+            assert dbg[..., 3:6].view(np.uint32).tolist() == aov["normal"].view(np.uint32).tolist(), which
+    finally:
+        tr.close()
+        ot.close()
+
+
+@pytest.mark.parametrize("name", SIDE_SCENES)
+def test_ray_queries_and_radiance_with_a_wave_of_witness_rays(pkg, api, orc, named_scenes, name):
+    abi = pkg.abi
+    tr, ot = api.create_tracer(0), orc.create_tracer(1)
+    try:
+        su = ta.Setup(pkg, api, tr, name, W, H)
+        ta.Setup(pkg, orc, ot, name, W, H)
+        p = su.params(FRAME)
+        tr.set_params(p)
+        ot.set_params(p)
+        idx, o, d, states = witness_batch(pkg, api, orc, name, p)
+        n = len(idx)
+        want10 = tq.oracle_hits(orc, ot, o, d)
+        hit = want10[:, 0] != 0
+        assert hit[33:97].all() and hit.sum() >= 100
+        dbg = tr.debug_intersect(o, d)
+        guard = 64
+        for what, order in (("in order", np.arange(n)), ("reversed", np.arange(n)[::-1])):
+            rays = abi.make_rays(o[order], d[order])
+            # ---- closest hit: every field against the oracle's function and against rt_debug_intersect
+            got = tr.query_closest(rays)
+            tq.assert_same_records(got, tq.records_from_oracle(pkg, None, want10[order], got["object"], got["triangle"]), f"{name}, {what}")
+            assert not got["reserved"].any()
+            assert (got["object"][hit[order]] >= 0).all() and (got["triangle"][hit[order]] >= 0).all()
+            assert tq.bits(dbg[order, 2]).tolist() == tq.bits(got["dst"]).tolist()
+            assert tq.bits(dbg[order, 3:6]).tolist() == tq.bits(got["normal"]).tolist() and tq.bits(dbg[order, 6:9]).tolist() == tq.bits(got["pos"]).tolist()
+            assert np.array_equal(dbg[order, 0] != 0, (got["hit"] & 3) != 0) and np.array_equal(dbg[order, 1] != 0, (got["hit"] & 0x100) != 0)
+            # the 64 witness slots hold one and the same record
+            w64 = got[33:97] if what == "in order" else got[n - 97:n - 33]
+            assert len({r.tobytes() for r in w64}) == 1
+            # ---- the buffer form, with guard words behind the last record
+            d_rays, d_hits = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 48 + guard, fill=0xa5)
+            tr.query_closest_buffers(d_rays.ptr, n, d_hits.ptr)
+            tr.synchronize()
+            raw = d_hits.download(np.uint8)
+            assert raw[:n * 48].tobytes() == got.tobytes() and (raw[n * 48:] == 0xa5).all(), (name, what)
+            # ---- occlusion below tmax = +inf, d, d / 2
+            dist = np.where(hit, want10[:, 2], F(1)).astype(F)[order]
+            for tname, tmax in (("+inf", np.full(n, np.inf, dtype=F)), ("d", dist), ("d / 2", dist / F(2))):
+                occ = tr.query_occluded(abi.make_rays(o[order], d[order], tmax=tmax))
+                wanted = (hit[order] & (want10[order, 2] < tmax)).astype(np.uint32)
+                assert np.array_equal(occ, wanted), (name, what, tname, np.argwhere(occ != wanted).ravel()[:5])
+                d_occ = tq.DevBuf(n * 4 + guard, fill=0xa5)
+                d_rays.upload(abi.make_rays(o[order], d[order], tmax=tmax))
+                tr.query_occluded_buffers(d_rays.ptr, n, d_occ.ptr)
+                tr.synchronize()
+                raw = d_occ.download(np.uint8)
+                assert raw[:n * 4].tobytes() == occ.tobytes() and (raw[n * 4:] == 0xa5).all(), (name, what, tname)
+                d_occ.free()
+                if tname == "+inf":
+                    assert occ[hit[order]].all()
+                else:
+                    assert not occ.any()  # nothing lies strictly below the closest hit's distance, or half of it
+            d_rays.free(), d_hits.free()
+        # ---- rt_radiance_trace: the same rays with their generator states against oracle_trace_pixel
+        want_rgb = np.zeros((n, 3), dtype=F)
+        o3 = F3()
+        for k, i in enumerate(idx):
+            orc.trace_pixel(ot.h, int(i % W), int(i // W), FRAME, o3)
+            want_rgb[k] = o3[:]
+        assert np.isfinite(want_rgb).all() and want_rgb.any()
+        for what, order in (("in order", np.arange(n)), ("reversed", np.arange(n)[::-1])):
+            got = tr.radiance_trace(abi.make_path_rays(o[order], d[order], states[order]))
+            bad = np.argwhere((rr.bits(got["rgb"]) != rr.bits(want_rgb[order])).any(axis=1)).ravel()
+            assert not len(bad), f"{name}, rt_radiance_trace {what}: {len(bad)} of {n} rays differ; first is ray {bad[0]}: got {got['rgb'][bad[0]]}, want {want_rgb[order][bad[0]]}"
+            assert (got["rng"] != states[order]).any()
+    finally:
+        tr.close()
+        ot.close()
+
+
+# ---------------------------------------------------------------- d. a refused upload
+def test_refused_upload_of_33_levels_leaves_the_context_usable(pkg, api, orc):
+    desc = scene(pkg, "comb32alternate")
+    bad = dt.one_model(pkg, *dt.comb(pkg.abi, 33))
+    frames = []
+    for lib, tr in ((api, api.create_tracer(0)), (orc, orc.create_tracer(8))):
+        mgr = desc.make_manager(tr, lib)
+        mgr.OnEnable(renderSeed=4)
+        mgr.RenderFrame()
+        first = tr.read_accumulated().copy()
+        if lib is api:
+            with pytest.raises(pkg.abi.RtError) as e:
+                tr.upload_scene(*bad, None)
+            assert e.value.status == pkg.abi.RT_ERR_SCENE and "BVH depth 33 > 32" in str(e.value), str(e.value)
+        mgr.RenderFrame()
+        frames.append((first, tr.read_accumulated(), tr.read_frame(), tr.counters()["segments"]))
+        tr.close()
+    (a1, a2, af, sa), (b1, b2, bf, sb) = frames
+    assert same(a1, b1) and same(a2, b2) and same(af, bf) and sa == sb and not same(a1, a2)
+
+
+# ---------------------------------------------------------------- e. the builder's depth-32 mesh
+def cone_scene(pkg, where):
+    v, nrm, idx = cone_mesh()
+    cone = pkg.meshes.Mesh(v, nrm, idx, "cone")
+    mats = dt.materials(pkg)
+    models = [pkg.Model(cone, mats["glass"], pkg.Transform((0, 0, 0), (0, 0, 0), CONE_SCALE)),
+              pkg.Model(cone, mats["diffuse"], pkg.Transform((0.3, 0.4, 1.0), (0, 0, 25), CONE_SCALE)),
+              pkg.Model(pkg.meshes.cube(), mats["emitter"], pkg.Transform((3.0, -2.5, 0.5), (0, 30, 0), 1.5))]
+    return pkg.scenes.SceneDescription("cone_" + where, W, H, 2, dict(dt.SETTINGS), cone_camera(pkg, where), models, [])
+
+
+def test_gpu_builder_takes_the_cone_to_depth_32_and_the_scene_renders_the_same_bits(pkg, api, orc, monkeypatch, capfd):
+    v, nrm, idx = cone_mesh()
+    nodes, tris, stats = api.build_bvh_arrays(v, nrm, idx, 1)
+    assert stats["leafDepthMax"] == 32
+    stats.pop("timeMs")
+    n2, t2, s2 = api.build_bvh_arrays_gpu(v, nrm, idx, 1)
+    s2.pop("timeMs")
+    assert n2.tobytes() == nodes.tobytes() and t2.tobytes() == tris.tobytes() and s2 == stats
+    # between two ordinary meshes in one batch
+    before, after = pkg.meshes.rounded_cube(4), pkg.meshes.icosphere(2, 1.0, 5)
+    nb, tb, per = api.build_bvh_arrays_gpu_batch([(m.vertices, m.normals, m.triangles) for m in (before, pkg.meshes.Mesh(v, nrm, idx), after)], 1)
+    host = [api.build_bvh_arrays(m.vertices, m.normals, m.triangles, 1) for m in (before, after)]
+    host.insert(1, (nodes, tris, dict(stats)))
+    ends = [per[k + 1][:2] if k + 1 < len(per) else (len(nb), len(tb)) for k in range(3)]
+    for k, ((n_off, t_off, s), (hn, ht, hs), (n_end, t_end)) in enumerate(zip(per, host, ends)):
+        s.pop("timeMs"), hs.pop("timeMs", None)
+        assert nb[n_off:n_end].tobytes() == hn.tobytes() and tb[t_off:t_end].tobytes() == ht.tobytes() and s == hs, k
+    # rendered: the trees built on the GPU, against the oracle with its own builder
+    monkeypatch.setenv("RT_DEBUG_LAUNCH", "1")
+    lines = []
+    for where in ("apex", "outside"):
+        desc = cone_scene(pkg, where)
+        want = render(orc, orc.create_tracer(8), desc)
+        assert np.isfinite(want["acc"]).all() and want["acc"][..., :3].any()
+        capfd.readouterr()
+        for stats_on in (False, True):
+            tr = api.create_tracer(0)
+            if stats_on:
+                tr.enable_stats(True)
+            mgr = desc.make_manager(tr, api)
+            mgr.bvhOnGpu = True
+            mgr.OnEnable(renderSeed=9)
+            mgr.RenderFrame()
+            mgr.divergeStrength = 0.7
+            mgr.RenderFrame()
+            c = tr.counters()
+            got = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in tf.KEYS],
+                       viol=tr.phase_profile()["filter_violations"][0] if stats_on else 0)
+            tr.close()
+            assert_render(got, want, f"cone from {where}, {'stats' if stats_on else 'shipped'} build", stats_on)
+        reported = launches(capfd)
+        assert reported and {r[1] for r in reported} == {32}, reported
+        lines.append(f"cone from {where}: stack entries reported 32, {want['counters'][tf.KEYS.index('innerSteps')]} inner steps")
+    print("\n".join(lines))

@@ -138,6 +138,45 @@ def test_variant_slots_and_lds(plan):
     assert shapes[keys.index((False, False, True, False))]["lds"] == 1792 * 16 + 12 * 24 * 256
 
 
+@pytest.mark.parametrize("stack", [1, 31, 32])
+def test_lds_of_the_shallowest_and_the_deepest_stacks(plan, stack):
+    """Stack heights 1, 31 and 32 = RT_MAX_BVH_DEPTH (tests/test_deep_trees.py: the trees that fill them): a wave's region is exactly
+    [stack][64] stack rows + [RT_PIXEL_FIELDS = 4][64] pixel fields + — more than 64 models — [2 + ext][64] mask extension, and a
+    workgroup's LDS the cache plus its waves' regions: the arithmetic of wave_lds_bytes, for the single-wave, hot and MANY shapes."""
+    reqs, keys = [], []
+    for ext in (0, 1, 3, 32):
+        for hot in (0, 64, 1792):
+            for stats in (False, True):
+                reqs.append(("shape", dict(flat=False, stats=stats, stack=stack, ext=ext, chunks=5 if ext else 0, hot=hot, wpg=12, pool=64, poolwaves=16,
+                                           minitems=10**6, cus=CUS, tiles=96, frames=2)))
+                keys.append((ext, hot))
+    for (ext, hot), s in zip(keys, plan(*reqs)):
+        rows = stack + 4 + (2 + ext if ext else 0)
+        assert s["wavedwords"] == rows * 64, (stack, ext, hot, s)
+        assert s["wpg"] == (12 if hot else 1) and s["threads"] == 64 * s["wpg"], (stack, ext, hot, s)
+        assert s["hotunits"] == hot and s["lds"] == hot * 16 + s["wpg"] * rows * 64 * 4, (stack, ext, hot, s)
+        assert (bool(s["many"]), bool(s["hot"])) == (ext > 0, hot > 0)
+    # and plan_groups sizes the cache from the same wave region (DESIGN.md, "Which workgroup shape a launch gets"): as many waves as a
+    # CU's 160 KB hold, 24 at the most, in whole groups of at most `want`; a group's share less 1 KB and its waves is the cache, and
+    # fewer than 16 records are not worth a group.  1, 97 and 2,000 models: 0, 2 and 32 extension words.
+    seen = {}
+    for models, ext in ((1, 0), (97, 2), (2000, 32)):
+        for asked in (12, 8, 4):
+            wave = (stack + 4 + (2 + ext if ext else 0)) * 256
+            per_cu = min(24, 160 * 1024 // wave)
+            want = next(w for w in range(asked, 0, -1) if per_cu % w == 0)
+            records = max(0, 160 * 1024 // (per_cu // want) - 1024 - want * wave) // 64
+            g = one(plan, "groups", height=stack, models=models, want=asked)
+            assert g == ({"wpg": want, "records": records} if records >= 16 else {"wpg": 1, "records": 0}), (stack, models, asked, g, want, records)
+            seen[models, asked] = g["wpg"]
+    # what that means for the deepest trees: with up to 64 models, stacks of 31 and 32 rows leave no room for a cache, whatever group size
+    # is asked for (18 or 17 waves per CU: no whole groups with room to spare) — such scenes run as single-wave workgroups; the two
+    # extension rows of 65 ... 94 models make it 16 waves again: groups of 8 around 16 records under a 32-row stack
+    # (tests/test_gpu_deep_trees.py reads both from the launch's own report)
+    assert [seen[1, asked] for asked in (12, 8, 4)] == ([1, 1, 1] if stack >= 31 else [12, 8, 4])
+    assert one(plan, "groups", height=32, models=65, want=12) == {"wpg": 8, "records": 16}
+
+
 def test_group_plan_shares_the_filter_rule(plan):
     f = plan(*[("filter", dict(models=m)) for m in (1, 64, 65, 95, 96, 1087, 1088, 5000)])
     assert [(x["nf"], x["ext"]) for x in f] == [(1, 0), (64, 0), (65, 1), (95, 1), (96, 2), (1087, 32), (1087, 32), (1087, 32)]

@@ -193,6 +193,36 @@ def test_hand_made_refusals_under_the_sanitizer(pkg, drivers, base_scene, sequen
         assert (g["rc"] == 0 and g["n_pairs"] > 0) or (g["rc"] == RT_ERR_SCENE and ("out of bounds" in g["msg"] or "two different nodeOffsets" in g["msg"])), g
 
 
+def test_depth_bound_under_the_sanitizer(pkg, api, drivers):
+    """tests/deep_trees.py's hand-made trees through the sanitized driver: heights 1, 31 and 32 accepted at exactly their height, 33 and 34
+    refused — by the check behind the walk and by the walk's own — and so the trees whose depth comes from the memo of converted pairs;
+    every verdict and message the library's (tests/test_deep_trees.py asserts those)."""
+    import deep_trees as dt
+    a = pkg.abi
+    trees = [("comb1", dt.comb(a, 1)), ("comb31", dt.comb(a, 31, "B")), ("comb32", dt.comb(a, 32, "alternate")), ("tied32", dt.comb_tied(a, 32)),
+             ("comb33", dt.comb(a, 33)), ("comb34", dt.comb(a, 34)), ("shared32", dt.shared(a, 16, 16)), ("shared33", dt.shared(a, 17, 16)),
+             ("shared33b", dt.shared(a, 1, 32))]
+    requests, lib = [], []
+    for name, (tris, nodes) in trees:
+        scene = dt.one_model(pkg, tris, nodes)
+        path = str(drivers["dir"] / f"{name}.scene")
+        write_scene(path, *scene, np.zeros(0, dtype=a.sphere_dtype))
+        requests += [f"load {path}", "validate"]
+        try:
+            lib.append((0, api.validate_scene_arrays(*scene)["max_height"]))
+        except a.RtError as e:
+            lib.append((e.status, str(e)))
+    got = [g for g in ask(drivers["san"], requests) if isinstance(g, dict) and "rc" in g]
+    assert len(got) == len(trees)
+    want = [(0, 1), (0, 31), (0, 32), (0, 32), "model 0: BVH depth 33 > 32", "model 0: BVH deeper than RT_MAX_BVH_DEPTH", (0, 32),
+            "model 0: BVH depth 33 > 32", "model 0: BVH depth 33 > 32"]
+    for (name, _), g, l, w in zip(trees, got, lib, want):
+        if isinstance(w, tuple):
+            assert (g["rc"], g["max_height"]) == w == l, (name, g, l)
+        else:
+            assert g["rc"] == a.RT_ERR_SCENE == l[0] and g["msg"] == w and w in l[1], (name, g, l)
+
+
 # ---------------------------------------------------------------- 5.2 root filter boxes
 def _node(bmin, bmax, start, count):
     n = np.zeros((), dtype=[("boundsMin", "<f4", 3), ("boundsMax", "<f4", 3), ("startIndex", "<i4"), ("triangleCount", "<i4")])
