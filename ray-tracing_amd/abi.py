@@ -121,6 +121,22 @@ def make_path_rays(origins, dirs, rng):
     return r
 
 
+# ---- rt_nee.h ---------------------------------------------------------------
+# RtLightEntry: one entry of the light table (80 bytes), and RtLightTableDump, what rt_debug_light_table hands back
+LIGHT_ENTRY_DTYPE = np.dtype([
+    ("a", "<f4", (3,)), ("size", "<f4"), ("e1", "<f4", (3,)), ("prob", "<f4"), ("e2", "<f4", (3,)), ("object", "<i4"),
+    ("ng", "<f4", (3,)), ("triangle", "<i4"), ("emission", "<f4", (3,)), ("reserved", "<f4")])
+NEE_MAX_LIGHTS = 1 << 22
+assert LIGHT_ENTRY_DTYPE.itemsize == 80
+
+
+class RtLightTableDump(C.Structure):
+    """include/rt_nee.h: the light table of a scene as rt_debug_light_table builds it (freed with rt_debug_light_table_free)."""
+    _fields_ = [
+        ("n_entries", C.c_int32), ("n_sphere_entries", C.c_int32), ("n_triangle_entries", C.c_int32), ("reserved", C.c_int32),
+        ("entries", C.c_void_p), ("cdf", C.c_void_p)]
+
+
 class RtDenoiseParams(C.Structure):
     """include/rt_denoise.h: the parameters of the a-trous filter (32 bytes; struct_size is the handshake)."""
     _fields_ = [

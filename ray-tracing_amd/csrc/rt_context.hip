@@ -36,6 +36,7 @@
 #include "../../include/rt_motion.h"
 #include "../../include/rt_query.h"
 #include "../../include/rt_radiance.h"
+#include "../../include/rt_nee.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
@@ -44,6 +45,8 @@
 #include "rt_adaptive_launch.h"
 #include "rt_query_launch.h"
 #include "rt_radiance_launch.h"
+#include "rt_nee_launch.h"
+#include "rt_light_table.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
 #include "rt_launch_plan.h"
@@ -71,8 +74,8 @@ struct HipOrder final : rt_order::Backend {
 };
 
 /* A side pass — a launch that traces outside the render launches, with a counter slot of its own (see "the side passes" above
- * rt_render_aov).  The context has three, in the order rt_synchronize reports them.  words: the slot, RT_COUNTER_FIELDS words made on
- * first use, of which the kernels write the watchdog word alone (the radiance pass also counts its blocks in word 0); unreported: a
+ * rt_render_aov).  The context has four, in the order rt_synchronize reports them.  words: the slot, RT_COUNTER_FIELDS words made on
+ * first use, of which the kernels write the watchdog word alone (the two radiance passes also count their blocks in word 0); unreported: a
  * device-form pass whose watchdog word has not been read back yet; whose / what: the two places where the deferred report differs by
  * pass. */
 struct SidePass {
@@ -81,7 +84,7 @@ struct SidePass {
     const char* whose;
     const char* what;
 };
-enum { SIDE_AOV, SIDE_QUERY, SIDE_RADIANCE, SIDE_COUNT };
+enum { SIDE_AOV, SIDE_QUERY, SIDE_RADIANCE, SIDE_NEE, SIDE_COUNT };
 
 struct RtContext {
     int device = 0;
@@ -222,12 +225,23 @@ struct RtContext {
     int lastLaunched = 0;            /* frames the last launch_frames call really enqueued (flush_pending rolls back the rest) */
     void* dDisplay = nullptr;  /* scratch of the display pass and of the other host reads, kept between calls (grows on demand) */
     size_t displayBytes = 0;
-    /* the side passes (SidePass, above): AOV, ray query, radiance */
+    /* the side passes (SidePass, above): AOV, ray query, radiance, radiance with direct light sampling */
     SidePass side[SIDE_COUNT] = {
         {nullptr, false, "the AOV pass of an rt_render_aov_to_device, rt_denoise_to_device or rt_reproject_accumulated call (or its centre / moving form)", "records or denoised image"},
         {nullptr, false, "the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call", "records or answers"},
         {nullptr, false, "the pass of an rt_radiance_trace_buffers call", "records"},
+        {nullptr, false, "the pass of an rt_nee_trace_buffers call", "records"},
     };
+    /* rt_nee (include/rt_nee.h): the light table.  hCorners: the local-space corners of the uploaded triangles, nine floats each, kept
+     * because rt_update_models can turn any model into an emitter.  The table is rebuilt from the host mirrors by the first call of
+     * rt_nee.h behind an upload or an update that changed something (lightDirty), and its device copy — entries, cdf and per-object
+     * flags in one allocation (rt_nee_launch.h, table_bytes) — is uploaded on the render stream, behind the passes that read the old one. */
+    std::vector<float> hCorners;
+    bool lightDirty = true;
+    int lightSpheres = 0, lightTriangles = 0;
+    rt_nee::TableBytes lightLayout;
+    void* dLightTable = nullptr;
+    size_t lightTableBytes = 0;
     /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand) */
     void* dAovOut = nullptr;
     size_t aovOutBytes = 0;
@@ -614,6 +628,7 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dRays);
     hipFree(ctx->dRayOut);
     for (SidePass& sp : ctx->side) hipFree(sp.words);
+    hipFree(ctx->dLightTable);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
@@ -862,6 +877,13 @@ static int commit_scene(RtContext* ctx, const PreparedScene& ps, const RtContext
     }
     ctx->hModels = ps.hModels;
     ctx->hRootCodes = ps.rootCodes;
+    try {
+        ctx->hCorners.resize((size_t)ps.nTris * 9); /* (ps.srcTris: the caller's array, alive for the upload call this runs in) */
+    } catch (const std::bad_alloc&) {
+        return fail(ctx, RT_ERR_OOM, "rt_upload_scene: out of host memory keeping the triangles' corners");
+    }
+    for (size_t k = 0; k < (size_t)ps.nTris; k++) memcpy(&ctx->hCorners[9 * k], ps.srcTris[k].posA, 36);
+    ctx->lightDirty = true;
     ctx->haveScene = true;
     ctx->tuner.done = getenv("RT_SUSPEND") != nullptr; /* RT_SUSPEND=3|4 pins the threshold (tests, A/B runs) */
     ctx->tuner.decided = ctx->tuner.done ? atoi(getenv("RT_SUSPEND")) : 3;
@@ -978,6 +1000,7 @@ int rt_update_models(RtContext* ctx, const RtModel* models, int n_models)
         if ((rc = refresh_filters(ctx, models, ctx->hSpheres))) { ctx->primaryTris.usable = false; return rc; }
     }
     ctx->hModels.assign(models, models + n_models);
+    ctx->lightDirty = true;
     return RT_OK;
 }
 
@@ -1005,6 +1028,7 @@ int rt_update_spheres(RtContext* ctx, const RtSphere* spheres, int n_spheres)
     ctx->sphereBound = bound;
     if ((rc = stage_upload(ctx, ctx->dMaterials, mats.data(), sizeof(DMaterial) * n_spheres))) { ctx->primaryTris.usable = false; return rc; }
     ctx->hSpheres.assign(spheres, spheres + n_spheres);
+    ctx->lightDirty = true;
     if (ctx->nModels) { /* the filter margins scale with the scene extent, which includes the spheres */
         if ((rc = refresh_filters(ctx, ctx->hModels.data(), ctx->hSpheres))) return rc;
     }
@@ -2254,7 +2278,7 @@ int rt_adaptive_render_frames(RtContext* ctx, int n)
     return RT_OK;
 }
 
-/* ---- the side passes: the AOV pass, the ray queries and the radiance pass -------------------------------------------------------------
+/* ---- the side passes: the AOV pass, the ray queries and the two radiance passes -------------------------------------------------------------
  * Each is ONE launch of a single-wave kernel (rt_kernels.h) on the joined main stream — behind every frame already requested, like every
  * use of the stream that is not a render launch.  A pass is the context's in nothing but the scene, the stream and, where it reads them,
  * the parameters: KArgs from fill_args, the FLAT / MANY / BVH instantiation of its kernel (RT_SCENE_KERNEL), a wave region of the trace
@@ -2424,7 +2448,73 @@ static int radiance_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut
     return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, (float4*)dOut);
 }
 
-/* ---- the host form and the buffer form of the six ray-batch calls ----------------------------------------------------------------------
+/* ---- rt_nee_trace / rt_nee_trace_buffers / rt_nee_light_count (include/rt_nee.h) -----------------------------------
+ * The light table first: rebuilt from the host mirrors when an upload or an update made it stale (rt_light_table.h), its device copy
+ * uploaded through the staging ring on the joined main stream — behind every pass that still reads the old one, in front of the pass
+ * that wants the new one.  A table past the cap stays dirty, so every call reports it. */
+static int nee_refresh_table(RtContext* ctx, const char* call)
+{
+    if (!ctx->lightDirty) return RT_OK;
+    rt_lt::LightTable t;
+    const char* why = "";
+    int rc;
+    try {
+        rc = rt_lt::build(ctx->hModels.data(), ctx->nModels, ctx->hCorners.data(), 9, ctx->nTris, ctx->hSpheres.data(), ctx->nSpheres, t, &why);
+    } catch (const std::bad_alloc&) {
+        return fail(ctx, RT_ERR_OOM, "%s: out of host memory building the light table", call);
+    }
+    if (rc) return fail(ctx, rc, "%s: the light table: %s", call, why);
+    rt_nee::TableBytes tb;
+    if ((rc = rt_nee::table_bytes((long long)t.entries.size(), (long long)t.inTable.size(), &tb, &why))) return fail(ctx, rc, "%s: the light table: %s", call, why);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if ((rc = grow_scratch(ctx, &ctx->dLightTable, &ctx->lightTableBytes, tb.total))) return rc;
+    char* const d = (char*)ctx->dLightTable;
+    /* in pieces (rt_nee::UPLOAD_CHUNK_BYTES): a slot of the pinned ring keeps the largest upload it has seen, and a table can be 335 MB */
+    auto upload = [&](size_t offset, const void* src, size_t bytes) {
+        for (size_t done = 0; done < bytes; done += rt_nee::UPLOAD_CHUNK_BYTES) {
+            const size_t piece = bytes - done < rt_nee::UPLOAD_CHUNK_BYTES ? bytes - done : (size_t)rt_nee::UPLOAD_CHUNK_BYTES;
+            if (int urc = stage_upload(ctx, d + offset + done, (const char*)src + done, piece)) return urc;
+        }
+        return (int)RT_OK;
+    };
+    if ((rc = upload(tb.entries, t.entries.data(), t.entries.size() * sizeof(RtLightEntry)))) return rc;
+    if ((rc = upload(tb.cdf, t.cdf.data(), t.cdf.size() * sizeof(float)))) return rc;
+    if ((rc = upload(tb.flags, t.inTable.data(), t.inTable.size() * sizeof(uint32_t)))) return rc;
+    ctx->lightLayout = tb;
+    ctx->lightSpheres = t.nSphere;
+    ctx->lightTriangles = t.nTriangle;
+    ctx->lightDirty = false;
+    return RT_OK;
+}
+
+/* The side pass of rt_radiance_nee_kernel: radiance_enqueue with the table and the unit -> triangle map of the layout behind it. */
+static int nee_enqueue(RtContext* ctx, const char* call, const void* dRays, int n, void* dOut)
+{
+    if (int rc = nee_refresh_table(ctx, call)) return rc;
+    KArgs a;
+    fill_args(ctx, 1, 1, a);
+    void (*kern)(const KArgs, const float4*, int, float4*, const rtk::NeeTable, const uint32_t*) = RT_SCENE_KERNEL(ctx, rtk::rt_radiance_nee_kernel);
+    a.suspendNum = RT_SUSPEND_NUM; /* (unused: both walks of the pass run to completion) */
+    SidePass& sp = ctx->side[SIDE_NEE];
+    size_t ldsBytes = 0;
+    long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
+    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
+    a.tileQueue = sp.words; /* word 0: a launch of this pass counts no segments there */
+    a.tileQueueBase = 0;
+    const char* const d = (const char*)ctx->dLightTable;
+    rtk::NeeTable lt;
+    lt.entries = (const float4*)(d + ctx->lightLayout.entries);
+    lt.cdf = (const float*)(d + ctx->lightLayout.cdf);
+    lt.inTable = (const uint32_t*)(d + ctx->lightLayout.flags);
+    lt.n = ctx->lightSpheres + ctx->lightTriangles;
+    const long long grid = rt_nee::grid(rt_nee::blocks(n), resident, ctx->gridOverride);
+    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, (float4*)dOut, lt, (const uint32_t*)ctx->dUnitTri);
+}
+
+static int nee_enqueue_host(RtContext* ctx, const void* dRays, int n, void* dOut) { return nee_enqueue(ctx, "rt_nee_trace", dRays, n, dOut); }
+static int nee_enqueue_buffers(RtContext* ctx, const void* dRays, int n, void* dOut) { return nee_enqueue(ctx, "rt_nee_trace_buffers", dRays, n, dOut); }
+
+/* ---- the host form and the buffer form of the eight ray-batch calls ----------------------------------------------------------------------
  * What tells the three kinds of batch apart: the pass and its enqueue function, the size of a ray's output, the buffer form's name for
  * the output pointer, the host form's word for the output, and whether the pass reads the parameters. */
 struct RayBatch {
@@ -2438,6 +2528,8 @@ struct RayBatch {
 static const RayBatch kClosest = {SIDE_QUERY, closest_enqueue, sizeof(RtRayHit), "d_hits", "records", false};
 static const RayBatch kOccluded = {SIDE_QUERY, occluded_enqueue, sizeof(uint32_t), "d_occluded", "answers", false};
 static const RayBatch kRadiance = {SIDE_RADIANCE, radiance_enqueue, sizeof(RtRadiance), "d_out", "records", true};
+static const RayBatch kNee = {SIDE_NEE, nee_enqueue_host, sizeof(RtRadiance), "d_out", "records", true}; /* (two rows: a table error names the call it came from) */
+static const RayBatch kNeeBuffers = {SIDE_NEE, nee_enqueue_buffers, sizeof(RtRadiance), "d_out", "records", true};
 
 /* what the calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch (rt_rd::check_batch is
  * rt_qr::check_batch with an RtRadiance per ray) */
@@ -2500,6 +2592,29 @@ int rt_query_occluded(RtContext* ctx, const RtRay* rays, int n, uint32_t* occlud
 int rt_query_occluded_buffers(RtContext* ctx, const void* d_rays, int n, void* d_occluded) { return rays_to_device(ctx, "rt_query_occluded_buffers", kOccluded, d_rays, n, d_occluded); }
 int rt_radiance_trace(RtContext* ctx, const RtPathRay* rays, int n, RtRadiance* out) { return rays_to_host(ctx, "rt_radiance_trace", kRadiance, rays, n, out); }
 int rt_radiance_trace_buffers(RtContext* ctx, const void* d_rays, int n, void* d_out) { return rays_to_device(ctx, "rt_radiance_trace_buffers", kRadiance, d_rays, n, d_out); }
+int rt_nee_trace(RtContext* ctx, const RtPathRay* rays, int n, RtRadiance* out) { return rays_to_host(ctx, "rt_nee_trace", kNee, rays, n, out); }
+int rt_nee_trace_buffers(RtContext* ctx, const void* d_rays, int n, void* d_out) { return rays_to_device(ctx, "rt_nee_trace_buffers", kNeeBuffers, d_rays, n, d_out); }
+
+int rt_nee_light_count(RtContext* ctx, int* n_sphere_emitters, int* n_triangle_emitters)
+{
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "null context");
+    if (!ctx->haveScene) return fail(ctx, RT_ERR_STATE, "rt_nee_light_count before rt_upload_scene");
+    RT_FLUSH(ctx); /* (the upload goes through the render stream, behind the frames held back) */
+    if (int rc = nee_refresh_table(ctx, "rt_nee_light_count")) return rc;
+    if (n_sphere_emitters) *n_sphere_emitters = ctx->lightSpheres;
+    if (n_triangle_emitters) *n_triangle_emitters = ctx->lightTriangles;
+    return RT_OK;
+}
+
+int rt_debug_light_table(const RtModel* models, int n_models, const RtTriangle* triangles, int n_triangles, const RtSphere* spheres, int n_spheres,
+                         RtLightTableDump* out)
+{
+    const char* why = "";
+    const int rc = rt_lt::dump(models, n_models, triangles, n_triangles, spheres, n_spheres, out, &why);
+    return rc ? fail(nullptr, rc, "rt_debug_light_table: %s", why) : RT_OK;
+}
+
+void rt_debug_light_table_free(RtLightTableDump* d) { rt_lt::dump_free(d); }
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main

@@ -34,6 +34,7 @@
 #include "../../include/rt_math.h"
 #include "rt_device.h"
 #include "rt_tile_cand.h"
+#include "rt_nee_launch.h"
 
 /* Tuning knobs (values measured on MI355X). */
 /* traverse() is left once active <= entered * NUM/DEN lanes are still traversing */
@@ -1784,6 +1785,268 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
 #undef RT_COST_SLOT
 #undef PXU
 #undef PXF
+}
+
+/* rt_nee_trace* (include/rt_nee.h): rt_radiance_kernel's paths with one emitter sampled directly at every diffuse vertex.  The
+ * header defines every operation below; what is said here is how the wave runs it.
+ * The light table as the kernel reads it (one device allocation, rt_nee_launch.h): n entries of five float4 (RtLightEntry), their cdf,
+ * and one word per object that says whether it has an entry (amendment 3). */
+struct NeeTable {
+    const float4* entries;
+    const float* cdf;
+    const uint32_t* inTable;
+    int n;
+};
+
+/* Amendment 2 for one lane: the three draws, the entry, the direction and the weight.  Returns whether a shadow walk is wanted; then
+ * omega is its direction (its origin is x), g the scalar the header names, Le the entry's emission and (obj, tri) what the closest hit
+ * has to be. */
+__device__ __forceinline__ bool nee_sample(const NeeTable& lt, uint32_t* rng, const rt_f3 x, const rt_f3 n, rt_f3& omega, float& g, rt_f3& Le, int& obj, int& tri)
+{
+    const float u0 = rt_random_value(rng);
+    const float u1 = rt_random_value(rng);
+    const float u2 = rt_random_value(rng);
+    const int li = rt_nee::pick(lt.cdf, lt.n, u0); /* (rt_nee_launch.h: bounded, clamped to the table) */
+    const float4* const e = lt.entries + 5 * (size_t)li; /* li < n: inside the n * 80 bytes the host made */
+    const float4 q0 = e[0], q1 = e[1], q2 = e[2], q3 = e[3], q4 = e[4];
+    const float prob = q1.w;
+    obj = (int)__float_as_uint(q2.w);
+    tri = (int)__float_as_uint(q3.w);
+    Le = rt_v3(q4.x, q4.y, q4.z);
+    omega = rt_v3s(0.0f);
+    g = 0.0f;
+    if (tri < 0) { /* a sphere: uniform in the cone it subtends */
+        const rt_f3 w = rt_v3(q0.x, q0.y, q0.z) - x;
+        const float d2 = rt_dot(w, w);
+        const float r2 = q0.w;
+        if (!(d2 > r2)) return false;
+        const float s2 = rt_div(r2, d2);
+        const float cmax = rt_sqrt(1.0f - s2);
+        const float q = rt_div(s2, 1.0f + cmax);
+        const float ct = 1.0f - u1 * q;
+        const float st = rt_sqrt(rt_max(0.0f, 1.0f - ct * ct));
+        float sn, cs;
+        rt_sincos(2 * 3.1415926f * u2, &sn, &cs);
+        const rt_f3 z = rt_normalize(w);
+        const float sg = rt_u2f(0x3f800000u | (rt_f2u(z.z) & 0x80000000u));
+        const float a = -rt_rcp(sg + z.z);
+        const float b = z.x * z.y * a;
+        const rt_f3 b1 = rt_v3(1.0f + sg * z.x * z.x * a, sg * b, -sg * z.x);
+        const rt_f3 b2 = rt_v3(b, sg + z.y * z.y * a, -z.y);
+        omega = b1 * (st * cs) + b2 * (st * sn) + z * ct;
+        const float cn = rt_dot(n, omega);
+        if (!(cn > 0.0f)) return false;
+        g = rt_div(cn * 2.0f * q, prob);
+        return true;
+    }
+    /* a triangle: uniform on it by the fold map */
+    const bool fold = u1 + u2 > 1.0f;
+    const float v1 = fold ? 1.0f - u1 : u1, v2 = fold ? 1.0f - u2 : u2;
+    const rt_f3 y = rt_v3(q0.x, q0.y, q0.z) + rt_v3(q1.x, q1.y, q1.z) * v1 + rt_v3(q2.x, q2.y, q2.z) * v2;
+    const rt_f3 v = y - x;
+    const float d2 = rt_dot(v, v);
+    omega = rt_normalize(v);
+    const float cl = rt_dot(rt_v3(q3.x, q3.y, q3.z), -omega);
+    const float cn = rt_dot(n, omega);
+    if (!(cl > 0.0f && cn > 0.0f)) return false;
+    g = rt_div(cn * cl * q0.w, 3.1415926f * d2 * prob);
+    return true;
+}
+
+/* One path per lane, blocks of 64 consecutive rays, the refill of idle lanes and the block counter exactly as rt_radiance_kernel (whose
+ * comment describes them); LDS the same wave region (rt_plan::wave_lds_bytes).  A wave iteration is: the path segments' walk, the shade
+ * block — this kernel's own copy of rt_shade_phase.inl's, with the three amendments; the empty-table identity of the header is what
+ * guards the duplication — and, when some lane sampled an emitter, the shadow rays' walk through the same begin_intersect / traverse /
+ * traverse_flat and the wave's one stack region.  Both walks run to completion (no suspension) with EVERY lane of the wave inside, because
+ * their votes count lanes: a lane without a path, or without a shadow ray, carries the null ray and enters parked as rt_query_kernel
+ * parks the lanes past n (BVH variants: RT_CODE_DONE; FLAT: dst = -inf).  The roulette draw follows the sample's three draws at once —
+ * it does not depend on the shadow ray — and only the sample's light waits for the walk.
+ * Written besides `out`: a.counters + 7 (the watchdog word of traverse()) and the block counter a.tileQueue, both words of this pass's own. */
+template <bool FLAT, bool MANY>
+__global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_radiance_nee_kernel(const KArgs a, const float4* __restrict__ rays, const int n, float4* __restrict__ out, const NeeTable lt, const uint32_t* __restrict__ unitTri)
+{
+    extern __shared__ uint32_t s_lds[];
+    const int lane = (int)threadIdx.x;
+    uint32_t* const stackBase = &s_lds[lane];
+    uint32_t* const extBase = &s_lds[(size_t)(a.stackEntries + RT_PIXEL_FIELDS) * RT_WAVE + lane];
+    uint32_t* const bounceLds = extBase + (1 + a.extWords) * RT_WAVE; /* MANY: the bounce count lives here, as in trace_body */
+
+    const int blocks = (n + RT_WAVE - 1) / RT_WAVE;
+    int poolBase = (int)blockIdx.x * RT_WAVE; /* first ray of the wave's block */
+    int poolPos = (int)blockIdx.x < blocks ? 0 : 64; /* next unassigned ray of the block, 64 = used up */
+    bool queueEmpty = false;
+
+    uint32_t rng = 0;
+    bool pathActive = false;  /* the lane holds a path */
+    bool prevSampled = false; /* the path's previous vertex was a diffuse vertex at which an emitter was sampled (amendment 3) */
+    int bounce = 0, rayIndex = 0;
+    rt_f3 rpos = rt_v3s(0.0f), rdir = rt_v3s(0.0f), transmittance = rt_v3s(0.0f), pathLight = rt_v3s(0.0f);
+    Stats st = {};
+
+    for (;;) {
+        /* ---- hand rays to idle lanes (every lane of the wave is active here) */
+        unsigned long long idle = __ballot(!pathActive);
+        while (idle) {
+            if (poolPos >= 64) {
+                if (queueEmpty) break;
+                int next = 0;
+                if (lane == 0) next = (int)atomicAdd(a.tileQueue, 1ull);
+                next = __builtin_amdgcn_readfirstlane(next) + (int)gridDim.x;
+                if (next >= blocks) { queueEmpty = true; break; }
+                poolBase = next * RT_WAVE;
+                poolPos = 0;
+            }
+            const int rank = __popcll(idle & ((1ull << lane) - 1ull));
+            const int avail = 64 - poolPos;
+            if (!pathActive && rank < avail) {
+                const int i = poolBase + poolPos + rank;
+                if (i < n) { /* inside the n * 32 and n * 16 bytes the host checked */
+                    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+                    if (a.maxBounce >= 0) { /* RC:485: the loop runs for i = 0 */
+                        rpos = rt_v3(r0.x, r0.y, r0.z);
+                        rdir = rt_v3(r1.x, r1.y, r1.z);
+                        rng = __float_as_uint(r1.w);
+                        transmittance = rt_v3s(1.0f);
+                        pathLight = rt_v3s(0.0f);
+                        if (MANY) *bounceLds = 0u;
+                        else bounce = 0;
+                        rayIndex = i;
+                        prevSampled = false;
+                        pathActive = true;
+                    } else {
+                        out[i] = make_float4(0.0f, 0.0f, 0.0f, r1.w); /* Trace returned 0 without a draw */
+                    }
+                }
+            }
+            const int wanted = __popcll(idle);
+            poolPos += wanted < avail ? wanted : avail;
+            idle = __ballot(!pathActive);
+        }
+        if (idle == ~0ull) break; /* no lane holds a path and there is no ray left */
+
+        /* ---- the path segments: CalculateRayCollision — RC:335-374 (every lane inside, those without a path parked) */
+        SceneHit h;
+        Trav t;
+        {
+            const rt_f3 wpos = pathActive ? rpos : rt_v3s(0.0f), wdir = pathActive ? rdir : rt_v3s(0.0f);
+            begin_intersect<false, FLAT, MANY>(a, wpos, wdir, extBase, h, t, st);
+            if (FLAT) {
+                if (!pathActive) h.dst = -RT_INF;
+                traverse_flat<false>(a, wpos, wdir, h, st);
+            } else {
+                if (!pathActive) {
+                    t.cur = RT_CODE_DONE;
+                    t.cand = 0;
+                }
+                traverse<false, false, MANY>(a, wpos, wdir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u);
+            }
+        }
+
+        /* ---- the rest of one iteration of Trace's bounce loop — RC:488-538, rt_shade_phase.inl's block with the three amendments */
+        bool endPath = false, shadow = false;
+        rt_f3 spos = rt_v3s(0.0f), sdir = rt_v3s(0.0f), sampled = rt_v3s(0.0f);
+        int wantObj = -1, wantTri = -1;
+        if (pathActive) {
+            if (h.obj < 0) {
+                const RT_CAS KArgs& c = cold_args();
+                if (c.useSky) pathLight = pathLight + transmittance * environment_light(c, rdir);
+                endPath = true;
+            } else {
+                rt_f3 hpos, normal;
+                resolve_hit(a, rpos, rdir, h, hpos, normal);
+                const DMaterial mat = a.materials[h.obj];
+                const bool isGlass = mat.flag == RT_MATERIAL_GLASS;
+                float uSpec = 0.0f;
+                if (!isGlass) uSpec = rt_random_value(&rng); /* RC:521 */
+                const rt_f3 diffuseDir = rt_normalize(normal + rand_direction(&rng)); /* RC:509 / RC:525 */
+                const rt_f3 specularDir = rt_reflect(rdir, normal);
+                rt_f3 lerpA = diffuseDir, lerpB = specularDir;
+                float lerpT;
+                bool sample = false;
+                if (isGlass) {
+                    if (h.backface) { /* RC:502 */
+                        rt_f3 e = ((-h.dst) * rt_v3(mat.absorption[0], mat.absorption[1], mat.absorption[2])) * mat.absorptionStrength;
+                        transmittance = transmittance * rt_v3(rt_exp(e.x), rt_exp(e.y), rt_exp(e.z));
+                    }
+                    float iorCurrent = h.backface ? mat.ior : 1.0f;
+                    float iorNext = h.backface ? 1.0f : mat.ior;
+                    const rt_f3 refractDir = refract_dir(rdir, normal, iorCurrent, iorNext);
+                    const float reflectWeight = reflectance(rdir, normal, iorCurrent, iorNext);
+                    const bool followReflection = rt_random_value(&rng) <= reflectWeight; /* RC:515 */
+                    lerpT = mat.specularProbability;
+                    if (!followReflection) {
+                        lerpA = -diffuseDir;
+                        lerpB = refractDir;
+                        lerpT = mat.smoothness;
+                    }
+                } else {
+                    const bool isSpecular = mat.specularProbability >= uSpec;
+                    lerpT = mat.smoothness * (isSpecular ? 1.0f : 0.0f);
+                    rt_f3 emitted = rt_v3(mat.emissionCol[0], mat.emissionCol[1], mat.emissionCol[2]) * mat.emissionStrength;
+                    /* amendment 3: the previous vertex's sample stood for this emission, unless it could not (no entry; a sphere from inside) */
+                    const bool counted = prevSampled && lt.inTable[h.obj] != 0u && !(h.obj < a.nSpheres && h.backface); /* h.obj < nSpheres + nModels: inside the table's flags */
+                    if (!counted) pathLight = pathLight + emitted * transmittance;
+                    transmittance = transmittance * material_colour(mat, hpos, normal, isSpecular);
+                    sample = lt.n > 0 && lerpT == 0.0f; /* amendment 2: a diffuse vertex */
+                }
+                rdir = rt_normalize(rt_lerp3(lerpA, lerpB, lerpT));
+                rpos = isGlass ? hpos + (0.001f * normal) * rt_sign(rt_dot(normal, rdir)) : hpos + (normal * 0.001f);
+                prevSampled = sample;
+                if (sample) {
+                    rt_f3 Le;
+                    float g;
+                    if (nee_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri)) {
+                        shadow = true;
+                        spos = rpos;
+                        sampled = (transmittance * Le) * g;
+                    }
+                }
+                /* RC:535-538 Russian roulette */
+                float p = rt_max(transmittance.x, rt_max(transmittance.y, transmittance.z));
+                if (rt_random_value(&rng) >= p) {
+                    endPath = true;
+                } else {
+                    transmittance = transmittance * rt_rcp(p);
+                    if (MANY) {
+                        const uint32_t b = *bounceLds + 1u;
+                        *bounceLds = b;
+                        if ((int)b > a.maxBounce) endPath = true;
+                    } else {
+                        bounce++;
+                        if (bounce > a.maxBounce) endPath = true; /* RC:485: i <= MaxBounceCount */
+                    }
+                }
+            }
+        }
+
+        /* ---- the shadow rays: the same walk from x along omega; identity with the closest hit is the visibility test */
+        if (__ballot(shadow) != 0ull) { /* (wave-uniform) */
+            if (!shadow) sdir = rt_v3s(0.0f);
+            SceneHit sh;
+            Trav tt;
+            begin_intersect<false, FLAT, MANY>(a, spos, sdir, extBase, sh, tt, st);
+            if (FLAT) {
+                if (!shadow) sh.dst = -RT_INF;
+                traverse_flat<false>(a, spos, sdir, sh, st);
+            } else {
+                if (!shadow) {
+                    tt.cur = RT_CODE_DONE;
+                    tt.cand = 0;
+                }
+                traverse<false, false, MANY>(a, spos, sdir, stackBase, extBase, sh, tt, st, (const RT_LDS char*)nullptr, 0u);
+            }
+            if (shadow && sh.obj == wantObj) {
+                bool same = true;
+                if (wantTri >= 0) same = (unitTri ? (int)unitTri[sh.tri] : sh.tri / 3) == wantTri;
+                if (same) pathLight = pathLight + sampled;
+            }
+        }
+
+        if (pathActive && endPath) {
+            out[rayIndex] = make_float4(0.0f + pathLight.x, 0.0f + pathLight.y, 0.0f + pathLight.z, __uint_as_float(rng)); /* RC:578's 0 + Trace(...), as rt_radiance_kernel; rayIndex < n */
+            pathActive = false;
+        }
+    }
 }
 
 /* ---- test hooks (rt_debug_*): the same device functions, one ray / value per lane */

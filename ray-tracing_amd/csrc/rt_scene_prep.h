@@ -466,6 +466,7 @@ struct PreparedScene {
     std::vector<RtModel> hModels;
     std::vector<RtSphere> hSpheres;
     int nTris = 0, maxHeight = 1;
+    const RtTriangle* srcTris = nullptr; /* the caller's triangles: valid only while the call that prepared the scene runs (commit_scene keeps their corners) */
     bool flat = true;
     int wavesPerGroup = 1; /* plan_groups: what the layout's cache prefix was sized for */
     std::string error;     /* prepare_scene refused the scene: why */
@@ -680,6 +681,7 @@ static inline int prepare_scene(const RtModel* models, int n_models, const RtTri
     ps.hModels.assign(models, models + n_models);
     ps.hSpheres.assign(spheres, spheres + n_spheres);
     ps.nTris = n_triangles;
+    ps.srcTris = triangles;
     ps.maxHeight = maxHeight;
     ps.flat = true;
     for (int i = 0; i < n_models; i++)

@@ -58,6 +58,8 @@ ADAPTIVE_SYMBOLS = ["rt_adaptive_default_params", "rt_adaptive_select_buffers", 
 QUERY_SYMBOLS = ["rt_query_closest", "rt_query_closest_buffers", "rt_query_occluded", "rt_query_occluded_buffers"]
 # every symbol include/rt_radiance.h declares
 RADIANCE_SYMBOLS = ["rt_radiance_trace", "rt_radiance_trace_buffers"]
+# every symbol include/rt_nee.h declares
+NEE_SYMBOLS = ["rt_nee_trace", "rt_nee_trace_buffers", "rt_nee_light_count", "rt_debug_light_table", "rt_debug_light_table_free"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -153,6 +155,11 @@ class HipApi(abi.CApi):
         "query_occluded_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "radiance_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "radiance_trace_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "nee_trace": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "nee_trace_buffers": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+        "nee_light_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "debug_light_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(abi.RtLightTableDump)]),
+        "debug_light_table_free": (None, [C.POINTER(abi.RtLightTableDump)]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -179,6 +186,24 @@ class HipApi(abi.CApi):
         if rc != abi.RT_OK:
             raise abi.RtError(rc, (self.last_error(None) or b"").decode(errors="replace"))
         return {k: getattr(info, k) for k, _ in _Info._fields_}
+
+    def light_table_arrays(self, models, triangles, spheres=None):
+        """rt_debug_light_table (include/rt_nee.h): the light table rt_nee_trace would sample for these arrays (no device
+        needed), as numpy copies: {entries (abi.LIGHT_ENTRY_DTYPE), cdf (float32), n_sphere_entries, n_triangle_entries}."""
+        m, nm = abi._ptr(models, abi.model_dtype)
+        t, nt = abi._ptr(triangles, abi.triangle_dtype)
+        sp, ns = abi._ptr(spheres, abi.sphere_dtype)
+        d = abi.RtLightTableDump()
+        rc = self.debug_light_table(m.ctypes.data if nm else None, nm, t.ctypes.data if nt else None, nt, sp.ctypes.data if ns else None, ns, C.byref(d))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, (self.last_error(None) or b"").decode(errors="replace"))
+        try:
+            n = d.n_entries
+            entries = np.frombuffer((C.c_char * (n * 80)).from_address(d.entries), dtype=abi.LIGHT_ENTRY_DTYPE).copy() if n else np.zeros(0, dtype=abi.LIGHT_ENTRY_DTYPE)
+            cdf = np.frombuffer((C.c_char * (n * 4)).from_address(d.cdf), dtype=np.float32).copy() if n else np.zeros(0, dtype=np.float32)
+            return {"entries": entries, "cdf": cdf, "n_sphere_entries": int(d.n_sphere_entries), "n_triangle_entries": int(d.n_triangle_entries)}
+        finally:
+            self.debug_light_table_free(C.byref(d))
 
     def layout_arrays(self, models, triangles, nodes, layout=None):
         """rt_debug_layout: the device-memory layout rt_upload_scene would produce (no device needed), as numpy copies:
@@ -653,6 +678,25 @@ class HipTracer(abi.Tracer):
         """rt_radiance_trace_buffers: the same on device memory (e.g. torch tensors' data_ptr(): n * 32 bytes of rays, n * 16 bytes of
         records, 16-byte aligned), enqueued on the stream the context renders on; complete after synchronize()."""
         self._check(self.api.radiance_trace_buffers(self.h, rays_ptr, int(n), out_ptr))
+
+    def radiance_trace_nee(self, rays):
+        """rt_nee_trace (include/rt_nee.h): radiance_trace with one emitter of the scene sampled directly at every diffuse
+        vertex (next-event estimation) — the same records, the same expectation per ray up to the cut at maxBounceCount (the header states it), less variance where small emitters light
+        the scene.  Changes no state of the context."""
+        r = np.ascontiguousarray(rays, dtype=abi.PATHRAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), dtype=abi.RADIANCE_DTYPE)
+        self._check(self.api.nee_trace(self.h, r.ctypes.data if len(r) else None, len(r), out.ctypes.data if len(r) else None))
+        return out
+
+    def radiance_trace_nee_buffers(self, rays_ptr, n, out_ptr):
+        """rt_nee_trace_buffers: the same on device memory, enqueued like radiance_trace_buffers."""
+        self._check(self.api.nee_trace_buffers(self.h, rays_ptr, int(n), out_ptr))
+
+    def nee_light_count(self):
+        """rt_nee_light_count: (sphere entries, triangle entries) of the light table as the next radiance_trace_nee would use it."""
+        ns, nt = C.c_int(0), C.c_int(0)
+        self._check(self.api.nee_light_count(self.h, C.byref(ns), C.byref(nt)))
+        return ns.value, nt.value
 
     def denoise(self, params=None, use_accumulated=True, aov_frame=1):
         """rt_denoise (include/rt_denoise.h): the context's accumulated image (or its last frame) through the edge-avoiding a-trous
