@@ -2318,6 +2318,25 @@ static int side_submit(RtContext* ctx, SidePass& sp, Kern kern, long long grid, 
     return RT_OK;
 }
 
+/* What the radiance pass and the NEE pass share (their enqueue functions are below): fill_args with the parameters present, the
+ * pass's suspension threshold, word 0 of the pass's slot as the counter that hands out the blocks of 64 rays to the resident waves
+ * (word 7 is the watchdog's), rt_radiance_launch.h's block and grid arithmetic, and `kern`(a, args...) over that grid. */
+template <class Kern, class... Args>
+static int path_enqueue(RtContext* ctx, int pass, int suspendNum, int n, Kern kern, Args... args)
+{
+    KArgs a;
+    fill_args(ctx, 1, 1, a);
+    a.suspendNum = suspendNum;
+    SidePass& sp = ctx->side[pass];
+    size_t ldsBytes = 0;
+    long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
+    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
+    a.tileQueue = sp.words; /* word 0: a launch of this pass counts no segments there */
+    a.tileQueueBase = 0;
+    const long long grid = rt_rd::grid(rt_rd::blocks(n), resident, ctx->gridOverride);
+    return side_submit(ctx, sp, kern, grid, ldsBytes, a, args...);
+}
+
 extern "C" {
 
 /* ---- rt_render_aov / rt_render_aov_to_device (include/rt_aov.h): what camera ray 0 of a frame finds, per pixel -------------
@@ -2429,23 +2448,12 @@ static int closest_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut)
 static int occluded_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut) { return query_enqueue(ctx, dRays, n, dOut, true); }
 
 /* ---- rt_radiance_trace / rt_radiance_trace_buffers (include/rt_radiance.h): Trace for caller-made rays -------------------------------
- * The side pass of rt_radiance_kernel.  fill_args with the parameters present (the kernel reads maxBounce, useSky and the sun's fields
- * besides the scene) and the tuner's suspension threshold; word 0 of the pass's slot hands out the blocks of 64 rays to the resident
- * waves (word 7 is the watchdog's).  The block and grid arithmetic is rt_radiance_launch.h's. */
+ * The side pass of rt_radiance_kernel: path_enqueue (the kernel reads maxBounce, useSky and the sun's fields besides the scene) with
+ * the tuner's suspension threshold. */
 static int radiance_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut)
 {
-    KArgs a;
-    fill_args(ctx, 1, 1, a);
     void (*kern)(const KArgs, const float4*, int, float4*) = RT_SCENE_KERNEL(ctx, rtk::rt_radiance_kernel);
-    a.suspendNum = ctx->tuner.decided; /* scheduling only: a path's bits do not depend on it */
-    SidePass& sp = ctx->side[SIDE_RADIANCE];
-    size_t ldsBytes = 0;
-    long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
-    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
-    a.tileQueue = sp.words; /* word 0: a launch of this pass counts no segments there */
-    a.tileQueueBase = 0;
-    const long long grid = rt_rd::grid(rt_rd::blocks(n), resident, ctx->gridOverride);
-    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, (float4*)dOut);
+    return path_enqueue(ctx, SIDE_RADIANCE, ctx->tuner.decided /* scheduling only: a path's bits do not depend on it */, n, kern, (const float4*)dRays, n, (float4*)dOut);
 }
 
 /* ---- rt_nee_trace / rt_nee_trace_buffers / rt_nee_light_count (include/rt_nee.h) -----------------------------------
@@ -2491,24 +2499,15 @@ static int nee_refresh_table(RtContext* ctx, const char* call)
 static int nee_enqueue(RtContext* ctx, const char* call, const void* dRays, int n, void* dOut)
 {
     if (int rc = nee_refresh_table(ctx, call)) return rc;
-    KArgs a;
-    fill_args(ctx, 1, 1, a);
     void (*kern)(const KArgs, const float4*, int, float4*, const rtk::NeeTable, const uint32_t*) = RT_SCENE_KERNEL(ctx, rtk::rt_radiance_nee_kernel);
-    a.suspendNum = RT_SUSPEND_NUM; /* (unused: both walks of the pass run to completion) */
-    SidePass& sp = ctx->side[SIDE_NEE];
-    size_t ldsBytes = 0;
-    long long resident = 0; /* every wave the device keeps resident; the blocks are handed out to them */
-    if (int rc = side_begin(ctx, sp, reinterpret_cast<const void*>(kern), a, &ldsBytes, &resident)) return rc;
-    a.tileQueue = sp.words; /* word 0: a launch of this pass counts no segments there */
-    a.tileQueueBase = 0;
     const char* const d = (const char*)ctx->dLightTable;
     rtk::NeeTable lt;
     lt.entries = (const float4*)(d + ctx->lightLayout.entries);
     lt.cdf = (const float*)(d + ctx->lightLayout.cdf);
     lt.inTable = (const uint32_t*)(d + ctx->lightLayout.flags);
     lt.n = ctx->lightSpheres + ctx->lightTriangles;
-    const long long grid = rt_nee::grid(rt_nee::blocks(n), resident, ctx->gridOverride);
-    return side_submit(ctx, sp, kern, grid, ldsBytes, a, (const float4*)dRays, n, (float4*)dOut, lt, (const uint32_t*)ctx->dUnitTri);
+    return path_enqueue(ctx, SIDE_NEE, RT_SUSPEND_NUM /* (unused: both walks of the pass run to completion) */, n, kern, (const float4*)dRays, n, (float4*)dOut, lt,
+                        (const uint32_t*)ctx->dUnitTri);
 }
 
 static int nee_enqueue_host(RtContext* ctx, const void* dRays, int n, void* dOut) { return nee_enqueue(ctx, "rt_nee_trace", dRays, n, dOut); }

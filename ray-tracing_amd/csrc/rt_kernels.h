@@ -864,6 +864,29 @@ __device__ __forceinline__ void traverse_flat(const KArgs& a, rt_f3 rpos, rt_f3 
     }
 }
 
+/* CalculateRayCollision (RC:335-374) run to completion, without suspension and without the top-of-tree cache, by EVERY lane of the wave:
+ * the side passes' walk.  The parking rule: begin_intersect and the traversals vote, and their votes count lanes, so a lane that has no
+ * ray (`live` false) may not skip the walk.  It comes in with the null ray (pos = dir = 0) and is parked behind begin_intersect — FLAT:
+ * dst = -inf, which no test beats (and with ANY lies below tmax = +inf); BVH: cur = RT_CODE_DONE with no candidate left — so that it
+ * walks nothing and its `h` means nothing.  ANY, tmax: the occlusion form of rt_query. */
+template <bool FLAT, bool MANY, bool ANY = false>
+__device__ __forceinline__ void walk_all(const KArgs& a, const bool live, const rt_f3 pos, const rt_f3 dir, uint32_t* stackBase, uint32_t* extBase, SceneHit& h, Stats& st,
+                                         const float tmax = 0.0f)
+{
+    Trav t;
+    begin_intersect<false, FLAT, MANY, ANY>(a, pos, dir, extBase, h, t, st, tmax);
+    if (FLAT) {
+        if (!live) h.dst = -RT_INF;
+        traverse_flat<false, ANY>(a, pos, dir, h, st, tmax);
+    } else {
+        if (!live) {
+            t.cur = RT_CODE_DONE;
+            t.cand = 0;
+        }
+        traverse<false, false, MANY, false, ANY>(a, pos, dir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u, tmax);
+    }
+}
+
 /* Run-to-completion form (debug hook). */
 template <bool STATS>
 __device__ __forceinline__ void intersect_scene(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* stackBase, uint32_t* extBase, SceneHit& h, Stats& st)
@@ -876,6 +899,20 @@ __device__ __forceinline__ void intersect_scene(const KArgs& a, rt_f3 rpos, rt_f
         begin_intersect<STATS, false, false>(a, rpos, rdir, extBase, h, t, st);
         traverse<STATS, false, false>(a, rpos, rdir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u);
     }
+}
+
+/* The uploaded index of the triangle `h` hit, from the 16-byte unit its record starts at (rt_layout.h moves the records); unitTri null =
+ * the dense layout (unit = 3 x index).  For a hit on a model (h.obj >= nSpheres). */
+__device__ __forceinline__ int hit_triangle(const SceneHit& h, const uint32_t* unitTri)
+{
+    return unitTri ? (int)unitTri[h.tri] : h.tri / 3;
+}
+
+/* The kind word of the AOV and query records: 1 opaque, 2 glass, bit 8 = the ray met the back of the surface.  (Arguments by reference:
+ * by value the loads move, and with them the instruction order of every rt_aov_kernel.) */
+__device__ __forceinline__ uint32_t hit_kind(const int& flag, const bool& backface)
+{
+    return (flag == RT_MATERIAL_GLASS ? 2u : 1u) | (backface ? 0x100u : 0u);
 }
 
 /* Position and world normal of the winning hit: RC:319-320 (sphere) or RC:208-209 +
@@ -1578,7 +1615,7 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             const rt_f3 rpos = rayOrigin;
             const rt_f3 rdir = rt_normalize(jfp - rayOrigin);
 
-            /* CalculateRayCollision — RC:335-374 */
+            /* CalculateRayCollision — RC:335-374: walk_all's walk without its parking (written out: through the call all six bodies change) */
             SceneHit h;
             Trav t;
             Stats st = {};
@@ -1595,9 +1632,9 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
                 const rt_f3 albedo = material_colour(mat, hpos, normal, false);
                 const rt_f3 emitted = rt_v3(mat.emissionCol[0], mat.emissionCol[1], mat.emissionCol[2]) * mat.emissionStrength; /* RC:530 */
                 int tri = -1;
-                if (h.obj >= a.nSpheres) tri = unitTri ? (int)unitTri[h.tri] : h.tri / 3;
+                if (h.obj >= a.nSpheres) tri = hit_triangle(h, unitTri);
                 q0 = make_float4(h.dst, normal.x, normal.y, normal.z);
-                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float((mat.flag == RT_MATERIAL_GLASS ? 2u : 1u) | (h.backface ? 0x100u : 0u)));
+                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float(hit_kind(mat.flag, h.backface)));
                 q2 = make_float4(albedo.x, albedo.y, albedo.z, __uint_as_float((uint32_t)h.obj));
                 q3 = make_float4(emitted.x, emitted.y, emitted.z, __uint_as_float((uint32_t)tri));
             } else if (a.useSky) {
@@ -1619,8 +1656,8 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
  * without the pool; LDS as a wave region of the trace kernel (rt_aov_kernel), so the host sizes it with rt_plan::wave_lds_bytes.  A ray
  * (RtRay, 32 bytes) comes in as two 16-byte loads; a record (RtRayHit, 48 bytes) leaves as three 16-byte stores, an occlusion answer as
  * one 4-byte store.  The traversal runs to completion (no suspension).
- * The lanes past n of the last block load and store nothing, but stay in the wave through begin_intersect and traverse, whose votes
- * count lanes: they carry the null ray and enter the traversal parked (BVH variants: RT_CODE_DONE).
+ * The lanes past n of the last block load and store nothing, but stay in the wave through the walk: they carry the null ray and are
+ * parked (walk_all).
  * ANY: the occlusion form, `out` = one uint32 per ray; the early exit of begin_intersect / traverse / traverse_flat.  Otherwise `out` =
  * the records, and `unitTri` as for rt_aov_kernel.  Only a.counters + 7 (the watchdog word of traverse()) is written besides `out`: the
  * host points it at a word of this pass's own.  n <= RT_QUERY_MAX_RAYS = 2^26: 64 x blocks fits an int. */
@@ -1645,20 +1682,9 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
         }
         /* CalculateRayCollision — RC:335-374 */
         SceneHit h;
-        Trav t;
         Stats st = {};
-        begin_intersect<false, FLAT, MANY, ANY>(a, rpos, rdir, extBase, h, t, st, tmax);
-        if (FLAT) {
-            if (!live) h.dst = -RT_INF; /* the flat form of parking: no test beats it, and with ANY it is below tmax = +inf */
-            traverse_flat<false, ANY>(a, rpos, rdir, h, st, tmax);
-        } else {
-            if (!live) {
-                t.cur = RT_CODE_DONE;
-                t.cand = 0;
-            }
-            traverse<false, false, MANY, false, ANY>(a, rpos, rdir, stackBase, extBase, h, t, st, (const RT_LDS char*)nullptr, 0u, tmax);
-        }
-        if (!live) continue; /* (behind the traversal: nothing below votes) */
+        walk_all<FLAT, MANY, ANY>(a, live, rpos, rdir, stackBase, extBase, h, st, tmax);
+        if (!live) continue; /* (behind the walk: nothing below votes) */
         if (ANY) {
             reinterpret_cast<uint32_t*>(out)[i] = (h.obj >= 0 && h.dst < tmax) ? 1u : 0u; /* i < n: inside the n * 4 bytes */
         } else {
@@ -1668,9 +1694,9 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
                 rt_f3 hpos, normal;
                 resolve_hit(a, rpos, rdir, h, hpos, normal);
                 int tri = -1;
-                if (h.obj >= a.nSpheres) tri = unitTri ? (int)unitTri[h.tri] : h.tri / 3;
+                if (h.obj >= a.nSpheres) tri = hit_triangle(h, unitTri);
                 q0 = make_float4(h.dst, normal.x, normal.y, normal.z);
-                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float((a.materials[h.obj].flag == RT_MATERIAL_GLASS ? 2u : 1u) | (h.backface ? 0x100u : 0u)));
+                q1 = make_float4(hpos.x, hpos.y, hpos.z, __uint_as_float(hit_kind(a.materials[h.obj].flag, h.backface)));
                 q2 = make_float4(__uint_as_float((uint32_t)h.obj), __uint_as_float((uint32_t)tri), 0.0f, 0.0f);
             }
             float4* const o = reinterpret_cast<float4*>(out) + 3 * (size_t)i; /* i < n: inside the n * 48 bytes */
@@ -1685,10 +1711,12 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
  * trace_body without camera, pixel, frame and image: a path starts from a ray of `rays` (RtPathRay, 32 bytes, two 16-byte loads) and
  * ends in one 16-byte store of its RtRadiance (the light and the generator's state) into `out`.  Between the two it is the frame's
  * path: begin_intersect, traverse (suspending, as trace_body calls it, at the context's threshold a.suspendNum) or traverse_flat,
- * and rt_shade_phase.inl — included here a third time behind locals of trace_body's names, so there is one copy of the arithmetic.  The
- * pixel's sum that the include adds a finished path to (PXF) is a local that starts at 0 in the iteration the path ends in: 0 + light.
- * One path per lane.  A wave owns a block of 64 consecutive rays at a time; a lane without a path takes the next unassigned ray of that
- * block by ballot and prefix rank (trace_body's refill with "slot of an 8 x 8 tile" replaced by "index into the block"), and when the
+ * and rt_shade_phase.inl — included here a third time behind locals of trace_body's names, and with it rt_shade_block.inl, the one copy
+ * of the shade arithmetic.  The pixel's sum that the include adds a finished path to (PXF) is a local that starts at 0 in the iteration
+ * the path ends in: 0 + light.
+ * One path per lane.  A wave owns a block of 64 consecutive rays at a time (rt_ray_feed.inl, shared with rt_radiance_nee_kernel); a lane
+ * without a path takes the next unassigned ray of that block by ballot and prefix rank (trace_body's refill with "slot of an 8 x 8
+ * tile" replaced by "index into the block"), and when the
  * block is used up the wave takes another: block blockIdx.x first, then gridDim.x + ticket from the counter a.tileQueue, which the host
  * zeroes for the launch (rt_radiance_launch.h).  So a wave does not idle on its longest path, and a wave of long paths draws fewer blocks.
  * Rays at or past n are never assigned: those lanes load and store nothing and stay in the loop, idle, until the wave leaves.
@@ -1714,6 +1742,7 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
 #define PXF(k) pxacc[(k)]
 #define RT_COST_SLOT(c) (reinterpret_cast<uint4*>(cost)) /* (COST is false: never evaluated) */
 
+    /* rt_ray_feed.inl's state: the wave's place in the blocks of rays */
     const int blocks = (n + RT_WAVE - 1) / RT_WAVE;
     int poolBase = (int)blockIdx.x * RT_WAVE; /* first ray of the wave's block */
     int poolPos = (int)blockIdx.x < blocks ? 0 : 64; /* next unassigned ray of the block, 64 = used up */
@@ -1731,45 +1760,13 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     Stats st = {};
 
     for (;;) {
-        /* ---- hand rays to idle lanes (every lane of the wave is active here) */
-        unsigned long long idle = __ballot(!pathActive);
-        while (idle) {
-            const RT_CAS KArgs& c = cold_args();
-            if (poolPos >= 64) {
-                if (queueEmpty) break;
-                int next = 0;
-                if (lane == 0) next = (int)atomicAdd(c.tileQueue, 1ull);
-                next = __builtin_amdgcn_readfirstlane(next) + (int)gridDim.x;
-                if (next >= blocks) { queueEmpty = true; break; }
-                poolBase = next * RT_WAVE;
-                poolPos = 0;
-            }
-            const int rank = __popcll(idle & ((1ull << lane) - 1ull));
-            const int avail = 64 - poolPos;
-            if (!pathActive && rank < avail) {
-                const int i = poolBase + poolPos + rank;
-                if (i < n) { /* inside the n * 32 and n * 16 bytes the host checked */
-                    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
-                    if (c.maxBounce >= 0) { /* RC:485: the loop runs for i = 0 */
-                        rpos = rt_v3(r0.x, r0.y, r0.z);
-                        rdir = rt_v3(r1.x, r1.y, r1.z);
-                        rng = __float_as_uint(r1.w);
-                        transmittance = rt_v3s(1.0f);
-                        pathLight = rt_v3s(0.0f);
-                        if (MANY) extBase[(1 + a.extWords) * RT_WAVE] = 0u; /* (trace_body: this variant keeps the bounce count in LDS) */
-                        else bounce = 0;
-                        PXU(PX_RAY) = (uint32_t)i;
-                        inTrav = false;
-                        pathActive = true;
-                    } else {
-                        out[i] = make_float4(0.0f, 0.0f, 0.0f, r1.w); /* Trace returned 0 without a draw */
-                    }
-                }
-            }
-            const int wanted = __popcll(idle);
-            poolPos += wanted < avail ? wanted : avail;
-            idle = __ballot(!pathActive);
-        }
+#define RT_FEED_ROUND const RT_CAS KArgs& c = cold_args();
+#define RT_FEED_ARGS c
+#define RT_FEED_START(i) PXU(PX_RAY) = (uint32_t)(i); inTrav = false;
+#include "rt_ray_feed.inl"
+#undef RT_FEED_ROUND
+#undef RT_FEED_ARGS
+#undef RT_FEED_START
         if (idle == ~0ull) break; /* no lane holds a path and there is no ray left */
         if (pathActive) {
             if (!inTrav) {
@@ -1853,27 +1850,27 @@ __device__ __forceinline__ bool nee_sample(const NeeTable& lt, uint32_t* rng, co
     return true;
 }
 
-/* One path per lane, blocks of 64 consecutive rays, the refill of idle lanes and the block counter exactly as rt_radiance_kernel (whose
- * comment describes them); LDS the same wave region (rt_plan::wave_lds_bytes).  A wave iteration is: the path segments' walk, the shade
- * block — this kernel's own copy of rt_shade_phase.inl's, with the three amendments; the empty-table identity of the header is what
- * guards the duplication — and, when some lane sampled an emitter, the shadow rays' walk through the same begin_intersect / traverse /
- * traverse_flat and the wave's one stack region.  Both walks run to completion (no suspension) with EVERY lane of the wave inside, because
- * their votes count lanes: a lane without a path, or without a shadow ray, carries the null ray and enters parked as rt_query_kernel
- * parks the lanes past n (BVH variants: RT_CODE_DONE; FLAT: dst = -inf).  The roulette draw follows the sample's three draws at once —
- * it does not depend on the shadow ray — and only the sample's light waits for the walk.
+/* One path per lane, blocks of 64 consecutive rays, the refill of idle lanes and the block counter are rt_radiance_kernel's (whose
+ * comment describes them): the same rt_ray_feed.inl; LDS the same wave region (rt_plan::wave_lds_bytes).  A wave iteration is: the path
+ * segments' walk, the shade block — rt_shade_block.inl, the text the frame kernels run, with the three amendments in its three hooks —
+ * and, when some lane sampled an emitter, the shadow rays' walk through the wave's one stack region.  Both walks run to completion with
+ * EVERY lane of the wave inside: a lane without a path, or without a shadow ray, carries the null ray and is parked (walk_all states
+ * the rule).  The roulette draw follows the sample's three draws at once — it does not depend on the shadow ray — and only the
+ * sample's light waits for the walk.
  * Written besides `out`: a.counters + 7 (the watchdog word of traverse()) and the block counter a.tileQueue, both words of this pass's own. */
 template <bool FLAT, bool MANY>
 __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_radiance_nee_kernel(const KArgs a, const float4* __restrict__ rays, const int n, float4* __restrict__ out, const NeeTable lt, const uint32_t* __restrict__ unitTri)
 {
     extern __shared__ uint32_t s_lds[];
+    constexpr bool STATS = false; /* (rt_shade_block.inl reads it) */
     const int lane = (int)threadIdx.x;
     uint32_t* const stackBase = &s_lds[lane];
     uint32_t* const extBase = &s_lds[(size_t)(a.stackEntries + RT_PIXEL_FIELDS) * RT_WAVE + lane];
-    uint32_t* const bounceLds = extBase + (1 + a.extWords) * RT_WAVE; /* MANY: the bounce count lives here, as in trace_body */
 
+    /* rt_ray_feed.inl's state, as in rt_radiance_kernel */
     const int blocks = (n + RT_WAVE - 1) / RT_WAVE;
-    int poolBase = (int)blockIdx.x * RT_WAVE; /* first ray of the wave's block */
-    int poolPos = (int)blockIdx.x < blocks ? 0 : 64; /* next unassigned ray of the block, 64 = used up */
+    int poolBase = (int)blockIdx.x * RT_WAVE;
+    int poolPos = (int)blockIdx.x < blocks ? 0 : 64;
     bool queueEmpty = false;
 
     uint32_t rng = 0;
@@ -1884,47 +1881,17 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     Stats st = {};
 
     for (;;) {
-        /* ---- hand rays to idle lanes (every lane of the wave is active here) */
-        unsigned long long idle = __ballot(!pathActive);
-        while (idle) {
-            if (poolPos >= 64) {
-                if (queueEmpty) break;
-                int next = 0;
-                if (lane == 0) next = (int)atomicAdd(a.tileQueue, 1ull);
-                next = __builtin_amdgcn_readfirstlane(next) + (int)gridDim.x;
-                if (next >= blocks) { queueEmpty = true; break; }
-                poolBase = next * RT_WAVE;
-                poolPos = 0;
-            }
-            const int rank = __popcll(idle & ((1ull << lane) - 1ull));
-            const int avail = 64 - poolPos;
-            if (!pathActive && rank < avail) {
-                const int i = poolBase + poolPos + rank;
-                if (i < n) { /* inside the n * 32 and n * 16 bytes the host checked */
-                    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
-                    if (a.maxBounce >= 0) { /* RC:485: the loop runs for i = 0 */
-                        rpos = rt_v3(r0.x, r0.y, r0.z);
-                        rdir = rt_v3(r1.x, r1.y, r1.z);
-                        rng = __float_as_uint(r1.w);
-                        transmittance = rt_v3s(1.0f);
-                        pathLight = rt_v3s(0.0f);
-                        if (MANY) *bounceLds = 0u;
-                        else bounce = 0;
-                        rayIndex = i;
-                        prevSampled = false;
-                        pathActive = true;
-                    } else {
-                        out[i] = make_float4(0.0f, 0.0f, 0.0f, r1.w); /* Trace returned 0 without a draw */
-                    }
-                }
-            }
-            const int wanted = __popcll(idle);
-            poolPos += wanted < avail ? wanted : avail;
-            idle = __ballot(!pathActive);
-        }
+#define RT_FEED_ROUND
+#define RT_FEED_ARGS a
+#define RT_FEED_START(i) rayIndex = (i); prevSampled = false;
+#include "rt_ray_feed.inl"
+#undef RT_FEED_ROUND
+#undef RT_FEED_ARGS
+#undef RT_FEED_START
         if (idle == ~0ull) break; /* no lane holds a path and there is no ray left */
 
-        /* ---- the path segments: CalculateRayCollision — RC:335-374 (every lane inside, those without a path parked) */
+        /* ---- the path segments: walk_all's walk, every lane inside and those without a path parked by its rule — written out, because
+         * through the call the FLAT instantiation takes 8 bytes of scratch per lane where it had none */
         SceneHit h;
         Trav t;
         {
@@ -1942,104 +1909,41 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             }
         }
 
-        /* ---- the rest of one iteration of Trace's bounce loop — RC:488-538, rt_shade_phase.inl's block with the three amendments */
+        /* ---- the rest of one iteration of Trace's bounce loop, with the three amendments in the block's hooks */
         bool endPath = false, shadow = false;
         rt_f3 spos = rt_v3s(0.0f), sdir = rt_v3s(0.0f), sampled = rt_v3s(0.0f);
         int wantObj = -1, wantTri = -1;
         if (pathActive) {
-            if (h.obj < 0) {
-                const RT_CAS KArgs& c = cold_args();
-                if (c.useSky) pathLight = pathLight + transmittance * environment_light(c, rdir);
-                endPath = true;
-            } else {
-                rt_f3 hpos, normal;
-                resolve_hit(a, rpos, rdir, h, hpos, normal);
-                const DMaterial mat = a.materials[h.obj];
-                const bool isGlass = mat.flag == RT_MATERIAL_GLASS;
-                float uSpec = 0.0f;
-                if (!isGlass) uSpec = rt_random_value(&rng); /* RC:521 */
-                const rt_f3 diffuseDir = rt_normalize(normal + rand_direction(&rng)); /* RC:509 / RC:525 */
-                const rt_f3 specularDir = rt_reflect(rdir, normal);
-                rt_f3 lerpA = diffuseDir, lerpB = specularDir;
-                float lerpT;
-                bool sample = false;
-                if (isGlass) {
-                    if (h.backface) { /* RC:502 */
-                        rt_f3 e = ((-h.dst) * rt_v3(mat.absorption[0], mat.absorption[1], mat.absorption[2])) * mat.absorptionStrength;
-                        transmittance = transmittance * rt_v3(rt_exp(e.x), rt_exp(e.y), rt_exp(e.z));
-                    }
-                    float iorCurrent = h.backface ? mat.ior : 1.0f;
-                    float iorNext = h.backface ? 1.0f : mat.ior;
-                    const rt_f3 refractDir = refract_dir(rdir, normal, iorCurrent, iorNext);
-                    const float reflectWeight = reflectance(rdir, normal, iorCurrent, iorNext);
-                    const bool followReflection = rt_random_value(&rng) <= reflectWeight; /* RC:515 */
-                    lerpT = mat.specularProbability;
-                    if (!followReflection) {
-                        lerpA = -diffuseDir;
-                        lerpB = refractDir;
-                        lerpT = mat.smoothness;
-                    }
-                } else {
-                    const bool isSpecular = mat.specularProbability >= uSpec;
-                    lerpT = mat.smoothness * (isSpecular ? 1.0f : 0.0f);
-                    rt_f3 emitted = rt_v3(mat.emissionCol[0], mat.emissionCol[1], mat.emissionCol[2]) * mat.emissionStrength;
-                    /* amendment 3: the previous vertex's sample stood for this emission, unless it could not (no entry; a sphere from inside) */
-                    const bool counted = prevSampled && lt.inTable[h.obj] != 0u && !(h.obj < a.nSpheres && h.backface); /* h.obj < nSpheres + nModels: inside the table's flags */
-                    if (!counted) pathLight = pathLight + emitted * transmittance;
-                    transmittance = transmittance * material_colour(mat, hpos, normal, isSpecular);
-                    sample = lt.n > 0 && lerpT == 0.0f; /* amendment 2: a diffuse vertex */
-                }
-                rdir = rt_normalize(rt_lerp3(lerpA, lerpB, lerpT));
-                rpos = isGlass ? hpos + (0.001f * normal) * rt_sign(rt_dot(normal, rdir)) : hpos + (normal * 0.001f);
-                prevSampled = sample;
-                if (sample) {
-                    rt_f3 Le;
-                    float g;
-                    if (nee_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri)) {
-                        shadow = true;
-                        spos = rpos;
-                        sampled = (transmittance * Le) * g;
-                    }
-                }
-                /* RC:535-538 Russian roulette */
-                float p = rt_max(transmittance.x, rt_max(transmittance.y, transmittance.z));
-                if (rt_random_value(&rng) >= p) {
-                    endPath = true;
-                } else {
-                    transmittance = transmittance * rt_rcp(p);
-                    if (MANY) {
-                        const uint32_t b = *bounceLds + 1u;
-                        *bounceLds = b;
-                        if ((int)b > a.maxBounce) endPath = true;
-                    } else {
-                        bounce++;
-                        if (bounce > a.maxBounce) endPath = true; /* RC:485: i <= MaxBounceCount */
-                    }
-                }
-            }
+            bool sample = false; /* this vertex is a diffuse vertex at which an emitter is sampled (amendment 2) */
+/* amendment 3: the previous vertex's sample stood for this emission, unless it could not (no entry; a sphere from inside);
+ * h.obj < nSpheres + nModels: inside the table's flags */
+#define RT_SHADE_EMIT(e) \
+    if (!(prevSampled && lt.inTable[h.obj] != 0u && !(h.obj < a.nSpheres && h.backface))) pathLight = pathLight + (e)
+#define RT_SHADE_OPAQUE_END sample = lt.n > 0 && lerpT == 0.0f; /* amendment 2: a diffuse vertex */
+/* amendment 2: the three draws, ahead of the roulette draw; the sample's light waits for the shadow walk */
+#define RT_SHADE_NEXT_RAY                                                          \
+    prevSampled = sample;                                                          \
+    if (sample) {                                                                  \
+        rt_f3 Le;                                                                  \
+        float g;                                                                   \
+        if (nee_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri)) {   \
+            shadow = true;                                                         \
+            spos = rpos;                                                           \
+            sampled = (transmittance * Le) * g;                                    \
+        }                                                                          \
+    }
+#include "rt_shade_block.inl"
+#undef RT_SHADE_EMIT
+#undef RT_SHADE_OPAQUE_END
+#undef RT_SHADE_NEXT_RAY
         }
 
         /* ---- the shadow rays: the same walk from x along omega; identity with the closest hit is the visibility test */
         if (__ballot(shadow) != 0ull) { /* (wave-uniform) */
             if (!shadow) sdir = rt_v3s(0.0f);
             SceneHit sh;
-            Trav tt;
-            begin_intersect<false, FLAT, MANY>(a, spos, sdir, extBase, sh, tt, st);
-            if (FLAT) {
-                if (!shadow) sh.dst = -RT_INF;
-                traverse_flat<false>(a, spos, sdir, sh, st);
-            } else {
-                if (!shadow) {
-                    tt.cur = RT_CODE_DONE;
-                    tt.cand = 0;
-                }
-                traverse<false, false, MANY>(a, spos, sdir, stackBase, extBase, sh, tt, st, (const RT_LDS char*)nullptr, 0u);
-            }
-            if (shadow && sh.obj == wantObj) {
-                bool same = true;
-                if (wantTri >= 0) same = (unitTri ? (int)unitTri[sh.tri] : sh.tri / 3) == wantTri;
-                if (same) pathLight = pathLight + sampled;
-            }
+            walk_all<FLAT, MANY>(a, shadow, spos, sdir, stackBase, extBase, sh, st);
+            if (shadow && sh.obj == wantObj && (wantTri < 0 || hit_triangle(sh, unitTri) == wantTri)) pathLight = pathLight + sampled;
         }
 
         if (pathActive && endPath) {

@@ -1,8 +1,9 @@
 /* rt_nee_launch.h — the host arithmetic of include/rt_nee.h's two ray calls, without HIP, so that a host test reaches it
- * (tests/light_table_driver.cpp): the argument and size checks, the blocks, the grid, the bytes of the device copy of the light table
- * and the pick rule — the one function body the kernel (rt_kernels.h, nee_sample) and the host test both run.  The rays, the records
- * and the way the waves of a launch come by their blocks are rt_radiance_launch.h's, which this header forwards to; what it adds is the
- * table.  The kernel is rt_kernels.h's rt_radiance_nee_kernel; the entry points live in rt_context.hip, with the context. */
+ * (tests/light_table_driver.cpp): the bytes of the device copy of the light table and the pick rule — the one function body the kernel
+ * (rt_kernels.h, nee_sample) and the host test both run.  The rays, the records, their checks and the way the waves of a launch come
+ * by their blocks are rt_radiance_launch.h's (rt_rd::), which the calls use as they are and this namespace only names again (the
+ * host test checks them under rt_nee::); what this header adds is the table.  The
+ * kernel is rt_kernels.h's rt_radiance_nee_kernel; the entry points live in rt_context.hip, with the context. */
 #ifndef RT_NEE_LAUNCH_H
 #define RT_NEE_LAUNCH_H
 
@@ -11,18 +12,15 @@
 
 namespace rt_nee {
 
-enum { RAYS_PER_BLOCK = rt_rd::RAYS_PER_BLOCK, PICK_STEPS = 23 }; /* 2^22 entries: 22 halvings find the entry, one to spare */
+/* the blocks, the grid and the batch checks of the two calls are the radiance pass's own, under this pass's name for its host test */
+using rt_rd::RAYS_PER_BLOCK;
+using rt_rd::check_batch;
+using rt_rd::blocks;
+using rt_rd::grid;
+
+enum { PICK_STEPS = 23 }; /* 2^22 entries: 22 halvings find the entry, one to spare */
 
 static_assert((1ll << (PICK_STEPS - 1)) >= RT_NEE_MAX_LIGHTS, "the bounded search must reach every entry");
-
-/* The errors both forms share, in the order include/rt_radiance.h lists them: RT_OK and the two byte counts, or RT_ERR_INVALID_ARG and *why */
-inline int check_batch(const void* rays, int n, const void* out, size_t* rayBytes, size_t* outBytes, const char** why)
-{
-    return rt_rd::check_batch(rays, n, out, rayBytes, outBytes, why);
-}
-
-inline long long blocks(long long n) { return rt_rd::blocks(n); }
-inline long long grid(long long nBlocks, long long residentWaves, int gridOverride) { return rt_rd::grid(nBlocks, residentWaves, gridOverride); }
 
 /* The pick rule of include/rt_nee.h: the smallest i with u < cdf[i], the last entry when there is none (u == 1, a NaN).  At most
  * PICK_STEPS halvings; mid lies in [lo, hi] within [0, n - 1] at every step and the result is clamped, so no index leaves the table
