@@ -2,7 +2,8 @@
 path in Python, and the light table restated in numpy.
 
   * every path segment and every shadow ray goes through rt_query_closest (existing, bit-pinned code: tests/test_gpu_query.py holds it
-    to the oracle), all paths of a batch at once per bounce;
+    to the oracle), all paths of a batch at once per bounce; each such ray is logged (Estimator.segment_log, .shadow_log), so that a
+    test can say from the rays themselves what its batch covered;
   * the draws and the shader's functions come from the oracle: random_value, random_direction, material_colour, reflectance, refract,
     environment_light; sqrt, divide, reciprocal, rsqrt, exp, sin and cos from oracle_math_eval (rt_math.h's, which
     tests/test_gpu_math.py pins the device against); everything else is numpy float32, one rounding per operation, in the header's order;
@@ -166,6 +167,9 @@ class Estimator:
         self.materials = np.ascontiguousarray(np.concatenate([spheres["material"], models["material"]]))
         self.table = light_table(pkg.abi, models, triangles, spheres)
         self.shadow_rays = self.samples = self.unshadowed = self.suppressed = self.inside = self.triangle_samples = 0  # what a batch covered
+        # every ray trace() walked, in the order it walked them (appended to by every call; the records do not depend on them):
+        self.segment_log = []  # (ray index, bounce, origin, direction) of every path segment
+        self.shadow_log = []   # (ray index, bounce, origin, direction, wanted object, wanted triangle, unshadowed) of every shadow ray
         self._x = np.zeros(1, dtype=F)
         self._y = np.zeros(1, dtype=F)
         self._o = np.zeros(1, dtype=F)
@@ -248,6 +252,8 @@ class Estimator:
                 ended, shadows = [], []
                 for j, i in enumerate(active):
                     h, st = hits[j], rng[i]
+                    vertex = int(bounce[i])  # the path's segment, and the vertex at its end, counted from 0
+                    self.segment_log.append((int(i), vertex, pos[i].copy(), dirs[i].copy()))
                     if h["object"] < 0:
                         if p.useSky:
                             orc.environment_light(C.byref(p), F3(*dirs[i]), o3)
@@ -300,7 +306,7 @@ class Estimator:
                         s = self.sample(st, pos[i].copy(), normal)
                         if s is not None:
                             omega, g, le, want_obj, want_tri = s
-                            shadows.append((i, pos[i].copy(), omega, ((T[i] * le) * g).astype(F), want_obj, want_tri))
+                            shadows.append((i, pos[i].copy(), omega, ((T[i] * le) * g).astype(F), want_obj, want_tri, vertex))
                     pr = _max(T[i][0], _max(T[i][1], T[i][2]))
                     if self.rand(st) >= pr:
                         ended.append(i)
@@ -312,10 +318,12 @@ class Estimator:
                 if shadows:
                     sh = self.tr.query_closest(abi.make_rays(np.array([s[1] for s in shadows]), np.array([s[2] for s in shadows])))
                     self.shadow_rays += len(shadows)
-                    for (i, _, _, light, want_obj, want_tri), h in zip(shadows, sh):
-                        if int(h["object"]) == want_obj and (want_tri < 0 or int(h["triangle"]) == want_tri):
+                    for (i, spos, sdir, light, want_obj, want_tri, vertex), h in zip(shadows, sh):
+                        seen = int(h["object"]) == want_obj and (want_tri < 0 or int(h["triangle"]) == want_tri)
+                        if seen:
                             L[i] = L[i] + light
                             self.unshadowed += 1
+                        self.shadow_log.append((int(i), vertex, spos, sdir, want_obj, want_tri, seen))
                 for i in ended:
                     out["rgb"][i] = F(0) + L[i]
                     out["rng"][i] = rng[i].value
@@ -370,4 +378,22 @@ def build_scene(pkg, name):
         floor = _floor(pkg)
         floor.material = M(diffuseCol=(0.8, 0.8, 0.8, 1), specularCol=(0.8, 0.8, 0.8, 1), **mirror)
         return _desc(pkg, name, [floor], spheres, (0, 1.5, -6), sky=True)
+    if name == "nee_instances":
+        # one mesh of 320 triangles (a tree with inner nodes, its triangles reordered by the builder) under three models: an emissive
+        # instance low over the floor, an emissive instance above and beside it under a mirroring, unevenly scaled, rotated transform —
+        # the lower one hides part of it from the floor — and a dark one; a small emissive sphere; a floor and a ceiling.  The emitters
+        # are diffuse too: paths go on from them, and sample their own far side.
+        ball = pkg.meshes.icosphere(2, radius=1.0)
+        lin = T((0, 0, 0), (25, 40, 10)).rotation_matrix() @ np.diag([-0.9, 0.55, 0.75])
+        assert np.linalg.det(lin) < 0
+        m = np.eye(4)
+        m[:3, :3], m[:3, 3] = lin, (0.2, 2.4, 0.4)
+        ceiling = Model(pkg.meshes.quad(), M(diffuseCol=(0.7, 0.7, 0.7, 1), specularProbability=0.0), T((0, 5.5, 0), (-90, 0, 0), (40, 40, 1)), "Ceiling")  # (faces down:
+        # paths that leave the floor go on, and its vertices see the instances from above)
+        models = [_floor(pkg, 40.0), ceiling,
+                  Model(ball, M(diffuseCol=(0.6, 0.5, 0.4, 1), emissionCol=(1, 0.8, 0.5, 1), emissionStrength=4.0, specularProbability=0.0), T((-0.2, 1.1, 0.3), (0, 0, 0), 0.65), "BallLight"),
+                  Model(ball, M(diffuseCol=(0.4, 0.5, 0.6, 1), emissionCol=(0.4, 0.6, 1, 1), emissionStrength=6.0, specularProbability=0.0), pkg.MatrixTransform(m), "MirroredBallLight"),
+                  Model(ball, M(diffuseCol=(0.7, 0.7, 0.3, 1), specularProbability=0.0), T((2.1, 0.75, -0.6), (0, 30, 0), (0.7, 0.75, 0.6)), "DarkBall")]
+        spheres = [S((-2.3, 0.45, -0.8), 0.25, M(diffuseCol=(0, 0, 0, 1), emissionCol=(1, 0.9, 0.7, 1), emissionStrength=15.0))]
+        return _desc(pkg, name, models, spheres, (0, 3.2, -6), (22, 0, 0))  # looking down: nearly every camera ray starts a path that samples
     raise KeyError(name)

@@ -9,7 +9,9 @@ from the memo of converted pairs.  Checked here:
     oracle; height 33 and 34 refused (the two checks of SceneBuilder::convert / prepare_scene, each by its message);
   - a tree whose depth comes from the memo (deep_trees.shared): 32 accepted, 33 refused by the check behind the walk;
   - what the GPU half relies on: most camera rays of every comb it renders hold max_height entries (deep_trees.occupancy), none of the
-    control's does, and the shared tree has such rays;
+    control's does, and the shared tree has such rays; and for rt_nee's two walks, which start on a catcher quad behind the camera: a
+    quarter or more of the shadow rays towards the facing leaves and of the cosine-distributed next segments do
+    (test_conditions_the_nee_gpu_half_rests_on);
   - the oracle's traversal of comb(32) against its brute-force loop over the triangles;
   - a 40-triangle mesh the builders take to leafDepthMax == 32, the reference's MaxDepth: every host builder writes the same bytes;
     the tree has rays that hold 32 entries."""
@@ -148,6 +150,45 @@ def test_conditions_the_gpu_half_rests_on(pkg, api, height, form):
         share = dt.witness_share(nodes, tris, p, dt.W, dt.H_IMG, height, cull)
         print(f"comb({height}, {form}) cull={cull}: witness share {share:.3f} ({time.perf_counter() - t0:.1f} s)")
         assert share >= 0.5
+
+
+CATCHER_Z = -0.05              # tests/test_gpu_deep_trees.py::nee_scene: a small diffuse quad behind deep_trees.camera that faces the comb
+CATCHER_POINT = (0.1, -0.05)   # where that file's witness ray (from z = 1 along -z) meets it
+NEE_COMBS = [(1, "alternate"), (31, "alternate"), (32, "alternate"), (32, "tied")]
+
+
+@pytest.mark.parametrize("height,form", NEE_COMBS)
+def test_conditions_the_nee_gpu_half_rests_on(pkg, api, height, form):
+    """rt_nee's two walks start at a vertex on the catcher, 0.001 in front of it: a shadow ray towards a point of a comb triangle that
+    faces it, and a cosine-distributed next segment.  The GPU half looks among 64 generator states for one whose first vertex has both
+    on the stack's last row, and asserts that it finds one.  That rests on such rays being common, which is asserted here for the
+    opaque (culled) comb: at least a quarter of 300 cosine-distributed directions, and at least a quarter of 300 rays towards
+    uniformly drawn points of the even (facing) leaves, hold `height` entries.  A quarter each, with about half of the states giving
+    the first vertex a shadow ray at all, leaves 64 / 2 / 4 / 4 = 2 expected witnesses; the thresholds are what that search needs,
+    not what the combs give (the shares are printed: the cone of directions through every leaf box is wider than the view)."""
+    tris, nodes = make(pkg.abi, height, form)
+    assert api.validate_scene_arrays(*dt.one_model(pkg, tris, nodes, "emitter"))["max_height"] == height
+    x = np.array([CATCHER_POINT[0], CATCHER_POINT[1], CATCHER_Z + 0.001], dtype=F)
+    assert x[2] < 0, "behind the camera"
+    rng = np.random.default_rng(height * 7 + len(form))
+    n = 300
+    # the shader's diffuse direction: normalize(normal + a uniform direction), the normal +z
+    v = rng.normal(size=(n, 3))
+    v = v / np.linalg.norm(v, axis=1, keepdims=True) + [0, 0, 1]
+    cosine = (v / np.linalg.norm(v, axis=1, keepdims=True)).astype(F)
+    # towards points of the leaves that face -z (even j): uniform barycentric coordinates, folded like the header's
+    leaf = 2 * rng.integers(0, height // 2 + 1, n)
+    u = rng.uniform(size=(n, 2))
+    u = np.where((u.sum(axis=1) > 1)[:, None], 1 - u, u)
+    a, b, c = (tris[k][leaf].astype(np.float64) for k in ("posA", "posB", "posC"))
+    to_leaf = a + (b - a) * u[:, :1] + (c - a) * u[:, 1:] - x
+    to_leaf = (to_leaf / np.linalg.norm(to_leaf, axis=1, keepdims=True)).astype(F)
+    t0 = time.perf_counter()
+    for what, dirs in (("cosine-distributed segments", cosine), ("shadow rays towards the facing leaves", to_leaf)):
+        occ = np.array([dt.occupancy(nodes, x, d, tris, cull=True)[0] for d in dirs])
+        print(f"comb({height}, {form}) from the catcher: {int((occ == height).sum())} of {n} {what} hold {height} entries ({time.perf_counter() - t0:.1f} s)")
+        assert occ.max() <= height
+        assert (occ == height).mean() >= 0.25, what
 
 
 def test_control_and_shared_tree(pkg, api):

@@ -14,7 +14,11 @@ reference's text compiled as C++ where it travelled:
   c. rt_render_cost, rt_render_aov, rt_render_aov_centre, rt_query_closest / _occluded, rt_radiance_trace and rt_debug_intersect on
      comb(32), comb_tied(32) and the 65-model scene, the query batches with a whole wave of witness rays;
   d. a refused upload (33 levels) leaves the context rendering its previous scene;
-  e. the 40-triangle mesh that the builders take to depth 32: rt_build_bvh_gpu(_batch) against the host builder, and rendered."""
+  e. the 40-triangle mesh that the builders take to depth 32: rt_build_bvh_gpu(_batch) against the host builder, and rendered;
+  f. rt_nee_trace, the one kernel with two run-to-completion walks per wave iteration through one stack region: emissive, diffuse combs
+     of height 1, 31 and 32, the tied comb and the 65-model scene, a wave's worth of identical witness rays whose shadow ray AND next
+     segment hold H entries, against tests/nee_reference.py bit for bit (in order, reversed, as prefixes, the buffer form with guard
+     bytes), the coverage asserted from that reference's ray logs."""
 import ctypes as C
 import re
 import time
@@ -24,12 +28,13 @@ import pytest
 
 import deep_trees as dt
 import motion_reference as mref
+import nee_reference as nr
 import radiance_reference as rr
 import test_gpu_aov as ta
 import test_gpu_cost_view as tc
 import test_gpu_fuzz as tf
 import test_gpu_query as tq
-from test_deep_trees import CONE_SCALE, cone_camera, cone_mesh
+from test_deep_trees import CATCHER_POINT, CATCHER_Z, CONE_SCALE, cone_camera, cone_mesh
 from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -56,9 +61,39 @@ def crowd(pkg, n, seed=3):
             for i in range(n)]
 
 
+def nee_scene(pkg, name):
+    """comb<H>alternate-emissive | tied32-emissive | crowd65_first-emissive: the tree as model 0, untransformed, opaque, diffuse AND
+    emitting — every leaf an entry of rt_nee's light table, and a surface whose vertices sample that table; behind it (the crowd
+    scene) the first 62 models of crowd65_first, of which seven emit; then a small diffuse quad behind the camera that faces the comb,
+    the catcher — a path that starts towards it has its first vertex there, and its shadow ray and its next segment go up the comb
+    like camera rays; last a dark quad at z = 2 that stands in the way of some of those shadow rays (the only thing in front of leaf 0,
+    which in comb(1) is the only leaf that faces the catcher: without it no shadow ray of that scene could be blocked).  Both quads
+    come after the comb: its walk starts with nothing hit, as deep_trees.occupancy assumes.  65 models in the crowd scene."""
+    abi, M, T = pkg.abi, pkg.RayTracingMaterial, pkg.Transform
+    base = name[:-len("-emissive")]
+    m = re.fullmatch(r"comb(\d+)alternate", base)
+    if m:
+        tree = dt.comb(abi, int(m.group(1)), "alternate")
+    elif base == "tied32":
+        tree = dt.comb_tied(abi, 32)
+    else:
+        assert base == "crowd65_first", name
+        tree = dt.comb(abi, 32, "alternate")
+    lit = M(diffuseCol=(0.7, 0.6, 0.5, 1), specularProbability=0.0, emissionCol=(1, 0.8, 0.5, 1), emissionStrength=2.0)
+    matte = M(diffuseCol=(0.8, 0.8, 0.8, 1), specularProbability=0.0)
+    catcher = pkg.Model(pkg.meshes.quad(), matte, T((0, 0, CATCHER_Z), (0, 180, 0), (0.6, 0.6, 1)), "Catcher")  # (the Quad's front is local -z)
+    blocker = pkg.Model(pkg.meshes.quad(), matte, T((-0.8, 0.5, 2.0), (0, 0, 0), (1.5, 1.5, 1)), "Blocker")
+    models = [pkg.Model(dt.HandMesh(base, *tree), lit, T())] + (crowd(pkg, 62) if base == "crowd65_first" else []) + [catcher, blocker]
+    assert base != "crowd65_first" or len(models) == 65
+    return dt.description(pkg, name, models, maxBounceCount=2)  # (two bounces: the reference is Python)
+
+
 def scene(pkg, name):
-    """comb<H><form>[-diffuse] | tied32 | behind32 | shared32 | cube_first | cube_last | crowd<N>_first | crowd<N>_last"""
+    """comb<H><form>[-diffuse] | tied32 | behind32 | shared32 | cube_first | cube_last | crowd<N>_first | crowd<N>_last | nee_scene's"""
     if name in _SCENES:
+        return _SCENES[name]
+    if name.endswith("-emissive"):
+        _SCENES[name] = nee_scene(pkg, name)
         return _SCENES[name]
     abi = pkg.abi
     cam = None
@@ -453,3 +488,191 @@ def test_gpu_builder_takes_the_cone_to_depth_32_and_the_scene_renders_the_same_b
         assert reported and {r[1] for r in reported} == {32}, reported
         lines.append(f"cone from {where}: stack entries reported 32, {want['counters'][tf.KEYS.index('innerSteps')]} inner steps")
     print("\n".join(lines))
+
+
+# ---------------------------------------------------------------- f. rt_nee: two walks per wave iteration through one stack region
+NEE_SCENES = ["comb1alternate-emissive", "comb31alternate-emissive", "comb32alternate-emissive", "tied32-emissive", "crowd65_first-emissive"]
+_NEE = {}
+
+
+class Occupancy:
+    """deep_trees.occupancy of model 0's tree (untransformed, opaque: culled) per ray, each distinct ray walked once"""
+
+    def __init__(self, mesh):
+        self.mesh, self.memo = mesh, {}
+
+    def __call__(self, o, d):
+        key = (np.asarray(o, dtype=F).tobytes(), np.asarray(d, dtype=F).tobytes())
+        if key not in self.memo:
+            self.memo[key] = dt.occupancy(self.mesh.nodes, o, d, self.mesh.tris, cull=True)[0]
+        return self.memo[key]
+
+
+def states_whose_first_sample_picks(orc, table, triangles, count, first=1 << 16):
+    """The first `count` generator states from `first` on for which a path's first vertex, on an opaque surface, draws an entry of
+    `triangles` from the light table: the draws in front of the sample's first are the specular draw and RandomDirection's
+    (tests/nee_reference.py, Estimator.trace).  Only a choice of inputs: what the batch covers is asserted from the reference's logs."""
+    found, o3 = [], F3()
+    for s in range(first, first + (1 << 20)):
+        st = C.c_uint32(s)
+        orc.random_value(C.byref(st))
+        orc.random_direction(C.byref(st), o3)
+        if int(table["entries"][nr.pick(table["cdf"], F(orc.random_value(C.byref(st))))]["triangle"]) in triangles:
+            found.append(s)
+            if len(found) == count:
+                break
+    assert len(found) == count
+    return np.array(found, dtype=np.int64)
+
+
+def nee_arrays(pkg, api, name):
+    """((meshInfo, triangles, nodes, spheres), RtParams) of a scene by name, as tests/test_gpu_radiance.py::params_of makes them"""
+    mgr = scene(pkg, name).make_manager(None, api, W, H)
+    mgr.renderSeed = 5
+    data = mgr.CreateAllMeshData(mgr.models)
+    p = mgr.params()
+    p.frame = FRAME
+    return (data["meshInfo"], data["triangles"], data["nodes"], np.zeros(0, dtype=pkg.abi.sphere_dtype)), p
+
+
+def nee_case(pkg, api, orc, name):
+    """The scene's arrays and parameters, the witness state, witness_batch()'s pattern for this pass — 33 rays onto the catcher, the
+    witness ray 64 times over, 33 camera rays onto the comb — and the reference's records and logs of that batch: computed once."""
+    if name in _NEE:
+        return _NEE[name]
+    abi = pkg.abi
+    arrays, p = nee_arrays(pkg, api, name)
+    height = height_of(name)
+    mesh = scene(pkg, name).models[0].Mesh  # model 0: the tree, untransformed; its triangles are the uploaded triangles 0 ... H
+    occ = Occupancy(mesh)
+    tr = api.create_tracer(0)
+    try:
+        tr.upload_scene(*arrays)
+        tr.set_params(p)
+        # One run of the reference picks the generator states.  Rays 0 ... 63: the witness — a ray onto the catcher whose first vertex
+        # samples a comb triangle with a shadow ray that fills the stack, and whose next segment fills it again — is the first of the
+        # states 1 ... 64 for which the reference says so.  Behind them the 33 outer catcher rays, each with four candidate states whose
+        # first sample falls on leaf 0.  The facing leaves hide one another and the far ones are the large ones, so in the deep combs a
+        # shadow ray that reaches its triangle is rare (about one in 150), and in comb(1) only the blocker can stop one: an outer ray
+        # takes the first of its candidates whose first shadow ray fills the stack and is unshadowed (even rays) or blocked (odd
+        # rays), and keeps its own state if there is none.
+        w_origin, w_dir = (CATCHER_POINT[0], CATCHER_POINT[1], 1.0), (0.0, 0.0, -1.0)
+        k = np.arange(33)
+        c_origins = np.stack([-0.24 + 0.015 * k, 0.2 - 0.0125 * k, np.ones(33)], axis=1)
+        c_states = 1000 + 7919 * k
+        table = nr.light_table(abi, arrays[0], arrays[1], arrays[3])
+        candidates = states_whose_first_sample_picks(orc, table, {0}, 33 * 4).reshape(33, 4)
+        probe = nr.Estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
+        probe.trace(abi.make_path_rays(np.concatenate([np.tile(w_origin, (64, 1)), np.repeat(c_origins, 4, axis=0)]), np.tile(w_dir, (64 + 132, 1)),
+                                       np.concatenate([np.arange(1, 65), candidates.reshape(-1)])))
+        first_shadow = {i: (o, d, obj, tri, seen) for (i, b, o, d, obj, tri, seen) in probe.shadow_log if b == 0}
+        second_segment = {i: (o, d) for (i, b, o, d) in probe.segment_log if b == 1}
+        state, tally = None, [sum(1 for i in first_shadow if i < 64), 0, 0]
+        for i in range(64):
+            if i not in first_shadow:
+                continue
+            o, d, obj, tri, _ = first_shadow[i]
+            if not (obj == 0 and 0 <= tri <= height and occ(o, d) == height):
+                continue
+            tally[1] += 1
+            if i in second_segment and occ(*second_segment[i]) == height:
+                tally[2] += 1
+                state = i + 1 if state is None else state
+        print(f"{name}: of the states 1 ... 64, {tally[0]} give the first vertex a shadow ray, {tally[1]} of those go to the comb with occupancy {height}, "
+              f"{tally[2]} of those have a second segment of occupancy {height}; the witness state is {state}")
+        assert state is not None, f"{name}: no witness among the states 1 ... 64: {tally}"
+        for j in range(33):
+            for m in range(4)[::-1]:
+                i = 64 + 4 * j + m
+                if i in first_shadow and first_shadow[i][4] == (j % 2 == 0) and occ(*first_shadow[i][:2]) == height:
+                    c_states[j] = candidates[j, m]
+        origins, dirs, states = rr.camera_rays(orc, p, W, H, FRAME)
+        idx = np.arange(W * H)[2::11][:33]
+        o = np.concatenate([c_origins, np.tile(w_origin, (64, 1)), origins.reshape(-1, 3)[idx]]).astype(F)
+        d = np.concatenate([np.tile(w_dir, (33 + 64, 1)), dirs.reshape(-1, 3)[idx]]).astype(F)
+        s = np.concatenate([c_states, np.full(64, state), states.reshape(-1)[idx]]).astype(np.uint32)
+        rays = abi.make_path_rays(o, d, s)
+        assert len(rays) == 130
+        est = nr.Estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
+        want = est.trace(rays)
+    finally:
+        tr.close()
+    for a in (rays, want):
+        a.setflags(write=False)
+    _NEE[name] = (arrays, p, height, occ, rays, want, est)
+    return _NEE[name]
+
+
+@pytest.mark.parametrize("name", NEE_SCENES)
+def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
+    """rt_radiance_nee_kernel runs two run-to-completion walks per wave iteration through one LDS stack region: the path segments'
+    (written out) and the shadow rays' (walk_all), with the feed's bookkeeping on the row behind the stack, extBase behind that, and
+    lanes without a shadow ray parked while their neighbours push.  Here both walks stand on the last row, in the same iteration, for a
+    whole wave's worth of lanes; everything bit for bit against tests/nee_reference.py, whose own walks (rt_query_closest) are tied to
+    rt_debug_intersect on the same rays."""
+    abi = pkg.abi
+    t0 = time.perf_counter()
+    arrays, p, height, occ, rays, want, est = nee_case(pkg, api, orc, name)
+    t_ref = time.perf_counter() - t0
+    n = len(rays)
+    assert p.maxBounceCount == 2 and np.isfinite(want["rgb"]).all() and want["rgb"].any()
+    # ---- what the batch covers, from the reference's logs
+    shadow0 = {i: (o, d, seen) for (i, b, o, d, _, _, seen) in est.shadow_log if b == 0}
+    full_shadows = [(i, b, seen) for (i, b, o, d, _, _, seen) in est.shadow_log if occ(o, d) == height]
+    full_segments = [(i, b) for (i, b, o, d) in est.segment_log if occ(o, d) == height]
+    # (every ray of a block starts in the same wave iteration, so vertex 0 of the 64 witness rays is one iteration in whichever wave holds them)
+    assert all(i in shadow0 and occ(*shadow0[i][:2]) == height for i in range(33, 97)), "the 64 witness rays' first shadow rays"
+    assert sum(1 for (i, b, _) in full_shadows if b == 0) >= 64
+    assert any(seen for (_, _, seen) in full_shadows) and not all(seen for (_, _, seen) in full_shadows), "shadow rays on the last row: some unshadowed, some blocked"
+    assert full_segments and any(b > 0 for (_, b) in full_segments), "a path segment on the last row"
+    assert all(any(i == w and b == 1 for (i, b) in full_segments) for w in range(33, 97)), "the witness rays' second segments"
+    mixed = []
+    for first in range(0, n, 64):  # per block of 64 consecutive rays, the lanes of vertex 0 with and without a shadow ray
+        lanes = range(first, min(first + 64, n))
+        mixed.append((sum(1 for i in lanes if i in shadow0), len(lanes)))
+    assert any(0 < with_shadow < lanes for (with_shadow, lanes) in mixed), mixed
+    assert est.triangle_samples > 0 and est.shadow_rays > est.unshadowed > 0
+    table = nr.light_table(abi, arrays[0], arrays[1], arrays[3])
+    assert table["n_triangle_entries"] >= height + 1 and table["n_sphere_entries"] == 0
+    # ---- the device
+    guard = 64
+    tr = api.create_tracer(0)
+    try:
+        tr.upload_scene(*arrays)
+        tr.set_params(p)
+        assert tr.nee_light_count() == (table["n_sphere_entries"], table["n_triangle_entries"])
+        got = tr.radiance_trace_nee(rays)
+        rev = tr.radiance_trace_nee(rays[::-1])[::-1]
+        prefixes = {k: tr.radiance_trace_nee(rays[:k]) for k in (1, 33, 96, 97, 130)}
+        d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16 + guard, fill=0xa5)
+        tr.radiance_trace_nee_buffers(d_rays.ptr, n, d_out.ptr)
+        tr.synchronize()
+        raw = d_out.download(np.uint8)
+        d_rays.free(), d_out.free()
+        # the reference's own walks at this depth against the second device path
+        seen_rays = {}
+        for (_, _, o, d, _, _, _) in est.shadow_log:
+            seen_rays.setdefault((o.tobytes(), d.tobytes()), (o, d))
+        so, sd = np.array([v[0] for v in seen_rays.values()], dtype=F), np.array([v[1] for v in seen_rays.values()], dtype=F)
+        hits, dbg = tr.query_closest(abi.make_rays(so, sd)), tr.debug_intersect(so, sd)
+        if name == "comb32alternate-emissive":  # with the emitter put out the pass is rt_radiance_trace, bit for bit
+            dark = arrays[0].copy()
+            dark["material"]["emissionStrength"] = 0
+            tr.update_models(dark)
+            assert tr.nee_light_count() == (0, 0)
+            plain, stripped = tr.radiance_trace(rays), tr.radiance_trace_nee(rays)
+            assert stripped.tobytes() == plain.tobytes() and (stripped["rng"] != rays["rng"]).any() and stripped.tobytes() != got.tobytes()
+    finally:
+        tr.close()
+    for what, rec in [("in order", got), ("reversed", rev)] + [(f"n = {k}", part) for k, part in prefixes.items()]:
+        ref = want[:len(rec)]
+        bad = np.argwhere((rr.bits(rec["rgb"]) != rr.bits(ref["rgb"])).any(axis=1) | (rec["rng"] != ref["rng"])).ravel()
+        assert not len(bad), f"{name}, {what}: {len(bad)} of {len(rec)} records differ; first is ray {bad[0]}: got {rec[bad[0]]}, want {ref[bad[0]]}"
+        assert rec.tobytes() == ref.tobytes(), (name, what)
+    assert raw[:n * 16].tobytes() == want.tobytes() and (raw[n * 16:] == 0xa5).all(), f"{name}: buffer form"
+    assert len({r.tobytes() for r in got[33:97]}) == 1, "the 64 witness slots hold one and the same record"
+    assert tq.bits(dbg[:, 2]).tolist() == tq.bits(hits["dst"]).tolist()
+    assert tq.bits(dbg[:, 3:6]).tolist() == tq.bits(hits["normal"]).tolist() and tq.bits(dbg[:, 6:9]).tolist() == tq.bits(hits["pos"]).tolist()
+    assert np.array_equal(dbg[:, 0] != 0, (hits["hit"] & 3) != 0) and np.array_equal(dbg[:, 1] != 0, (hits["hit"] & 0x100) != 0)
+    print(f"{name}: {len(full_shadows)} shadow rays and {len(full_segments)} path segments with {height} stack entries; lanes of vertex 0 with a shadow ray per block {mixed}; "
+          f"{len(so)} distinct shadow rays against rt_debug_intersect; reference {t_ref:.1f} s, all {time.perf_counter() - t0:.1f} s")

@@ -2,25 +2,37 @@
 
   1. bit for bit, rgb and rng, against tests/nee_reference.py (the header's estimator restated path by path over rt_query_closest, the
      oracle's draws and functions, and a numpy light table): 200 camera rays and their prefixes n = 1, 63, 64, 65, maxBounceCount -1, 0,
-     1 and the scene's own, on six scenes — FLAT (three spheres, two emissive, a quad light), config 3 (triangle emitters through a
+     1 and the scene's own, on seven scenes — FLAT (three spheres, two emissive, a quad light), config 3 (triangle emitters through a
      BVH), the 70-model scene with a model and a sphere made emissive (MANY), a quad light under a mirroring transform, a glass sphere
-     between light and floor, and a camera inside an emissive sphere — and with a grid of two waves;
+     between light and floor, a camera inside an emissive sphere, and the instances of item 8 — and with a grid of two waves;
   2. the two identities: every scene with its emitters stripped, and an all-mirror scene with emitters, give rt_radiance_trace's bits;
   3. physics in closed form: the radiance a diffuse floor reflects under one spherical emitter, for NEE and for plain radiance, and the
      ratio of their variances;
   4. the same expectation as rt_radiance_trace on three scenes, 2^20 paths each way;
   5. the side-pass manners of tests/test_gpu_radiance.py: the buffer form behind updates and held-back frames and into torch tensors,
      updates that turn emission on and off, no visible state change, every error row, the pass's own watchdog word;
-  6. the entry cap through a context: RT_ERR_SCENE from the three calls, the scene still usable, and a table of exactly 2^22 entries."""
+  6. the entry cap through a context: RT_ERR_SCENE from the three calls, the scene still usable, and a table of exactly 2^22 entries;
+  7. every device layout (RT_LAYOUT at rt_upload_scene): the visibility test names a triangle by hit_triangle(), which under `dense` divides
+     the unit by 3 and under every other layout reads the unit -> triangle map, indexed in the triangle space or, under `arena`, in the
+     pair space; a wrong index would only darken the picture.  Against the reference's records computed under the default layout;
+  8. instances of one mesh with a real tree (scene nee_instances: two emissive models and a dark one share 320 triangles; the
+     uploaded triangle index is the same for both, the object alone tells them apart);
+  9. updates that move geometry: one context through a translation, a rotation with uneven scale, a mirroring transform, a moved and
+     resized sphere, an identical update, the way back, an upload of another scene, a refused upload and the first scene again — the
+     table holds world-space corners, areas, normals and probabilities, and a stale one gives plausible, wrong light.
+The stack's last row under this kernel's two walks: tests/test_gpu_deep_trees.py."""
 import ctypes as C
 import os
+import re
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import deep_trees as dt  # noqa: E402
 import nee_reference as nr  # noqa: E402
 import radiance_reference as rr  # noqa: E402
 import test_gpu_query as tq  # noqa: E402  (scenes, DevBuf, snapshot: shared, never written)
@@ -31,8 +43,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 FRAME = 3
 W, H = 20, 10  # 200 camera rays: three blocks and a partial one
-BIT_SCENES = ["nee_flat", "config3_bvh", "crowded70_emissive", "nee_mirrored", "nee_glass", "nee_inside"]
+BIT_SCENES = ["nee_flat", "config3_bvh", "crowded70_emissive", "nee_mirrored", "nee_glass", "nee_inside", "nee_instances"]
 BOUNCES = [-1, 0, 1, None]
+LAYOUTS = ["dense", "pre", "pre,align", "pre,arena", "pre,arena,cache", "pre,hot=2,arena,palign"]
+LAYOUT_SCENES = ["config3_bvh", "crowded70_emissive", "nee_instances"]
 
 _SCENES = {}
 _CASES = {}
@@ -154,6 +168,38 @@ def test_records_equal_the_reference_bit_for_bit(pkg, api, orc, name, bounce):
         assert est.shadow_rays > est.unshadowed, "some shadow ray must be blocked"
     if name == "nee_inside":
         assert est.inside > 0
+    if name == "nee_instances" and bounce is None:
+        instances_cover_what_they_are_there_for(pkg, sc, est)
+
+
+def instances_cover_what_they_are_there_for(pkg, sc, est):
+    """The mesh has a real tree, and the reference's shadow rays (its shadow_log) went to both emissive instances, to one uploaded
+    triangle under both objects, and were blocked and let through towards each."""
+    names = [m.name for m in sc.desc.models]
+    first, second, dark = (len(sc.spheres) + names.index(k) for k in ("BallLight", "MirroredBallLight", "DarkBall"))
+    mesh = sc.desc.models[names.index("BallLight")].Mesh
+    count = mesh.triangle_count
+    offsets = sc.models["triOffset"][[names.index(k) for k in ("BallLight", "MirroredBallLight", "DarkBall")]]
+    assert count >= 200 and len(set(offsets.tolist())) == 1, "three models, one mesh"
+    off, node_off = int(offsets[0]), int(sc.models["nodeOffset"][names.index("BallLight")])
+    node_end = min([int(o) for o in sc.models["nodeOffset"] if o > node_off], default=len(sc.nodes))
+    nodes = sc.nodes[node_off:node_end]
+    assert (nodes["triangleCount"] <= 0).sum() > 8 and (nodes["triangleCount"] > 0).sum() > 8, "a tree with inner nodes and many leaf runs"
+    given = mesh.vertices[mesh.triangles.reshape(-1, 3)[:, 0]]
+    assert not np.array_equal(sc.triangles["posA"][off:off + count], given), "the builder reordered the triangles"
+    assert np.linalg.det(sc.models["localToWorld"][names.index("MirroredBallLight")].reshape(4, 4)[:3, :3].astype(np.float64)) < 0
+    log = est.shadow_log
+    wanted = {obj: {t for (_, _, _, _, o, t, _) in log if o == obj} for obj in (first, second)}
+    assert wanted[first] and wanted[second], "samples on both instances"
+    assert all(off <= t < off + count for obj in wanted for t in wanted[obj])
+    assert wanted[first] & wanted[second], "no uploaded triangle index was wanted under both objects"
+    for obj in (first, second):
+        seen = [s for (_, _, _, _, o, _, s) in log if o == obj]
+        assert any(seen) and not all(seen), f"object {obj}: {sum(seen)} of {len(seen)} shadow rays unshadowed"
+    assert not any(o == dark for (_, _, _, _, o, _, _) in log)
+    assert est.suppressed > 0 and est.samples > est.triangle_samples > 0
+    print(f"nee_instances: {len(wanted[first])} / {len(wanted[second])} triangles wanted on the two instances, {len(wanted[first] & wanted[second])} on both; "
+          f"{est.suppressed} emissions left out")
 
 
 def test_a_grid_of_two_waves_draws_its_blocks_from_the_counter(pkg, api, orc, monkeypatch):
@@ -669,3 +715,155 @@ def test_more_entries_than_the_cap_is_a_scene_error_of_these_calls_only(pkg, api
     finally:
         tr.close()
         d_rays.free(), d_out.free()
+
+
+# ---------------------------------------------------------------- 7. every device layout
+def without_cache(layout):
+    """tests/test_layout.py's: `used` reports the records the cache really holds, so the cache word is compared apart"""
+    return ",".join(w for w in layout.split(",") if not w.startswith("cache")) or "dense"
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("name", LAYOUT_SCENES)
+def test_every_device_layout_gives_the_references_records(pkg, api, orc, monkeypatch, capfd, name, layout):
+    """RT_LAYOUT is read by rt_upload_scene (prepare_scene), not by rt_create: it stays set until the scene is uploaded, and the upload's
+    own report (RT_DEBUG_UPLOAD) must name the layout asked for — a context that took the default, or a scene that silently fell back
+    to `dense`, would make the case empty."""
+    t0 = time.perf_counter()
+    monkeypatch.delenv("RT_LAYOUT", raising=False)
+    sc, p, rays, want, est = case(pkg, api, orc, name, None)  # the reference walked its rays under the default layout
+    used = api.layout_arrays(sc.models, sc.triangles, sc.nodes, layout)["used"]  # (no device needed)
+    assert without_cache(used) == without_cache(layout), f"asked for {layout}, the scene is laid out as {used}"
+    assert (used == "dense") == (layout == "dense")
+    monkeypatch.setenv("RT_LAYOUT", layout)
+    monkeypatch.setenv("RT_DEBUG_UPLOAD", "1")
+    tr = api.create_tracer(0)
+    try:
+        capfd.readouterr()
+        sc.upload(tr)
+        reported = re.findall(r"prepare_scene: layout (\S+)", capfd.readouterr().err)
+        monkeypatch.delenv("RT_LAYOUT")
+        monkeypatch.delenv("RT_DEBUG_UPLOAD")
+        tr.set_params(p)
+        got = tr.radiance_trace_nee(rays)
+        counts = tr.nee_light_count()
+    finally:
+        tr.close()
+    assert [without_cache(r) for r in reported] == [without_cache(used)], f"asked for {layout}: the upload reports {reported}, rt_debug_layout {used}"
+    assert_records(got, want, f"{name}, RT_LAYOUT={layout}")
+    assert got.tobytes() == want.tobytes()
+    assert counts == (est.table["n_sphere_entries"], est.table["n_triangle_entries"])
+    assert est.triangle_samples > 0, "no vertex sampled a triangle entry"
+    on_triangles = [seen for (_, _, _, _, _, tri, seen) in est.shadow_log if tri >= 0]
+    assert any(on_triangles) and est.unshadowed > 0, "no shadow ray towards a triangle entry was unshadowed: a wrong triangle index would not show"
+    print(f"{name}, RT_LAYOUT={layout} (used: {used}): {sum(on_triangles)} of {len(on_triangles)} shadow rays towards triangles unshadowed; {time.perf_counter() - t0:.1f} s")
+
+
+# ---------------------------------------------------------------- 9. updates that move geometry
+def with_transform(pkg, models, index, matrix):
+    """A copy of the model array with model `index` under the 4 x 4 localToWorld `matrix`"""
+    out = models.copy()
+    m = np.asarray(matrix, dtype=np.float64)
+    out["localToWorld"][index] = pkg.manager.matrix_to_abi(m)
+    out["worldToLocal"][index] = pkg.manager.matrix_to_abi(np.linalg.inv(m))
+    return out
+
+
+def test_one_context_through_updates_that_move_emitters(pkg, api, orc):
+    """The steps of the module text's item 9.  After every step: a buffer-form call enqueued right behind it (no synchronise), then the
+    host form; both == a fresh context that was given the step's arrays; rt_nee_light_count == that context's == the numpy table's; on
+    the steps marked so, also == the reference rebuilt from the step's arrays."""
+    abi = pkg.abi
+    t0 = time.perf_counter()
+    first, other = scene(pkg, api, "nee_flat"), scene(pkg, api, "nee_instances")
+    p, rays = camera_batch(pkg, api, orc, first, 16, 8, 2)
+    n = len(rays)
+    names = [m.name for m in first.desc.models]
+    light = names.index("QuadLight")
+    T = pkg.Transform
+    assert nr.light_table(abi, first.models, first.triangles, first.spheres)["in_table"][len(first.spheres) + light]
+    moved = with_transform(pkg, first.models, light, T((-0.7, 3.0, 0.6), (-90, 0, 0), (1.5, 1.0, 1)).localToWorldMatrix)
+    turned = with_transform(pkg, first.models, light, T((-0.7, 3.0, 0.6), (-70, 25, 10), (2.2, 0.6, 1)).localToWorldMatrix)
+    mirror = np.array([[1.5, 0, 0, 0.3], [0, 0, 1, 2.5], [0, 1.2, 0, 0.2], [0, 0, 0, 1]], dtype=np.float64)  # (nee_mirrored's: local -z -> world -y)
+    assert np.linalg.det(mirror[:3, :3]) < 0
+    mirrored = with_transform(pkg, first.models, light, mirror)
+    spheres = first.spheres.copy()
+    assert spheres["material"]["emissionStrength"][1] > 0
+    spheres["centre"][1], spheres["radius"][1] = (-1.5, 2.8, -0.3), 2 * first.spheres["radius"][1]
+    deep = dt.one_model(pkg, *dt.comb(abi, 33))  # 33 levels: refused
+
+    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    tr = api.create_tracer(0)
+    records, lines = {}, []
+
+    def check(step, arrays, reference):
+        """Called right behind the step's update or upload."""
+        tr.radiance_trace_nee_buffers(d_rays.ptr, n, d_out.ptr)  # no synchronise in between
+        host = tr.radiance_trace_nee(rays)
+        tr.synchronize()
+        behind = d_out.download(abi.RADIANCE_DTYPE)
+        counts = tr.nee_light_count()
+        models, triangles, nodes, sph = arrays
+        table = nr.light_table(abi, models, triangles, sph)
+        fresh = api.create_tracer(0)
+        try:
+            fresh.upload_scene(models, triangles, nodes, sph)
+            fresh.set_params(p)
+            want = fresh.radiance_trace_nee(rays)
+            assert fresh.nee_light_count() == counts, step
+            if reference:
+                est = nr.Estimator(pkg, orc, fresh, models, triangles, sph, p)
+                ref = est.trace(rays)
+                assert_records(host, ref, f"step {step} against the reference")
+                assert est.shadow_rays > est.unshadowed > 0, step
+        finally:
+            fresh.close()
+        assert counts == (table["n_sphere_entries"], table["n_triangle_entries"]) and sum(counts) > 0, (step, counts)
+        assert behind.tobytes() == want.tobytes(), f"step {step}: the pass enqueued behind it != a context that was given its arrays"
+        assert host.tobytes() == want.tobytes(), f"step {step}: host form"
+        assert np.isfinite(host["rgb"]).all() and host["rgb"].any()
+        records[step] = (host, counts)
+        lines.append(f"step {step}: lights {counts}")
+        return host
+
+    try:
+        tr.upload_scene(first.models, first.triangles, first.nodes, first.spheres)
+        tr.set_params(p)
+        at_first = (first.models, first.triangles, first.nodes, first.spheres)
+        check("0", at_first, False)
+        tr.update_models(moved)
+        check("a", (moved, first.triangles, first.nodes, first.spheres), True)
+        tr.update_models(turned)
+        check("b", (turned, first.triangles, first.nodes, first.spheres), False)
+        tr.update_models(mirrored)
+        check("c", (mirrored, first.triangles, first.nodes, first.spheres), True)
+        for prev, step in (("0", "a"), ("a", "b"), ("b", "c")):  # otherwise the update was not seen
+            assert records[step][0].tobytes() != records[prev][0].tobytes(), f"step {step} left the records of step {prev}"
+        tr.update_spheres(spheres)
+        check("d", (mirrored, first.triangles, first.nodes, spheres), True)
+        assert records["d"][0].tobytes() != records["c"][0].tobytes()
+        tr.update_models(mirrored.copy())  # byte-identical updates
+        tr.update_spheres(spheres.copy())
+        check("e", (mirrored, first.triangles, first.nodes, spheres), False)
+        assert records["e"][0].tobytes() == records["d"][0].tobytes() and records["e"][1] == records["d"][1]
+        tr.update_models(first.models)
+        tr.update_spheres(first.spheres)
+        check("f", at_first, False)
+        assert records["f"][0].tobytes() == records["0"][0].tobytes() and records["f"][1] == records["0"][1]
+        assert (len(other.triangles), len(other.models), len(other.spheres)) != (len(first.triangles), len(first.models), len(first.spheres))
+        tr.upload_scene(other.models, other.triangles, other.nodes, other.spheres)
+        at_other = (other.models, other.triangles, other.nodes, other.spheres)
+        check("g", at_other, True)
+        assert records["g"][1] != records["0"][1]
+        with pytest.raises(abi.RtError) as e:
+            tr.upload_scene(*deep, None)
+        assert e.value.status == abi.RT_ERR_SCENE and "BVH depth 33 > 32" in str(e.value), str(e.value)
+        check("h", at_other, False)
+        assert records["h"][0].tobytes() == records["g"][0].tobytes() and records["h"][1] == records["g"][1]
+        tr.upload_scene(first.models, first.triangles, first.nodes, first.spheres)
+        check("i", at_first, False)
+        assert records["i"][0].tobytes() == records["0"][0].tobytes() and records["i"][1] == records["0"][1]
+    finally:
+        tr.close()
+        d_rays.free(), d_out.free()
+    print("\n".join(lines + [f"{time.perf_counter() - t0:.1f} s"]))

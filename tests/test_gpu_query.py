@@ -555,11 +555,11 @@ def test_device_layout_does_not_change_the_records(pkg, api, orc, monkeypatch):
     rays = pkg.abi.make_rays(origins, dirs, tmax=np.where(want10[:, 0] != 0, want10[:, 2] * F(1.5), F(1)).astype(F))
     out = []
     for layout in ("dense", "pre,arena,cache"):  # the layouts tests/test_gpu_cost_view.py cycles through
-        monkeypatch.setenv("RT_LAYOUT", layout)
+        monkeypatch.setenv("RT_LAYOUT", layout)  # read by rt_upload_scene
         tr = api.create_tracer(0)
-        monkeypatch.delenv("RT_LAYOUT")
         try:
             sc.upload(tr)
+            monkeypatch.delenv("RT_LAYOUT")
             out.append((tr.query_closest(rays), tr.query_occluded(rays)))
         finally:
             tr.close()
