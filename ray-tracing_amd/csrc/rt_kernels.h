@@ -32,6 +32,7 @@
 
 #include "../../include/rt_abi.h"
 #include "../../include/rt_math.h"
+#include "rt_math_device.h" /* rtd_*: the kernels' sequences for log, exp, pow, sin / cos and smoothstep — the same bits */
 #include "rt_device.h"
 #include "rt_tile_cand.h"
 #include "rt_nee_launch.h"
@@ -107,8 +108,8 @@ __device__ __forceinline__ void phase_mark(Stats& st, int ph)
 __device__ __forceinline__ float rand_normal(uint32_t* state)
 {
     float theta = 2 * 3.1415926f * rt_random_value(state);
-    float rho = rt_sqrt(-2 * rt_log(rt_random_value(state)));
-    return rho * rt_cos(theta);
+    float rho = rt_sqrt(-2 * rtd_log(rt_random_value(state)));
+    return rho * rtd_cos(theta);
 }
 __device__ __forceinline__ rt_f3 rand_direction(uint32_t* state)
 {
@@ -128,7 +129,7 @@ __device__ __forceinline__ rt_f2 rand_circle(uint32_t* state)
 {
     float angle = rt_random_value(state) * 2 * 3.1415f;
     float c, s;
-    rt_sincos(angle, &s, &c); /* == rt_cos(angle), rt_sin(angle): one shared range reduction */
+    rtd_sincos(angle, &s, &c); /* == rt_cos(angle), rt_sin(angle): one shared range reduction */
     float r = rt_sqrt(rt_random_value(state));
     rt_f2 o = {c * r, s * r};
     return o;
@@ -138,12 +139,12 @@ __device__ __forceinline__ rt_f2 rand_circle(uint32_t* state)
 template <class Args>
 __device__ __forceinline__ rt_f3 environment_light(const Args& a, rt_f3 dir)
 {
-    float skyGradientT = rt_pow(rt_smoothstep_edges(0.0f, 0.4f, dir.y), 0.35f);
-    float groundToSkyT = rt_smoothstep_edges(-0.01f, 0.0f, dir.y);
+    float skyGradientT = rtd_pow(rtd_smoothstep_edges(0.0f, 0.4f, dir.y), 0.35f);
+    float groundToSkyT = rtd_smoothstep_edges(-0.01f, 0.0f, dir.y);
     rt_f3 skyGradient = rt_lerp3(rt_v3(1, 1, 1), rt_v3(0.08f, 0.37f, 0.73f), skyGradientT);
     float s = rt_div(1000 * 1, a.sunFocus);
     rt_f3 toSun = rt_v3(a.dirToSun[0], a.dirToSun[1], a.dirToSun[2]);
-    float sun = rt_pow(rt_max(0.0f, rt_dot(dir, toSun)), s) * a.sunIntensity;
+    float sun = rtd_pow(rt_max(0.0f, rt_dot(dir, toSun)), s) * a.sunIntensity;
     float gate = (groundToSkyT >= 1.0f) ? 1.0f : 0.0f;
     return rt_lerp3(rt_v3(0.35f, 0.3f, 0.35f), skyGradient, groundToSkyT)
            + sun * rt_v3(a.sunColour[0], a.sunColour[1], a.sunColour[2]) * gate;
@@ -264,7 +265,9 @@ struct TriWant {
     uint32_t wave; /* wave-uniform: triangles some active lane may be accepted by; all ones = no table */
     uint32_t lane; /* this lane's own mask (read by the stats build's audit only) */
 };
-template <bool STATS, bool FLAT, bool MANY, bool ANY = false, bool PRIMARY = false>
+/* TRACE: the call comes from a FLAT trace kernel (the frame's hot loop): the general sphere loop below then keeps its shared reciprocal
+ * behind the candidate test, see there; every other caller compiles the code it always had. */
+template <bool STATS, bool FLAT, bool MANY, bool ANY = false, bool PRIMARY = false, bool TRACE = false>
 __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f3 rdir, uint32_t* extBase, SceneHit& h, Trav& t, Stats& st, const float tmax = 0.0f,
                                                 const RT_CAS PrimaryTable* pt = nullptr, const uint32_t* tileCand = nullptr, const uint32_t tile = 0u,
                                                 TriWant* tw = nullptr)
@@ -385,6 +388,15 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
                 cand |= ((keep0 ? 1u : 0u) << k) | ((keep1 ? 1u : 0u) << (k + 1));
             }
             if (ANY && h.dst < tmax) cand = 0;
+            /* TRACE: the reciprocal both roots share is computed by the lanes that hold a candidate, behind this test, as in the table branch.
+             * Left in the loop it is loop-invariant and free of side effects, so the compiler moves all of it, its 11-instruction IEEE form
+             * included, in front of the pre-test, where every lane of every wave pays for it; the empty asm pins the operand to this block. */
+            float inv2aFlat = 0.0f;
+            if (TRACE && cand != 0u) {
+                float twoA = 2 * qa;
+                asm volatile("" : "+v"(twoA));
+                inv2aFlat = rt_rcp(twoA);
+            }
             while (cand) {
                 phase_mark<STATS>(st, PH_SPHERE_ROOTS);
                 const int k = __builtin_ctz(cand);
@@ -404,7 +416,7 @@ __device__ __forceinline__ void begin_intersect(const KArgs& a, rt_f3 rpos, rt_f
                 float disc = qb * qb - 4 * qa * qc;
                 if (!(disc >= 0)) continue; /* RC:304: a false positive of phase 1 ends here */
                 float sq = rt_sqrt(disc);
-                const float inv2a = rt_rcp(2 * qa); /* both roots share the reciprocal (rt_div) */
+                const float inv2a = TRACE ? inv2aFlat : rt_rcp(2 * qa); /* both roots share the reciprocal (rt_div) */
                 float dstNear = rt_max(0.0f, (-qb - sq) * inv2a);
                 float dstFar = (-qb + sq) * inv2a;
                 if (dstFar >= 0) {
@@ -1455,11 +1467,11 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
                         const uint32_t* const tileCand = cold_args().tileCand;
                         const uint32_t tile = tileCand ? __float_as_uint(PX_COLD(cold_args())[RT_WAVE].w) : 0u;
                         TriWant tw = {0xffffffffu, 0xffffffffu}; /* (no table: every triangle) */
-                        begin_intersect<STATS, FLAT, MANY, false, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt, tileCand, tile, &tw);
+                        begin_intersect<STATS, FLAT, MANY, false, true, true>(a, rpos, rdir, extBase, h, t, st, 0.0f, pt, tileCand, tile, &tw);
                         if (STATS || tw.wave != 0u) /* (no lane's tile meets a triangle: sky; the stats build goes in to count and audit) */
                             traverse_flat<STATS, false, true>(a, rpos, rdir, h, st, 0.0f, pt, tw.wave, tw.lane);
                     } else {
-                        begin_intersect<STATS, FLAT, MANY>(a, rpos, rdir, extBase, h, t, st);
+                        begin_intersect<STATS, FLAT, MANY, false, false, true>(a, rpos, rdir, extBase, h, t, st);
                         traverse_flat<STATS>(a, rpos, rdir, h, st);
                     }
                     segments++;
@@ -1823,7 +1835,7 @@ __device__ __forceinline__ bool nee_sample(const NeeTable& lt, uint32_t* rng, co
         const float ct = 1.0f - u1 * q;
         const float st = rt_sqrt(rt_max(0.0f, 1.0f - ct * ct));
         float sn, cs;
-        rt_sincos(2 * 3.1415926f * u2, &sn, &cs);
+        rtd_sincos(2 * 3.1415926f * u2, &sn, &cs);
         const rt_f3 z = rt_normalize(w);
         const float sg = rt_u2f(0x3f800000u | (rt_f2u(z.z) & 0x80000000u));
         const float a = -rt_rcp(sg + z.z);
@@ -1977,23 +1989,25 @@ __global__ void __launch_bounds__(RT_WAVE) rt_debug_intersect_kernel(const KArgs
         r[9] = (float)a.materials[h.obj].flag;
     }
 }
-/* op codes as oracle_math_eval: 0 log 1 exp 2 sin 3 cos 4 sqrt 5 pow 6 div 7 smoothstep(0,y,x) */
+/* op codes as oracle_math_eval: 0 log 1 exp 2 sin 3 cos 4 sqrt 5 pow 6 div 7 smoothstep(0,y,x); device only: 10 / 11 the sine / cosine of the shared
+ * reduction.  Each function as the kernels evaluate it: rt_math_device.h's sequence where there is one. */
 __global__ void rt_debug_math_kernel(int op, const float* x, const float* y, float* out, int n)
 {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float r = 0.0f;
     switch (op) {
-    case 0: r = rt_log(x[i]); break;
-    case 1: r = rt_exp(x[i]); break;
-    case 2: r = rt_sin(x[i]); break;
-    case 3: r = rt_cos(x[i]); break;
+    case 0: r = rtd_log(x[i]); break;
+    case 1: r = rtd_exp(x[i]); break;
+    case 2: r = rtd_sin(x[i]); break;
+    case 3: r = rtd_cos(x[i]); break;
     case 4: r = rt_sqrt(x[i]); break;
-    case 5: r = rt_pow(x[i], y[i]); break;
+    case 5: r = rtd_pow(x[i], y[i]); break;
     case 6: r = rt_div(x[i], y[i]); break;
     case 8: r = rt_rsqrt(x[i]); break;
     case 9: r = rt_rcp(x[i]); break;
-    case 7: r = rt_smoothstep(0.0f, y[i], x[i]); break;
+    case 7: r = rtd_smoothstep(0.0f, y[i], x[i]); break;
+    case 10: case 11: { float s, c; rtd_sincos(x[i], &s, &c); r = op == 10 ? s : c; } break;
     }
     out[i] = r;
 }

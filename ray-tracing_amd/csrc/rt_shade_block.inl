@@ -40,7 +40,7 @@
                     phase_mark<STATS>(st, PH_GLASS);
                     if (h.backface) { /* RC:502 */
                         rt_f3 e = ((-h.dst) * rt_v3(mat.absorption[0], mat.absorption[1], mat.absorption[2])) * mat.absorptionStrength;
-                        transmittance = transmittance * rt_v3(rt_exp(e.x), rt_exp(e.y), rt_exp(e.z));
+                        transmittance = transmittance * rt_v3(rtd_exp(e.x), rtd_exp(e.y), rtd_exp(e.z));
                     }
                     float iorCurrent = h.backface ? mat.ior : 1.0f;
                     float iorNext = h.backface ? 1.0f : mat.ior;

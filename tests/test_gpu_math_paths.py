@@ -1,0 +1,73 @@
+"""The kernels' own sequences for log, exp, pow, sine / cosine and smoothstep (ray-tracing_amd/csrc/rt_math_device.h: exact-product fusions, class tests
+in fewer compares) give the bits of include/rt_math.h on the host.
+
+Through the debug math entry point, against the oracle's build of include/rt_math.h.  Per function: a
+stratified sample of 2^20 arguments — one bit pattern drawn from each run of 4,096 consecutive ones, so every binade of both signs and the
+NaN space are covered — in ascending order, which fills most wavefronts with one class of argument (the wave-uniform paths run), then the
+same arguments with a NaN in every wavefront (the per-lane paths run); and an edge list: the zeros, the subnormal boundaries, the class
+thresholds the source names with their neighbours, the infinities, NaN, and the ends of [0, 2 pi].  tools/ubench/exact_math.hip is the
+exhaustive form of this (all 2^32 arguments, device against device); this is the part that runs with the suite."""
+import numpy as np
+import pytest
+
+from test_math import OPS, ev
+
+pytestmark = pytest.mark.gpu
+
+DEVICE_OPS = dict(OPS, sincos_sin=10, sincos_cos=11)  # rt_sincos has no host op: its halves equal rt_sin / rt_cos bit for bit
+HOST_OP = {"sincos_sin": "sin", "sincos_cos": "cos"}
+
+
+def neighbours(words):
+    w = np.array(words, dtype=np.uint32)
+    w = np.concatenate([w - 1, w, w + 1])
+    return np.concatenate([w, w ^ np.uint32(0x80000000)])
+
+
+EDGE_BITS = np.concatenate([
+    np.array([0x00000000, 0x80000000, 0x7f800000, 0xff800000, 0x7fc00000, 0xffc00000, 0x7f800001, 0x00000001, 0x007fffff, 0x00800000, 0x7f7fffff], dtype=np.uint32),
+    neighbours([0x00800000, 0x3f800000, 0x3f3504f3, 0x7f800000]),                                      # rt_log: subnormal bound, 1, sqrt(2)/2, inf
+    neighbours([0x42aeac50, 0x42b17218, 0x42cff1b5, 0x3eb17218, 0x3f851592, 0x39000000]),              # rt_exp: 87.34, overflow, underflow, ln2/2, 3 ln2/2, 2^-14
+    neighbours([0x46ea6000, 0x40c90fdb, 0x3f490fdb, 0x3fc90fdb, 0x40490fdb, 0x4096cbe4, 0x3f000000]),  # 3e4, 2 pi, pi/4, pi/2, pi, 3 pi/2, 0.5
+    neighbours([0x3ecccccd, 0xbc23d70a, 0x3f7fffff]),                                                  # smoothstep edges 0.4, -0.01, just below 1
+])
+
+
+@pytest.fixture(scope="module")
+def sample():
+    rng = np.random.default_rng(1717)
+    bits = (np.arange(1 << 20, dtype=np.uint64) << 12 | rng.integers(0, 4096, 1 << 20, dtype=np.uint64)).astype(np.uint32)
+    edge = np.resize(EDGE_BITS, (len(EDGE_BITS) + 63) // 64 * 64)
+    x = np.concatenate([bits, edge]).view(np.float32)
+    poisoned = x.copy()
+    poisoned[::64] = np.nan
+    return np.concatenate([x, poisoned, x[::64]])  # (the arguments the NaNs replaced, once more)
+
+
+@pytest.mark.parametrize("op,y", [("log", None), ("exp", None), ("sin", None), ("cos", None), ("sincos_sin", None), ("sincos_cos", None),
+                                  ("smoothstep", 1.0 / 0.4), ("smoothstep", 1.0 / 0.01), ("pow", 0.35), ("pow", 240.0)])
+def test_device_sequences_give_the_host_bits(api, orc, sample, op, y):
+    x = sample
+    yy = None if y is None else np.full_like(x, np.float32(y))
+    tr = api.create_tracer(0)
+    got = tr.debug_math_eval(DEVICE_OPS[op], x, yy) if yy is not None else tr.debug_math_eval(DEVICE_OPS[op], x)
+    tr.close()
+    want = ev(orc, HOST_OP.get(op, op), x, yy)
+    nan = np.isnan(want)
+    assert np.array_equal(np.isnan(got), nan), op
+    bad = got.view(np.uint32)[~nan] != want.view(np.uint32)[~nan]
+    assert not bad.any(), (op, int(bad.sum()), x[~nan][bad][:5].view(np.uint32))
+
+
+def test_tracer_range_of_the_trigonometric_functions(api, orc):
+    """[0, 2 pi], the only arguments the tracer passes: every 16th of its 2^30.3 bit patterns would be too many; 2^20 evenly spaced patterns
+    and the ends"""
+    top = int(np.float32(6.2831855).view(np.uint32))
+    bits = np.unique(np.concatenate([np.linspace(0, top, 1 << 20).astype(np.uint64), np.array([0, 1, top - 1, top, top + 1], dtype=np.uint64)])).astype(np.uint32)
+    x = bits.view(np.float32)
+    tr = api.create_tracer(0)
+    for op in ("sin", "cos", "sincos_sin", "sincos_cos"):
+        got = tr.debug_math_eval(DEVICE_OPS[op], x)
+        want = ev(orc, HOST_OP.get(op, op), x)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), op
+    tr.close()

@@ -2,9 +2,13 @@
 // square root (the arithmetic contract of include/rt_math.h: rt_rcp(x) = 1.0f / x, rt_sqrt = IEEE sqrt) BIT FOR BIT.
 // Every one of the 2^32 bit patterns is evaluated; mismatches are counted per candidate, inside and outside the
 // guarded range the fast path would accept.   hipcc -O3 --offload-arch=gfx950 -ffp-contract=off exact_math.hip -o exact_math
+// Second part (sweep_cuts): the kernels' sequences (ray-tracing_amd/csrc/rt_math_device.h, rtd_*) side by side with include/rt_math.h's, which
+// they restate in fewer issue slots: every function compared over all 2^32 arguments.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+
+#include "../../ray-tracing_amd/csrc/rt_math_device.h"
 
 __device__ __forceinline__ float f_of(uint32_t u) { return __uint_as_float(u); }
 
@@ -71,11 +75,20 @@ __device__ __forceinline__ float div_fast(float a, float b)
     return __builtin_fmaf(r, y, q);
 }
 
+// the same without the Newton step on the reciprocal: a candidate for rt_div_narrow (kept only if it never differs from the IEEE quotient)
+__device__ __forceinline__ float div_fast_raw(float a, float b)
+{
+    float y = __builtin_amdgcn_rcpf(b);
+    float q = a * y;
+    float r = __builtin_fmaf(-b, q, a);
+    return __builtin_fmaf(r, y, q);
+}
+
 // counters: [0] rcp_a in range, [1] rcp_a out of range, [2] rcp_b in, [3] rcp_b out, [4] sqrt_a in, [5] sqrt_a out, [6] sqrt_b in, [7] sqrt_b out
 __global__ void sweep(unsigned long long* cnt, uint32_t* firstBad)
 {
     const uint32_t stride = gridDim.x * blockDim.x;
-    unsigned long long c[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long c[18] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (uint64_t u64 = blockIdx.x * blockDim.x + threadIdx.x; u64 < (1ull << 32); u64 += stride) {
         const uint32_t u = (uint32_t)u64;
         const float x = f_of(u);
@@ -100,6 +113,7 @@ __global__ void sweep(unsigned long long* cnt, uint32_t* firstBad)
         if (x >= -0.30f && x <= 0.42f) {
             const float b = 2.0f + x;
             if (__float_as_uint(div_fast(x, b)) != __float_as_uint(x / b)) { c[12]++; atomicMin(&firstBad[2], u); }
+            if (__float_as_uint(div_fast_raw(x, b)) != __float_as_uint(x / b)) c[16]++;
             c[13]++;
         }
         // the one division of rt_exp: x * c / (2 - c), c = x - x^2 (P1 + x^2 P2), reduced |x| <= 0.5 ln 2 (swept to 0.36)
@@ -109,10 +123,43 @@ __global__ void sweep(unsigned long long* cnt, uint32_t* firstBad)
             const float cc = x - xx * (P1 + xx * P2);
             const float a = x * cc, b = 2.0f - cc;
             if (__float_as_uint(div_fast(a, b)) != __float_as_uint(a / b)) c[14]++;
+            if (__float_as_uint(div_fast_raw(a, b)) != __float_as_uint(a / b)) c[17]++;
             c[15]++;
         }
     }
-    for (int k = 0; k < 16; k++)
+    for (int k = 0; k < 18; k++)
+        if (c[k]) atomicAdd(&cnt[k], c[k]);
+}
+
+// rt_math_device.h against rt_math.h, all 2^32 arguments.  A difference counts unless both results are NaNs.
+// counters: [0] log [1] exp [2] sin [3] cos [4] sincos.s [5] sincos.c [6] smoothstep(0, 1/0.4, x) [7] smoothstep(-0.01, 1/0.01, x) [8] pow(x, 0.35)
+//           [9] sincos against sin / cos of the same build; first[k] = the lowest differing bit pattern
+__device__ __forceinline__ bool differ(float a, float b)
+{
+    const uint32_t ua = __float_as_uint(a), ub = __float_as_uint(b);
+    return ua != ub && !((ua & 0x7fffffffu) > 0x7f800000u && (ub & 0x7fffffffu) > 0x7f800000u);
+}
+// poison: that lane of every wavefront gets a NaN instead of its argument, so that the other 63 run the per-lane code behind the wave-uniform
+// branches (RT_WAVE_ALL) on ordinary arguments too; -1 = none.  main() runs none, lane 0 and lane 1: every argument meets both kinds of path.
+__global__ void sweep_cuts(unsigned long long* cnt, uint32_t* first, const int poison)
+{
+    const uint32_t stride = gridDim.x * blockDim.x;
+    unsigned long long c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    for (uint64_t u64 = blockIdx.x * blockDim.x + threadIdx.x; u64 < (1ull << 32); u64 += stride) {
+        const uint32_t u = (uint32_t)u64;
+        const float x = (int)(threadIdx.x & 63u) == poison ? f_of(0x7fc00000u) : f_of(u);
+        float sa, ca, sb, cb;
+        rtd_sincos(x, &sa, &ca);
+        rt_sincos(x, &sb, &cb);
+        const bool d[10] = {differ(rtd_log(x), rt_log(x)), differ(rtd_exp(x), rt_exp(x)), differ(rtd_sin(x), rt_sin(x)),
+                            differ(rtd_cos(x), rt_cos(x)), differ(sa, sb), differ(ca, cb),
+                            differ(rtd_smoothstep(0.0f, 1.0f / 0.4f, x), rt_smoothstep(0.0f, 1.0f / 0.4f, x)),
+                            differ(rtd_smoothstep(-0.01f, 1.0f / 0.01f, x), rt_smoothstep(-0.01f, 1.0f / 0.01f, x)),
+                            differ(rtd_pow(x, 0.35f), rt_pow(x, 0.35f)), differ(sa, rtd_sin(x)) || differ(ca, rtd_cos(x))};
+        for (int k = 0; k < 10; k++)
+            if (d[k]) { c[k]++; atomicMin(&first[k], u); }
+    }
+    for (int k = 0; k < 10; k++)
         if (c[k]) atomicAdd(&cnt[k], c[k]);
 }
 
@@ -120,14 +167,14 @@ int main()
 {
     unsigned long long* d;
     uint32_t* fb;
-    hipMalloc(&d, 128);
-    hipMemset(d, 0, 128);
+    hipMalloc(&d, 144);
+    hipMemset(d, 0, 144);
     hipMalloc(&fb, 16);
     hipMemset(fb, 0xff, 16);
     hipLaunchKernelGGL(sweep, dim3(256 * 16), dim3(256), 0, 0, d, fb);
-    unsigned long long h[16];
+    unsigned long long h[18];
     uint32_t hb[4];
-    hipMemcpy(h, d, 128, hipMemcpyDeviceToHost);
+    hipMemcpy(h, d, 144, hipMemcpyDeviceToHost);
     hipMemcpy(hb, fb, 16, hipMemcpyDeviceToHost);
     const char* names[4] = {"rcp: v_rcp_f32 + 1 fma-Newton step", "rcp: v_rcp_f32 + 2 fma-Newton steps", "sqrt: v_rsq_f32 + 1 fma step", "sqrt: v_rsq_f32 + 2 fma steps"};
     for (int k = 0; k < 4; k++)
@@ -136,5 +183,27 @@ int main()
     printf("%-40s mismatches: %llu in the guarded range, %llu outside\n", "sqrt: v_sqrt_f32 + residual * 0.5 rsq", h[10], h[11]);
     printf("%-40s mismatches: %llu of %llu arguments (first mismatching f bits 0x%08x)\n", "log's division f/(2+f), fast form", h[12], h[13], hb[2]);
     printf("%-40s mismatches: %llu of %llu arguments\n", "exp's division x*c/(2-c), fast form", h[14], h[15]);
-    return 0;
+    printf("%-40s mismatches: %llu of %llu arguments (log), %llu of %llu (exp)\n", "the divisions without the Newton step", h[16], h[13], h[17], h[15]);
+
+    unsigned long long* dc;
+    uint32_t* df;
+    hipMalloc(&dc, 80);
+    hipMemset(dc, 0, 80);
+    hipMalloc(&df, 40);
+    hipMemset(df, 0xff, 40);
+    for (int poison = -1; poison <= 1; poison++) hipLaunchKernelGGL(sweep_cuts, dim3(256 * 16), dim3(256), 0, 0, dc, df, poison);
+    unsigned long long hc[10];
+    uint32_t hf[10];
+    if (hipMemcpy(hc, dc, 80, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(hf, df, 40, hipMemcpyDeviceToHost) != hipSuccess) {
+        printf("sweep_cuts: the device run failed\n");
+        return 1;
+    }
+    const char* cn[10] = {"rt_log", "rt_exp", "rt_sin", "rt_cos", "rt_sincos (sin)", "rt_sincos (cos)", "rt_smoothstep(0, 1/0.4, x)", "rt_smoothstep(-0.01, 1/0.01, x)",
+                          "rt_pow(x, 0.35)", "rt_sincos against rt_sin / rt_cos"};
+    unsigned long long bad = 0;
+    for (int k = 0; k < 10; k++) {
+        printf("cuts: %-34s mismatches against rt_math.h over all 2^32 arguments, three passes: %llu (first 0x%08x)\n", cn[k], hc[k], hf[k]);
+        bad += hc[k];
+    }
+    return bad ? 2 : 0;
 }
