@@ -27,6 +27,7 @@
 #include "rt_kernels.h"
 #include "../../include/rt_cost.h"
 #include "../../include/rt_primary.h"
+#include "../../include/rt_held_back.h"
 #include "../../include/rt_tile_cand.h"
 #include "../../include/rt_aov.h"
 #include "../../include/rt_denoise.h"
@@ -185,6 +186,7 @@ struct RtContext {
     int frameGroupOverride = 0; /* RT_FRAME_GROUP: frames per (tile, frame group) item of fused launches (tuning hook) */
     bool coalesce = true;  /* RT_COALESCE=0: every rt_render_frame launches at once */
     int pending = 0;       /* frames [frame - pending, frame) requested but not launched yet */
+    bool holdBack = false; /* RT_HOLD_BACK=1 (test hook): gpu_idle answers "busy", so every eligible rt_render_frame is held back */
     bool fuseFrames = true; /* rt_render_frames(n): up to fuseCap frames per launch (RT_FUSE_FRAMES=0: one launch per frame) */
     int fuseCap = RT_FUSE_MIN;  /* frames per fused launch right now (see RT_FUSE_MIN) */
     bool fuseCapPinned = false; /* RT_FUSE_CAP */
@@ -580,6 +582,7 @@ int rt_create(int device_id, RtContext** out)
     if (const char* l = getenv("RT_LPT")) ctx->order.lpt = atoi(l) != 0;
     if (const char* t = getenv("RT_TWO_STREAMS")) ctx->twoStreams = atoi(t) != 0;
     if (const char* c = getenv("RT_COALESCE")) ctx->coalesce = atoi(c) != 0;
+    if (const char* hb = getenv("RT_HOLD_BACK")) ctx->holdBack = atoi(hb) != 0; /* test hook */
     if (const char* fg = getenv("RT_FRAME_GROUP")) ctx->frameGroupOverride = atoi(fg);
     if (const char* al = getenv("RT_ALTERNATE")) ctx->order.alternate = ctx->alternateWanted = atoi(al) != 0;
     ctx->order.set_two_streams(ctx->twoStreams && ctx->sideStream);
@@ -1618,6 +1621,7 @@ static int check_renderable(RtContext* ctx)
 
 static bool gpu_idle(RtContext* ctx)
 {
+    if (ctx->holdBack) return false;
     if (hipStreamQuery(ctx->stream) != hipSuccess) return false;
     if (ctx->sideStream && ctx->order.sideDirty && hipStreamQuery(ctx->sideStream) != hipSuccess) return false;
     return true;
@@ -1878,6 +1882,7 @@ struct DevScratch {
 };
 
 int rt_debug_fused_frames_cap(const RtContext* ctx) { return ctx ? ctx->fuseCap : RT_ERR_INVALID_ARG; }
+int rt_debug_pending_frames(const RtContext* ctx) { return ctx ? ctx->pending : RT_ERR_INVALID_ARG; }
 int rt_debug_primary_table(const RtContext* ctx) { return ctx ? ctx->lastPrimaryOn : RT_ERR_INVALID_ARG; }
 int rt_debug_tile_cand(const RtContext* ctx) { return ctx ? ctx->lastTileCand : RT_ERR_INVALID_ARG; }
 int rt_debug_tile_tri(const RtContext* ctx) { return ctx ? ctx->lastTileTri : RT_ERR_INVALID_ARG; }
@@ -3649,6 +3654,14 @@ int rt_gather_rccl(RtContext* ctx, void* nccl_comm, int root, int use_accumulate
     }
     if (badDst) return fail(ctx, RT_ERR_INVALID_ARG, "rt_gather_rccl: bytes %zu != H*W*16 = %zu (the tiles were received and dropped)", bytes, (size_t)W * H * 16);
     return RT_OK;
+}
+
+int rt_debug_multi_pending_frames(const RtMulti* m)
+{
+    if (!m) return RT_ERR_INVALID_ARG;
+    int most = 0;
+    for (const RtContext* c : m->ctx) most = c->pending > most ? c->pending : most;
+    return most;
 }
 
 int rt_multi_get_counters(RtMulti* m, RtCounters* out)

@@ -31,6 +31,8 @@ ABI_SYMBOLS = [
 ]
 # every symbol include/rt_cost.h declares (kept apart: ABI_SYMBOLS mirrors rt_abi.h alone)
 COST_SYMBOLS = ["rt_render_cost"]
+# include/rt_held_back.h (test hooks; its third declaration restates rt_multi_context of rt_abi.h)
+HELD_BACK_SYMBOLS = ["rt_debug_pending_frames", "rt_debug_multi_pending_frames"]
 # include/rt_primary.h
 PRIMARY_SYMBOLS = ["rt_debug_primary_table"]
 # include/rt_tile_cand.h
@@ -89,6 +91,8 @@ class HipApi(abi.CApi):
         "debug_layout": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_char_p, C.c_void_p]),
         "debug_layout_free": (None, [C.c_void_p]),
         "debug_fused_frames_cap": (C.c_int, [C.c_void_p]),
+        "debug_pending_frames": (C.c_int, [C.c_void_p]),
+        "debug_multi_pending_frames": (C.c_int, [C.c_void_p]),
         "debug_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
         "debug_math_eval": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
         "debug_phase_profile": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
@@ -469,6 +473,10 @@ class MultiTracer:
     def last_gather_ms(self):
         return float(self.api.multi_last_gather_ms(self.h))
 
+    def pending_frames(self):
+        """rt_debug_multi_pending_frames (test hook): the most frames any context holds back right now."""
+        return self.api.debug_multi_pending_frames(self.h)
+
     def counters(self):
         c = abi.RtCounters()
         self._check(self.api.multi_get_counters(self.h, C.byref(c)))
@@ -551,6 +559,10 @@ class HipTracer(abi.Tracer):
 
     def fused_frames_cap(self):
         return self.api.debug_fused_frames_cap(self.h)
+
+    def pending_frames(self):
+        """rt_debug_pending_frames (test hook): frames counted by render_frame but not launched yet."""
+        return self.api.debug_pending_frames(self.h)
 
     def primary_table(self):
         """rt_debug_primary_table: 1 / 0 = the last trace launch carried its table of ray-origin constants switched on / off, -1 = no launch yet"""

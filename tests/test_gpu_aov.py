@@ -21,6 +21,8 @@ import sys
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -471,7 +473,7 @@ def test_device_variant_into_a_torch_tensor(pkg, api):
 
 
 # ---------------------------------------------------------------- 9. no visible state change
-def test_aov_calls_leave_no_trace(pkg, api, orc):
+def test_aov_calls_leave_no_trace(pkg, api, orc, forced=False):
     cfg, w, h, seed = (3, {}), 96, 54, 5
     snaps, seen = [], {}
     for with_aov in (True, False):
@@ -483,9 +485,14 @@ def test_aov_calls_leave_no_trace(pkg, api, orc):
 
         def probe(tag):
             if with_aov:
+                if tag.startswith("after held"):    # (rt_get_counters below launches held frames too: this pass comes first)
+                    held_at(tr, "test_gpu_aov: rt_render_aov after held-back frames", forced)
+                    met = tr.render_aov(tr.frame())
                 before = (tr.frame(), tr.counters())
                 a = tr.render_aov(tr.frame())  # the frame the context renders next
                 assert_records_equal(a, tr.render_aov(tr.frame()), tag)
+                if tag.startswith("after held"):
+                    assert_records_equal(a, met, tag)
                 tr.render_aov_to_device(1, t.ptr, t.nbytes)
                 first = tr.render_aov(1)
                 assert_records_equal(first, seen.setdefault(1, first), tag)
@@ -514,6 +521,12 @@ def test_aov_calls_leave_no_trace(pkg, api, orc):
     acc_o = ot.read_accumulated()
     ot.close()
     assert acc_a.view(np.uint32).tobytes() == acc_o.view(np.uint32).tobytes(), "accumulated image != oracle"
+
+
+def test_aov_calls_leave_no_trace_with_frames_held_back_for_certain(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: frames 19-21 ARE held back when the AOV pass comes (asserted right before it)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_aov_calls_leave_no_trace(pkg, api, orc, forced=True)
 
 
 # ---------------------------------------------------------------- 10. errors, and the pass's own watchdog word

@@ -15,6 +15,8 @@ import os
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KEYS = ("segments", "innerSteps", "leafSteps", "triTests")
@@ -238,7 +240,7 @@ def test_image_sum_equals_the_stats_frame(pkg, api, cfg):
 
 
 # ---------------------------------------------------------------- 4. no side effects
-def test_cost_calls_leave_no_trace(pkg, api, orc):
+def test_cost_calls_leave_no_trace(pkg, api, orc, forced=False):
     cfg, w, h, seed = (3, {}), 96, 54, 5
     snaps = []
     costs = {}
@@ -249,6 +251,8 @@ def test_cost_calls_leave_no_trace(pkg, api, orc):
 
         def probe(tag):
             if with_cost:
+                if tag.startswith("after held"):
+                    held_at(tr, "test_gpu_cost_view: rt_render_cost after held-back frames", forced)
                 a = tr.render_cost(tr.frame())  # the frame the context renders next
                 assert np.array_equal(a, tr.render_cost(tr.frame())), tag  # the same frame twice: the same work
                 costs[tr.frame()] = a
@@ -275,6 +279,12 @@ def test_cost_calls_leave_no_trace(pkg, api, orc):
     acc_o = ot.read_accumulated()
     ot.close()
     assert acc_a.view(np.uint32).tobytes() == acc_o.view(np.uint32).tobytes(), "accumulated image != oracle"
+
+
+def test_cost_calls_leave_no_trace_with_frames_held_back_for_certain(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: frames 19-21 ARE held back when the cost pass comes (asserted right before it)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_cost_calls_leave_no_trace(pkg, api, orc, forced=True)
 
 
 # ---------------------------------------------------------------- 5. layout and partition independence

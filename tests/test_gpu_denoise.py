@@ -19,6 +19,8 @@ import sys
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 import denoise_reference as ref
 import test_gpu_aov as ga
 
@@ -229,7 +231,7 @@ def test_exact_properties_on_synthetic_buffers(pkg, api):
 
 
 # ---------------------------------------------------------------- 9. no visible state change
-def test_denoise_calls_leave_no_trace(pkg, api):
+def test_denoise_calls_leave_no_trace(pkg, api, forced=False):
     cfg, w, h, seed = (3, {}), 96, 54, 5
     snaps = []
     for with_call in (True, False):
@@ -242,9 +244,14 @@ def test_denoise_calls_leave_no_trace(pkg, api):
 
         def probe(tag):
             if with_call:
+                if tag.startswith("after held"):    # (rt_get_counters below launches held frames too: this filter comes first)
+                    held_at(tr, "test_gpu_denoise: rt_denoise after held-back frames", forced)
+                    met = tr.denoise(api.denoise_params(scale=1.0 / max(tr.frame() - 1, 1)), aov_frame=tr.frame())
                 before = (tr.frame(), tr.counters())
                 p = api.denoise_params(scale=1.0 / max(tr.frame() - 1, 1))
                 a = tr.denoise(p, aov_frame=tr.frame())
+                if tag.startswith("after held"):
+                    assert met.tobytes() == a.tobytes(), tag
                 tr.denoise_to_device(t.ptr, t.nbytes, p, aov_frame=tr.frame())
                 tr.render_aov_to_device(tr.frame(), rec.ptr, rec.nbytes)
                 tr.denoise_buffers(w, h, t.ptr, rec.ptr, t2.ptr, p)
@@ -273,6 +280,12 @@ def test_denoise_calls_leave_no_trace(pkg, api):
     for k in range(4):
         assert a[k].tobytes() == b[k].tobytes(), k
     assert a[4] == b[4] == 25 and a[5] == b[5]
+
+
+def test_denoise_calls_leave_no_trace_with_frames_held_back_for_certain(pkg, api, monkeypatch):
+    """The same with RT_HOLD_BACK=1: frames 19-21 ARE held back when the filter comes (asserted right before it)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_denoise_calls_leave_no_trace(pkg, api, forced=True)
 
 
 # ---------------------------------------------------------------- 10. errors

@@ -35,6 +35,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import deep_trees as dt  # noqa: E402
 import nee_reference as nr  # noqa: E402
 import radiance_reference as rr  # noqa: E402
+from flush_table import held_at  # noqa: E402
 import test_gpu_query as tq  # noqa: E402  (scenes, DevBuf, snapshot: shared, never written)
 import test_gpu_radiance as rg  # noqa: E402  (params_of, assert_rgb)
 
@@ -349,7 +350,7 @@ def test_same_expectation_as_plain_radiance(pkg, api, orc, name):
 
 
 # ---------------------------------------------------------------- 5. the side-pass manners
-def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc):
+def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc, forced=False):
     """A pass enqueued right behind rt_update_spheres sees the emitter it made (and the table rebuilt for it); passes between
     rt_render_frame calls that are held back leave the image what the same frames give without any pass."""
     abi = pkg.abi
@@ -374,6 +375,7 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
             for _ in range(3):  # rt_render_frame may hold these back
                 mgr.RenderFrame()
                 if with_passes:
+                    held_at(tr, "test_gpu_nee: rt_nee_trace_buffers behind rt_render_frame", forced)
                     tr.radiance_trace_nee_buffers(d_rays.ptr, n, d_out.ptr)
             if with_passes:
                 tr.synchronize()
@@ -406,6 +408,12 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
         finally:
             tr.close()
     assert images[0] == images[1]
+
+
+def test_buffer_form_runs_behind_frames_that_are_held_back_for_certain(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: every rt_render_frame of the burst IS held back (asserted right before each pass)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc, forced=True)
 
 
 def test_updates_that_turn_a_models_emission_on_and_off_are_seen(pkg, api, orc):

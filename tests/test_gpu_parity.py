@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 from conftest import render
 
 pytestmark = pytest.mark.gpu
@@ -450,7 +452,7 @@ def test_multi_device_entry_equals_single_context(pkg, api, n):
     assert ca["segments"] == cb["segments"] and cb["pixelFrames"] == 3 * 120 * 100
 
 
-def test_multi_device_upload_paths_and_held_frames(pkg, api, monkeypatch):
+def test_multi_device_upload_paths_and_held_frames(pkg, api, monkeypatch, forced=False):
     """rt_multi_upload_scene prepares the scene once and fills contexts 1.. with device-to-device copies of context 0's
     arrays (RT_MULTI_PEER_UPLOAD=0: every context from the host): same image either way.  And frames a context holds back
     (rt_render_frame calls that arrive while the GPU is busy) are launched on every device by the gather itself."""
@@ -463,6 +465,7 @@ def test_multi_device_upload_paths_and_held_frames(pkg, api, monkeypatch):
         mgr.OnEnable(renderSeed=9)
         for _ in range(7):          # back-to-back single-frame requests: some are held back in every context
             mgr.RenderFrame()
+        held_at(multi, "test_gpu_parity: rt_gather_accumulated behind seven rt_multi_render_frame calls", forced)
         images.append(multi.read_accumulated())   # no synchronise before: the gather has to flush all three devices
         assert multi.last_gather_ms() > 0
         multi.close()
@@ -472,6 +475,12 @@ def test_multi_device_upload_paths_and_held_frames(pkg, api, monkeypatch):
     a, _ = render(pkg, api, single, 4, 96, 56, 7, seed=9, scene_kw={"subdivisions": 3})
     single.close()
     assert bits_equal(images[0], a)
+
+
+def test_multi_device_gather_launches_frames_that_are_held_back_for_certain(pkg, api, monkeypatch):
+    """The same with RT_HOLD_BACK=1: all seven frames ARE held back in every context when the gather comes (asserted)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_multi_device_upload_paths_and_held_frames(pkg, api, monkeypatch, forced=True)
 
 
 def test_gather_into_device_memory_equals_the_host_gather(pkg, api):
@@ -504,7 +513,7 @@ def test_gather_into_device_memory_equals_the_host_gather(pkg, api):
         multi.close()
 
 
-def test_direct_target_readers_see_every_requested_frame(pkg, api):
+def test_direct_target_readers_see_every_requested_frame(pkg, api, forced=False):
     """A host that reads the render targets itself after its own device synchronise: rt_get_render_targets launches the
     frames rt_render_frame still held back (they are launched lazily), so that synchronise covers them."""
     import ctypes as C
@@ -514,6 +523,7 @@ def test_direct_target_readers_see_every_requested_frame(pkg, api):
     mgr.OnEnable(renderSeed=2)
     for _ in range(12):
         mgr.RenderFrame()
+    held_at(tr, "test_gpu_parity: rt_get_render_targets behind twelve rt_render_frame calls", forced)
     f, a = tr.render_targets()          # flushes
     hip = C.CDLL("libamdhip64.so")
     assert hip.hipDeviceSynchronize() == 0
@@ -522,6 +532,12 @@ def test_direct_target_readers_see_every_requested_frame(pkg, api):
     assert np.all(host[..., 3] == 12)
     assert bits_equal(host, tr.read_accumulated())
     tr.close()
+
+
+def test_direct_target_readers_see_frames_that_are_held_back_for_certain(pkg, api, monkeypatch):
+    """The same with RT_HOLD_BACK=1: all twelve frames ARE held back when rt_get_render_targets comes (asserted)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_direct_target_readers_see_every_requested_frame(pkg, api, forced=True)
 
 
 # ------------------------------------------------------------------ scheduling must not change results
@@ -572,7 +588,7 @@ def test_frame_group_size_does_not_change_a_bit(pkg, api, monkeypatch):
 
 
 @pytest.mark.parametrize("alternate", ["0", "1"])
-def test_alternating_fused_launches_add_frames_in_frame_order(pkg, api, orc, alternate, monkeypatch):
+def test_alternating_fused_launches_add_frames_in_frame_order(pkg, api, orc, alternate, monkeypatch, forced=False):
     """Round 4: consecutive fused launches run on the context's two streams in turn (own staging slab each), the re-sort of the tile
     order runs without joining the streams, and only the accumulate kernels are chained.  A long burst of back-to-back
     rt_render_frame calls (1 + 16 + 16 + 16 + ... frames, sorts due after 1, 2, 4, 8, 16, 32 frames), interleaved with single frames
@@ -589,14 +605,26 @@ def test_alternating_fused_launches_add_frames_in_frame_order(pkg, api, orc, alt
                 for _ in range(burst):
                     tr.render_frame()          # back to back: held back and fused by the library
                 if burst == 1 and hasattr(tr, "synchronize"):
+                    held_at(tr, "test_gpu_parity: rt_synchronize behind a burst of 38 rt_render_frame calls", forced)
                     tr.synchronize()           # the next burst starts from an idle GPU
             mgr.numAccumulatedFrames += 37 + 1 + 5 + 18
+            if lib is api:
+                held_at(tr, "test_gpu_parity: rt_read_accumulated behind a burst of 23 rt_render_frame calls", forced)
             imgs.append((tr.read_accumulated().copy(), tr.read_frame().copy(), tr.frame()))
             tr.close()
         (a, fa, na), (b, fb, nb) = imgs
         assert na == nb == 62
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), (cfg, alternate, int(np.any(a.view(np.uint32) != b.view(np.uint32), axis=-1).sum()))
         assert np.array_equal(fa.view(np.uint32), fb.view(np.uint32)), (cfg, alternate)
+
+
+@pytest.mark.parametrize("alternate", ["0", "1"])
+def test_alternating_fused_launches_of_frames_that_are_held_back_for_certain(pkg, api, orc, alternate, monkeypatch):
+    """The same with RT_HOLD_BACK=1: every frame of a burst is held back until sixteen have gathered (RT_FUSE_CAP pins the sixteen, so
+    that 38 and 23 frames leave 6 and 7 behind: asserted where the synchronise and the read come)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    monkeypatch.setenv("RT_FUSE_CAP", "16")
+    test_alternating_fused_launches_add_frames_in_frame_order(pkg, api, orc, alternate, monkeypatch, forced=True)
 
 
 @pytest.mark.parametrize("alternate", ["0", "1"])
@@ -630,7 +658,7 @@ def test_a_single_frame_behind_a_fused_launch_waits_for_its_accumulate_kernel(pk
 
 
 @pytest.mark.parametrize("coalesce", ["0", "1"])
-def test_held_back_frames_see_the_state_they_were_requested_with(pkg, api, orc, coalesce, monkeypatch):
+def test_held_back_frames_see_the_state_they_were_requested_with(pkg, api, orc, coalesce, monkeypatch, forced=False):
     """rt_render_frame holds frames requested while the GPU is busy back and launches them fused.  Every call that
     changes what they depend on must flush them first: here the bounce limit, a model matrix and the sphere set
     change between bursts of back-to-back frames; the oracle renders the same sequence frame by frame."""
@@ -647,6 +675,8 @@ def test_held_back_frames_see_the_state_they_were_requested_with(pkg, api, orc, 
             for _ in range(7):
                 mgr.RenderFrame()          # InitFrame (UpdateModels + SetShaderParams) + dispatch, back to back
             frames_seen.append(tr.frame())
+            if lib is api:      # the next call into the library is the one that changes the state (or, after the last burst, rt_flush)
+                held_at(tr, f"test_gpu_parity: the state change behind burst {burst} of seven rt_render_frame calls (RT_COALESCE={coalesce})", forced)
             if burst == 0:
                 mgr.maxBounceCount = 3
             elif burst == 1:
@@ -662,6 +692,12 @@ def test_held_back_frames_see_the_state_they_were_requested_with(pkg, api, orc, 
         tr.close()
     (a, fa, sa), (b, fb, sb) = out
     assert bits_equal(a, b) and bits_equal(fa, fb) and sa == sb
+
+
+def test_frames_that_are_held_back_for_certain_see_the_state_they_were_requested_with(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: the seven frames of every burst ARE held back when the change comes (asserted)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_held_back_frames_see_the_state_they_were_requested_with(pkg, api, orc, "1", monkeypatch, forced=True)
 
 
 @pytest.mark.parametrize("two", ["0", "1"])

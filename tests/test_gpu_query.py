@@ -22,6 +22,8 @@ import sys
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
@@ -385,7 +387,7 @@ def test_a_grid_of_two_waves_goes_round_more_than_once(pkg, api, orc, name, monk
 
 
 # ---------------------------------------------------------------- 5. forms
-def test_buffer_forms_see_updates_and_run_behind_held_back_frames(pkg, api, orc):
+def test_buffer_forms_see_updates_and_run_behind_held_back_frames(pkg, api, orc, forced=False):
     """A query enqueued right behind rt_update_spheres sees the moved sphere; queries between rt_render_frame calls that are held back
     leave the image what the same frames give without any query."""
     abi = pkg.abi
@@ -410,6 +412,7 @@ def test_buffer_forms_see_updates_and_run_behind_held_back_frames(pkg, api, orc)
             for _ in range(3):  # rt_render_frame may hold these back
                 mgr.RenderFrame()
                 if with_queries:
+                    held_at(tr, "test_gpu_query: rt_query_closest_buffers behind rt_render_frame", forced)
                     tr.query_closest_buffers(d_rays.ptr, 70, d_hits.ptr)
                     tr.query_occluded_buffers(d_rays.ptr, 70, d_occ.ptr)
             if with_queries:
@@ -431,6 +434,12 @@ def test_buffer_forms_see_updates_and_run_behind_held_back_frames(pkg, api, orc)
         finally:
             tr.close()
     assert images[0] == images[1]
+
+
+def test_buffer_forms_run_behind_frames_that_are_held_back_for_certain(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: every rt_render_frame of the burst IS held back (asserted right before each pass)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_buffer_forms_see_updates_and_run_behind_held_back_frames(pkg, api, orc, forced=True)
 
 
 _TORCH_CHILD = r"""

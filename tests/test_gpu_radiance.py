@@ -22,6 +22,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import radiance_reference as rr  # noqa: E402
+from flush_table import held_at  # noqa: E402
 import test_gpu_query as tq  # noqa: E402  (scenes, the ray mix, DevBuf and the cached oracle records: shared, never written)
 
 pytestmark = pytest.mark.gpu
@@ -228,7 +229,7 @@ def test_a_grid_of_two_waves_draws_its_blocks_from_the_counter(pkg, api, orc, mo
 
 
 # ---------------------------------------------------------------- 6. the buffer form
-def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc):
+def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc, forced=False):
     """A pass enqueued right behind rt_update_spheres and rt_set_params sees both; passes between rt_render_frame calls that are held
     back leave the image what the same frames give without any pass."""
     abi = pkg.abi
@@ -252,6 +253,7 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
             for _ in range(3):  # rt_render_frame may hold these back
                 mgr.RenderFrame()
                 if with_passes:
+                    held_at(tr, "test_gpu_radiance: rt_radiance_trace_buffers behind rt_render_frame", forced)
                     tr.radiance_trace_buffers(d_rays.ptr, 70, d_out.ptr)
             if with_passes:
                 tr.synchronize()
@@ -278,6 +280,12 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
         finally:
             tr.close()
     assert images[0] == images[1]
+
+
+def test_buffer_form_runs_behind_frames_that_are_held_back_for_certain(pkg, api, orc, monkeypatch):
+    """The same with RT_HOLD_BACK=1: every rt_render_frame of the burst IS held back (asserted right before each pass)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc, forced=True)
 
 
 _TORCH_CHILD = r"""

@@ -19,6 +19,8 @@ import sys
 import numpy as np
 import pytest
 
+from flush_table import held_at
+
 import motion_reference as mref
 import reproject_reference as rp
 import test_gpu_aov as ga
@@ -274,7 +276,7 @@ def test_reset_empties_the_moments_and_rebases(pkg, api, orc):
 
 
 # ---------------------------------------------------------------- 4. no visible state change
-def test_variance_calls_leave_no_trace(pkg, api):
+def test_variance_calls_leave_no_trace(pkg, api, forced=False):
     cfg, w, h, seed = (3, {}), 96, 54, 5
     snaps = []
     for with_call in (True, False):
@@ -288,6 +290,9 @@ def test_variance_calls_leave_no_trace(pkg, api):
 
         def probe(tag):
             if with_call:
+                if tag.startswith("after held"):    # (rt_get_counters below launches held frames too: this filter, which changes no state, comes first)
+                    held_at(tr, "test_gpu_variance: rt_denoise_variance after held-back frames", forced)
+                    tr.denoise_variance(api.variance_denoise_params(), aov_frame=tr.frame())
                 before = (tr.frame(), tr.counters())
                 p = api.variance_denoise_params()
                 tr.variance_update()
@@ -324,6 +329,12 @@ def test_variance_calls_leave_no_trace(pkg, api):
     for k in range(4):
         assert a[k].tobytes() == b[k].tobytes(), k
     assert a[4] == b[4] == 25 and a[5] == b[5]
+
+
+def test_variance_calls_leave_no_trace_with_frames_held_back_for_certain(pkg, api, monkeypatch):
+    """The same with RT_HOLD_BACK=1: frames 19-21 ARE held back when the variance-guided filter comes (asserted right before it)."""
+    monkeypatch.setenv("RT_HOLD_BACK", "1")
+    test_variance_calls_leave_no_trace(pkg, api, forced=True)
 
 
 # ---------------------------------------------------------------- 5. errors
