@@ -1,0 +1,384 @@
+"""Non-finite and extreme scene values on every kernel: the catalogue of tests/hazard_scenes.py on the GPU.  tests/test_hazards.py has
+pinned the oracle to the reference text on every case on the CPU; here the device renders each case and must equal the oracle.
+
+Whole frames (every case, every base scene it applies to; the shipped and the STATS instantiation): both images after two single frames
+and after a fused launch of three, under the NaN-position rule; segments and pixelFrames, in the STATS build all seven exact counters;
+filter_violations == 0; the three rt_debug_* calls after either part say what the catalogue reasons (`tables`: (1, 1, 1) or (0, 0, 0) on
+flat-tables, (0, 0, 0) on every other base).  The watchdog word: a context whose watchdog fired fails every pixel read and
+rt_get_counters with RT_ERR_HIP (the wrapper raises), so the reads of each case succeeding IS that assertion.  What no debug call exposes — a
+per-tile table that keeps every bit, the root filter dropped for one model — is held by the image, the exact counters and the audit.
+
+The contexts are shared by the cases of this module (a case starts with rt_resize, rt_upload_scene, rt_set_params and
+rt_reset_accumulation): a table left over from the previous case's key would show as a wrong pixel.
+
+Side passes (hazard_scenes.SIDE_CASES on SIDE_BASES): rt_render_aov, rt_query_closest / rt_query_occluded / rt_debug_intersect,
+rt_radiance_trace and (NEE_CASES) rt_nee_trace against the oracle's functions.  Floats are compared bit for bit, except that where
+the expected value is a NaN the device's must be one too (a NaN's sign and payload are not part of the contract)."""
+import ctypes as C
+import time
+
+import numpy as np
+import pytest
+
+import hazard_scenes as hz
+import nee_reference as nr
+import radiance_reference as rr
+from test_gpu_tile_tri import KEYS, environment
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+F3 = C.c_float * 3
+POOLED, SINGLE = {"RT_POOL_MIN_ITEMS": "0"}, {"RT_POOL": "0"}
+ALL = [None] + hz.CASES
+IDS = ["unplanted"] + [c.name for c in hz.CASES]
+
+
+@pytest.fixture(scope="module")
+def contexts(api):
+    """(name, environment, tracer, stats?) — made once: the default schedule, and for flat-general pooled workgroups / single waves"""
+    made = []
+    for name, env in (("default", {}), ("pooled", POOLED), ("single waves", SINGLE)):
+        for stats in (False, True):
+            with environment(env) if env else _nothing():
+                tr = api.create_tracer(0)
+            tr.enable_stats(stats)
+            made.append((name, env, tr, stats))
+    yield made
+    for _, _, tr, _ in made:
+        tr.close()
+
+
+class _nothing:
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        return False
+
+
+def _tables(tr):
+    return (tr.primary_table(), tr.tile_cand(), tr.tile_tri())
+
+
+def _drive_watched(rig, tr):
+    """hz.drive, and what the three debug calls say after the single frames and after the fused launch"""
+    rig.upload(tr)
+    for i in range(2):
+        tr.set_params(rig.params(i))
+        tr.render_frame()
+    single = (tr.read_accumulated().copy(), tr.read_frame().copy())
+    after_single = _tables(tr)
+    tr.set_params(rig.params(2))
+    tr.render_frames(3)
+    fused = (tr.read_accumulated().copy(), tr.read_frame().copy())
+    return single, fused, tr.counters(), (after_single, _tables(tr))
+
+
+def _check(pkg, api, orc, case, base, name, env, tr, stats):
+    what = f"{case.name if case else 'unplanted'} on {base} ({name}, {'STATS' if stats else 'shipped'})"
+    want = hz.expected(pkg, orc, base, case)
+    with environment(env) if env else _nothing():
+        tr.reset_counters()
+        single, fused, c, debug = _drive_watched(hz.Rig(pkg, api, base, case), tr)
+        viol = tr.phase_profile()["filter_violations"][0] if stats else 0
+    print(f"{what}: segments {c['segments']} (oracle {want[2]['segments']}), tables {debug}, NaN share {hz.nan_share(want[1][0]):.2f}")
+    for part, g, o in (("two single frames", single, want[0]), ("then 3 fused frames", fused, want[1])):
+        hz.assert_image(g[0], o[0], f"{what}, {part}: AccumulatedRender != oracle")
+        hz.assert_image(g[1], o[1], f"{what}, {part}: FrameRender != oracle")
+    assert (c["segments"], c["pixelFrames"]) == (want[2]["segments"], want[2]["pixelFrames"]), (what, c, want[2])
+    if stats:
+        assert [c[k] for k in KEYS] == [want[2][k] for k in KEYS], (what, c, want[2])
+        assert viol == 0, what
+    on = base == "flat-tables" and (case is None or case.tables == "on")
+    assert debug == (((1, 1, 1),) * 2 if on else ((0, 0, 0),) * 2), f"{what}: rt_debug_primary_table / _tile_cand / _tile_tri = {debug}"
+
+
+@pytest.mark.parametrize("case", ALL, ids=IDS)
+def test_every_case_on_every_base_equals_the_oracle(pkg, api, orc, contexts, case):
+    bases = [b for b in hz.BASES if case is None or case.applies(b)]
+    for base in bases:
+        hz.expected(pkg, orc, base, case)   # (the oracle's renders, on the CPU: not part of the time printed below)
+    t0 = time.perf_counter()
+    for base in bases:
+        for name, env, tr, stats in contexts:
+            if name == "default":
+                _check(pkg, api, orc, case, base, name, env, tr, stats)
+    print(f"{len(bases)} bases x 2 instantiations x 5 frames: {time.perf_counter() - t0:.2f} s on the device side")
+
+
+@pytest.mark.parametrize("case", ALL, ids=IDS)
+def test_flat_general_as_pooled_workgroups_and_as_single_waves(pkg, api, orc, contexts, case):
+    assert case is None or case.applies("flat-general")
+    for name, env, tr, stats in contexts:
+        if name != "default":
+            _check(pkg, api, orc, case, "flat-general", name, env, tr, stats)
+
+
+# ---- the side passes ------------------------------------------------------------------------------------------------------------------
+
+def _same(got, want):
+    """bit for bit; where the expected float is a NaN, a NaN"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    if want.dtype != np.float32:
+        return got == want
+    nan = np.isnan(want)
+    return np.where(nan, np.isnan(got), got.view(np.uint32) == want.view(np.uint32))
+
+
+def _assert_fields(got, want, fields, what):
+    for f in fields:
+        ok = _same(got[f], want[f])
+        bad = np.argwhere(~ok.reshape(len(got), -1).all(axis=1))
+        assert not len(bad), f"{what}: field {f}: {len(bad)} records differ; first {int(bad[0][0])}: got {got[int(bad[0][0])]}, want {want[int(bad[0][0])]}"
+
+
+def _oracle_hits(orc, ot, origins, dirs):
+    """oracle_ray_collision per ray: (n, 10) float32 = didHit, isBackface, dst, normal, pos, material flag"""
+    out = np.zeros((len(origins), 10), dtype=F)
+    o10 = (C.c_float * 10)()
+    for i in range(len(origins)):
+        orc.ray_collision(ot.h, F3(*origins[i]), F3(*dirs[i]), o10)
+        out[i] = o10[:]
+    return out
+
+
+def _hit_records(abi, dtype, hits10):
+    """the float fields and the hit word of RtRayHit / RtPixelAov records from oracle_ray_collision's answers (a miss: dst alone)"""
+    want = np.zeros(len(hits10), dtype=dtype)
+    hit = hits10[:, 0] != 0
+    want["dst"] = hits10[:, 2]
+    want["normal"][hit], want["pos"][hit] = hits10[hit, 3:6], hits10[hit, 6:9]
+    glass = hits10[:, 9].astype(np.int64) == abi.MATERIAL_GLASS
+    want["hit"][hit] = (np.where(glass, 2, 1) | np.where(hits10[:, 1] != 0, abi.AOV_HIT_BACKFACE, 0))[hit]
+    return want, hit
+
+
+def _side_setup(pkg, api, orc, contexts, base, case):
+    rig = hz.Rig(pkg, api, base, case)
+    tr = next(t for name, _, t, stats in contexts if name == "default" and not stats)
+    rig.upload(tr)
+    ot = orc.create_tracer(1)
+    hz.Rig(pkg, orc, base, case).upload(ot)
+    return rig, tr, ot
+
+
+SIDE = [hz.BY_NAME[n] for n in hz.SIDE_CASES]
+
+
+@pytest.mark.parametrize("case", SIDE, ids=hz.SIDE_CASES)
+def test_aov_records_of_a_hazard_scene(pkg, api, orc, contexts, case):
+    """rt_render_aov, frame 2: every field of every pixel.  dst / normal / pos / hit from oracle_ray_collision on the camera rays of
+    tests/test_gpu_aov.py; albedo from oracle_material_colour (a hit; the material is the one of the record's own object, whose flag
+    must be the oracle's hit's) or oracle_environment_light (a miss); emission = emissionCol * emissionStrength; object and
+    triangle: -1 exactly on a miss, a sphere's triangle -1, a model's inside the model's range."""
+    import test_gpu_aov as ta
+    abi = pkg.abi
+    for base in hz.SIDE_BASES:
+        if not case.applies(base):
+            continue
+        rig, tr, ot = _side_setup(pkg, api, orc, contexts, base, case)
+        try:
+            p = rig.params(1)
+            aov = tr.render_aov(rig.frame0 + 1).reshape(-1)
+            o, d = ta.camera_rays(orc, p, rig.w, rig.h, rig.frame0 + 1)
+            o, d = o.reshape(-1, 3), d.reshape(-1, 3)
+            hits10 = _oracle_hits(orc, ot, o, d)
+            want, hit = _hit_records(abi, abi.AOV_DTYPE, hits10)
+            what = f"{case.name} on {base}: rt_render_aov"
+            assert np.array_equal(aov["object"] >= 0, hit), what + ": object >= 0 exactly where the oracle hits"
+            o3 = F3()
+            for i in range(len(aov)):
+                if hit[i]:
+                    obj = int(aov["object"][i])
+                    mat = rig.materials[obj:obj + 1].copy()
+                    assert int(mat["flag"][0]) == int(hits10[i, 9]), (what, i, obj)
+                    orc.material_colour(mat.ctypes.data, F3(*hits10[i, 6:9]), F3(*hits10[i, 3:6]), 0, o3)
+                    want["albedo"][i] = o3[:]
+                    with np.errstate(all="ignore"):
+                        want["emission"][i] = mat["emissionCol"][0][:3] * mat["emissionStrength"][0]
+                elif p.useSky:
+                    orc.environment_light(C.byref(p), F3(*d[i]), o3)
+                    want["albedo"][i] = o3[:]
+            _assert_fields(aov, want, ("dst", "normal", "pos", "hit", "albedo", "emission"), what)
+            model = aov["object"] >= rig.n_spheres
+            assert ((aov["triangle"] >= 0) == model).all(), what
+            for i in np.argwhere(model).ravel():
+                mi = int(aov["object"][i]) - rig.n_spheres
+                off = int(rig.models["triOffset"][mi])
+                assert off <= int(aov["triangle"][i]) < off + int(rig.tri_count[mi]), (what, i)
+            print(f"{what}: {int(hit.sum())} of {len(hit)} pixels hit, {int(np.isnan(hits10).any(axis=1).sum())} records with a NaN")
+        finally:
+            ot.close()
+
+
+@pytest.mark.parametrize("case", SIDE, ids=hz.SIDE_CASES)
+def test_ray_queries_into_a_hazard_scene(pkg, api, orc, contexts, case):
+    """one ray per pixel centre: rt_query_closest and rt_debug_intersect against oracle_ray_collision; rt_query_occluded at tmax = +inf
+    (any hit), at the ray's own hit distance d (the comparison is strict: 0) and one ulp above it (1 where there is a hit)"""
+    abi = pkg.abi
+    for base in hz.SIDE_BASES:
+        if not case.applies(base):
+            continue
+        rig, tr, ot = _side_setup(pkg, api, orc, contexts, base, case)
+        try:
+            o, d = hz.pixel_centre_rays(rig)
+            o, d = o.reshape(-1, 3), d.reshape(-1, 3)
+            hits10 = _oracle_hits(orc, ot, o, d)
+            want, hit = _hit_records(abi, abi.RAYHIT_DTYPE, hits10)
+            what = f"{case.name} on {base}"
+            got = tr.query_closest(abi.make_rays(o, d))
+            assert np.array_equal(got["object"] >= 0, hit), what + ": rt_query_closest: object >= 0 exactly where the oracle hits"
+            _assert_fields(got, want, ("dst", "normal", "pos", "hit"), what + ": rt_query_closest")
+            dbg = tr.debug_intersect(o, d)
+            ok = _same(dbg, hits10)
+            ok[~hit, 3:] = True   # (a miss: didHit, isBackface and dst are the contract)
+            assert ok.all(), f"{what}: rt_debug_intersect: {int((~ok.all(axis=1)).sum())} rays differ from oracle_ray_collision"
+            dst = hits10[:, 2]
+            with np.errstate(all="ignore"):
+                for name, tmax in (("+inf", np.full(len(o), np.inf, dtype=F)), ("d", dst), ("one ulp above d", np.nextafter(dst, F(np.inf)))):
+                    occ = tr.query_occluded(abi.make_rays(o, d, tmax))
+                    expect = (hit & (dst < tmax)).astype(np.uint32)
+                    assert np.array_equal(occ, expect), f"{what}: rt_query_occluded at tmax = {name}: {int((occ != expect).sum())} rays differ"
+            print(f"{what}: {int(hit.sum())} of {len(hit)} rays hit")
+        finally:
+            ot.close()
+
+
+@pytest.mark.parametrize("case", SIDE, ids=hz.SIDE_CASES)
+def test_radiance_of_camera_rays_into_a_hazard_scene(pkg, api, orc, contexts, case):
+    """rt_radiance_trace of (camera ray 0 of frame 2, the generator state behind its two draws), one ray per pixel, at one ray per
+    pixel in the parameters: oracle_trace_pixel of that frame (x / 1 is x)"""
+    abi = pkg.abi
+    for base in hz.SIDE_BASES:
+        if not case.applies(base):
+            continue
+        rig, tr, ot = _side_setup(pkg, api, orc, contexts, base, case)
+        try:
+            frame = rig.frame0 + 1
+            rig.p.numRaysPerPixel = 1
+            p = rig.params(1)
+            tr.set_params(p)
+            ot.set_params(p)
+            o, d, state = rr.camera_rays(orc, p, rig.w, rig.h, frame=frame)
+            got = tr.radiance_trace(abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel()))
+            want = rr.oracle_pixels(orc, ot, rig.w, rig.h, frame).reshape(-1, 3)
+            ok = _same(got["rgb"], want).all(axis=1)
+            assert ok.all(), f"{case.name} on {base}: rt_radiance_trace: {int((~ok).sum())} of {len(ok)} rays differ from oracle_trace_pixel"
+            print(f"{case.name} on {base}: {int(np.isnan(want).any(axis=1).sum())} of {len(want)} rays carry a NaN")
+        finally:
+            ot.close()
+
+
+def _nee_rig(pkg, api, base, name):
+    """the four emission and area hazards: the object the value is planted in is made an emitter where the case does not do so itself"""
+    case = hz.BY_NAME[name]
+    t = hz.TARGETS[base]
+
+    def scene(pkg_, sc, t_):
+        if case.scene:
+            case.scene(pkg_, sc, t_)
+        if name == "radius-0":
+            m = sc.spheres[t_.sphere].material
+            m.flag, m.emissionCol, m.emissionStrength = 0, (1.0, 0.9, 0.7, 1.0), 5.0
+        if name == "matrix-singular":
+            m = sc.models[t_.model].material
+            m.flag, m.emissionCol, m.emissionStrength = 0, (1.0, 0.9, 0.7, 1.0), 5.0
+    made = hz.Case(name + "-emitter", case.kind, case.guard, case.tables, scene=scene, records=case.records)
+    return hz.Rig(pkg, api, base, made), (t.sphere if name == "radius-0" else None)
+
+
+@pytest.mark.parametrize("name", hz.NEE_CASES)
+def test_nee_with_emission_and_area_hazards(pkg, api, orc, contexts, name):
+    """rt_debug_light_table against the numpy table of tests/nee_reference.py, bit for bit; rt_nee_light_count; the header's rules leave
+    out an emitter whose emission is not finite and a sphere of radius 0 (asserted); rt_nee_trace on every 7th pixel's camera ray against
+    the estimator restated in tests/nee_reference.py"""
+    abi = pkg.abi
+    for base in hz.SIDE_BASES:
+        if not hz.BY_NAME[name].applies(base):
+            continue
+        rig, zero_sphere = _nee_rig(pkg, api, base, name)
+        tr = next(t for n, _, t, stats in contexts if n == "default" and not stats)
+        rig.upload(tr)
+        what = f"{name} on {base}"
+        want = nr.light_table(abi, rig.models, rig.triangles, rig.spheres)
+        got = api.light_table_arrays(rig.models, rig.triangles, rig.spheres)
+        assert got["entries"].tobytes() == want["entries"].tobytes() and got["cdf"].tobytes() == want["cdf"].tobytes(), what
+        counts = (want["n_sphere_entries"], want["n_triangle_entries"])
+        assert (got["n_sphere_entries"], got["n_triangle_entries"]) == counts and tr.nee_light_count() == counts, what
+        t = rig.targets
+        planted = t.sphere if (t.material_on == "sphere" and name.startswith("emission")) or name == "radius-0" else rig.n_spheres + t.model
+        if name in ("emission-inf", "radius-0"):   # excluded by the header's rules
+            assert not want["in_table"][planted], what
+        else:
+            assert want["in_table"][planted], what
+        assert np.isfinite(want["cdf"]).all() and np.isfinite(want["entries"]["prob"]).all()
+        rig.p.numRaysPerPixel = 1
+        p = rig.params(1)
+        tr.set_params(p)
+        o, d, state = rr.camera_rays(orc, p, rig.w, rig.h, frame=rig.frame0 + 1)
+        rays = abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel())[::7]
+        est = nr.Estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
+        expect = est.trace(rays)
+        out = tr.radiance_trace_nee(rays)
+        ok = _same(out["rgb"], expect["rgb"]).all(axis=1) & (out["rng"] == expect["rng"])
+        print(f"{what}: lights {counts}, {est.samples} samples, {est.shadow_rays} shadow rays, {est.unshadowed} unshadowed")
+        assert ok.all(), f"{what}: rt_nee_trace: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+
+
+# ---- one context through hazards and back -----------------------------------------------------------------------------------------------
+
+SEQUENCE = ("start", "sphere centre NaN", "sphere back", "matrix singular", "matrix back", "matrix NaN entry", "matrix back again")
+SEQUENCE_TABLES = (1, 0, 1, 1, 1, 0, 1)   # a singular pair is finite: by rt_primary.h's rule the tables stay on (the root filter is what it drops)
+
+
+def _sequence(pkg, lib, builder, tr, watch):
+    rig = hz.Rig(pkg, builder, "flat-tables")
+    t = rig.targets
+    rig.upload(tr)
+    tr.reset_counters()
+    spheres, models = rig.spheres.copy(), rig.models.copy()
+    l2w = hz._from_abi(models[t.model]["localToWorld"])
+    frame, out = rig.frame0, []
+    for step in SEQUENCE:
+        s, m = spheres.copy(), models.copy()
+        if step == "sphere centre NaN":
+            s[t.sphere]["centre"][0] = np.nan
+        if step in ("matrix singular", "matrix NaN entry"):
+            m[t.model]["localToWorld"], m[t.model]["worldToLocal"] = hz.matrix_pair(l2w, "singular" if step == "matrix singular" else "nan")
+        tr.update_spheres(s)
+        tr.update_models(m)
+        seen = []
+        for n in (1, 2):   # a single frame, then a fused launch
+            rig.p.frame = frame
+            tr.set_params(rig.p)
+            tr.render_frame() if n == 1 else tr.render_frames(n)
+            frame += n
+            img = tr.read_accumulated().copy()
+            seen.append((img, tr.read_frame().copy(), tr.counters()["segments"], watch(tr)))
+        out.append(seen)
+    return out
+
+
+def test_one_context_through_hazards_and_back(pkg, api, orc, contexts):
+    """rt_update_spheres swaps a finite sphere for a NaN-centred one and back, rt_update_models a regular matrix pair for a singular one,
+    for one with a NaN entry, and back; a single frame and a fused launch after each step.  The tables go off with the NaN and come back
+    on, and every image equals the oracle's, which took the same steps."""
+    ot = orc.create_tracer(8)
+    try:
+        want = _sequence(pkg, orc, orc, ot, lambda tr: None)
+    finally:
+        ot.close()
+    for name, env, tr, stats in contexts:
+        if name != "default":
+            continue
+        got = _sequence(pkg, api, api, tr, _tables)
+        for step, expect_on, g, w in zip(SEQUENCE, SEQUENCE_TABLES, got, want):
+            for part, (ga, gf, gs, gd), (wa, wf, ws, _) in zip(("single frame", "fused launch"), g, w):
+                what = f"{step}, {part} ({'STATS' if stats else 'shipped'})"
+                print(f"{what}: segments {gs} (oracle {ws}), tables {gd}")
+                hz.assert_image(ga, wa, what + ": AccumulatedRender != oracle")
+                hz.assert_image(gf, wf, what + ": FrameRender != oracle")
+                assert gs == ws, what
+                assert gd == ((1, 1, 1) if expect_on else (0, 0, 0)), f"{what}: rt_debug_primary_table / _tile_cand / _tile_tri = {gd}"
+        if stats:
+            assert tr.phase_profile()["filter_violations"][0] == 0
