@@ -636,7 +636,7 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
 #define RT_TRAV_VOTE()                                                                                         \
     do {                                                                                                       \
         /* a lane between models that has no model left is done: no more demand for phase A */              \
-        if (t.cur == RT_CODE_NEXT_MODEL && !t.cand && (MANY ? (t.m < a.nFiltered - 1 ? a.nFiltered : t.m + 1) : (t.m < 63 ? 64 : t.m + 1)) >= a.nModels) t.cur = RT_CODE_DONE; \
+        if (t.cur == RT_CODE_NEXT_MODEL && !t.cand && (MANY ? rt_plan::next_unfiltered_model(t.m, a.nFiltered) : (t.m < 63 ? 64 : t.m + 1)) >= a.nModels) t.cur = RT_CODE_DONE; \
         atNext = t.cur == RT_CODE_NEXT_MODEL;                                                                  \
         atLeaf = (t.cur & RT_CODE_LEAF) != 0;                                                                  \
         atInner = t.cur < RT_CODE_DONE; /* leaf codes have bit 31 set */                                       \
@@ -665,7 +665,7 @@ __device__ __forceinline__ bool traverse(const KArgs& a, rt_f3 rpos, rt_f3 rdir,
                         if (!summary) t.cand = 0;
                     }
                 } else {
-                    t.m = MANY ? (t.m < a.nFiltered - 1 ? a.nFiltered : t.m + 1) : (t.m < 63 ? 64 : t.m + 1);
+                    t.m = MANY ? rt_plan::next_unfiltered_model(t.m, a.nFiltered) : (t.m < 63 ? 64 : t.m + 1);
                     if (STATS && !(models[t.m].rootCode & RT_CODE_LEAF)) st.inner++;
                 }
                 t.rootStep = true;

@@ -23,6 +23,15 @@
 
 #include <cmath>
 
+/* functions the kernels call too (include/rt_math.h defines the same macro the same way) */
+#ifndef RT_HD
+#if defined(__HIPCC__)
+#define RT_HD __host__ __device__ __forceinline__
+#else
+#define RT_HD inline
+#endif
+#endif
+
 /* ---- launch geometry, shared with the kernels */
 #define RT_WAVE 64
 #define RT_PIXEL_FIELDS 4
@@ -79,6 +88,11 @@ inline Filtering filtering(int nModels)
     f.extWords = (f.nFiltered - 63 + 31) / 32;
     return f;
 }
+
+/* the model a lane of the > 64-model kernels visits after model m once its filtered candidates are used up (m = -1: none visited yet):
+ * the first model behind the filtered range, then every further one in index order; a result >= nModels says the lane is done.  The
+ * vote and phase A of traverse (rt_kernels.h) share it; tests/many_tail_driver.cpp replays it on the host. */
+RT_HD int next_unfiltered_model(int m, int nFiltered) { return m < nFiltered - 1 ? nFiltered : m + 1; }
 
 /* a wave's LDS region: traversal stack + pixel fields + (more than 64 models) the mask extension: summary + words + the MANY variant's bounce row */
 inline size_t wave_lds_bytes(int stackEntries, int extWords)

@@ -1,0 +1,323 @@
+"""Scenes with more than 64 models at every end of their candidate mask: the catalogue tests/test_many_models.py checks on the CPU and
+tests/test_gpu_many_models.py renders on the device.  A plain helper module: no GPU, no pytest.
+
+The kernels' candidate set of such a scene has four parts (ray-tracing_amd/csrc/rt_kernels.h, begin_intersect and phase A of traverse):
+a 63-bit register mask for models 0 ... 62; up to 32 extension words in the lane's LDS column for models 63 ... 1086, behind a summary
+word; models from index 1087 on, which no filter sees and which are walked in index order; and, in the trace kernel, one more LDS row
+behind the extension for the bounce count.  The catalogue:
+
+  crowd<n>            tests/test_gpu_fuzz.py::crowded_scene with n models and no spheres, n in N_EDGES: the last model of word 0 (94), the
+                      first of word 1 (95), 96, word 1 full (127), word 31 one short of full (1086), the cap (1087), one and two models
+                      behind it, a tail of 213.
+  stairs-near_first   N_STAIRS plates (one small mesh with an inner root), one behind the other, all around the ray of pixel W_PIXEL: the
+  stairs-near_last    world boxes of ALL of them hold a piece of that ray, so that lane has every extension word and every summary bit
+                      set at once.  The plates of WITNESS are larger, the farther the larger: each is the nearest surface in a ring of
+                      pixels of its own.  near_first: depth grows with the index (the first candidate is the hit); near_last: it shrinks
+                      (every later candidate replaces the hit).
+  always1300          crowd1300 with models the filter cannot reject at ALWAYS: the singular matrix pair of tests/hazard_scenes.py
+                      (matrix-singular) on a mesh with an inner root at 62, 1086, 1087 and 1299, and at 63 a leaf root the filter has no
+                      usable box for (a vertex at infinity: mesh E of tests/test_scene_prep.py::test_root_filter_boxes).  The OVERSIZED
+                      leaf root of test_oversized_and_unusable_leaf_roots_are_never_filtered takes the same arm but needs 2^23 triangles
+                      (600 MB, and 2^23 triangle tests per visit in the oracle): it stays with the host test.
+  comb_first<n>       the height-32 comb of tests/deep_trees.py as model 0 / as the last model beside n small models, n = 1086 and 1299:
+  comb_last<n>        the largest LDS region a wave can have (32 stack rows + 4 + 2 + 32); last means in the unfiltered tail for 1299.
+  flat1300            crowd1300 with bvhQuality = 2: every root is a leaf, the FLAT kernel.
+
+A Scene holds what a tracer is given — the arrays of rt_upload_scene and the RtParams — built once per name and shared; drive() uploads
+them and renders one single frame and one fused launch of two.  Test infrastructure: nothing here is imported by the product."""
+import math
+import os
+import re
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+    sys.path.insert(0, HERE)
+
+import deep_trees as dt  # noqa: E402
+import hazard_scenes as hz  # noqa: E402
+
+N_EDGES = (94, 95, 96, 127, 1086, 1087, 1088, 1089, 1300)
+FILTER_CAP = 1087                      # 63 + 32 * RT_MAX_FILTER_EXT_WORDS: models from this index on are not filtered
+N_STAIRS = 1300
+WITNESS = (0, 62, 63, 94, 95, 1085, 1086, 1087, 1088, N_STAIRS - 1)
+ALWAYS = (62, 63, 1086, 1087, 1299)
+ALWAYS_LEAF = 63                       # the one of ALWAYS that is the unusable leaf root
+EMITTERS = (62, 63, 1086, 1087, N_STAIRS - 1)   # rt_nee_trace: the emissive material on these
+COMB_OTHERS = (1086, 1299)
+CROWD_SIZE = (45, 30)                  # not a multiple of the 8 x 8 tile in either direction
+STAIRS_SIZE = (48, 32)
+COMB_SIZE = (dt.W, dt.H_IMG)
+FLAT_SIZE = (23, 15)                   # (every root a leaf of up to 108 triangles: the oracle tests each of them for every ray)
+# the largest LDS region a wave can have, 32 stack rows under 32 extension words: (waves per group, cache records, LDS bytes per group) as
+# rt_launch_plan.h plans it (tests/test_many_models.py asserts it there; the device half asserts that this is what was launched)
+EXTREME_GROUP = (9, 24, 162816)
+RENDER_SEED = 11
+
+# ---- the staircase's geometry: camera at the origin looking along +z
+STAIRS_FOV = 60.0
+W_PIXEL = (24, 16)                     # (x, y) of the pixel whose centre ray every plate's box holds
+Z0, DZ, THICK = 4.0, 0.004, 0.002      # plate at depth rank k: centre at z = Z0 + k * DZ, THICK thick
+SMALL = (1.4, 1.2)                     # half-size, in pixels around W_PIXEL, of a plate that is no witness
+
+
+def _witness_half_size(rank):
+    """half-size in pixels of the witness plate that is the rank-th nearest of the ten: rings 2.3 x 1.45 pixels wide"""
+    return 2.2 + 2.3 * rank, 1.7 + 1.45 * rank
+
+
+def pixel_tangent(x, y, size=STAIRS_SIZE, fov=STAIRS_FOV):
+    """(tan x, tan y) of the pixel-centre ray of pixel (x, y), fractions allowed: RCC:15 and RC:557-558, uv = id / (size - 1), on a plane
+    of height 2 tan(fov / 2) and width height * aspect at distance 1"""
+    w, h = size
+    th = math.tan(math.radians(fov) / 2.0)
+    return (x / (w - 1.0) - 0.5) * 2.0 * th * (w / h), (y / (h - 1.0) - 0.5) * 2.0 * th
+
+
+def plate_depth(order, index, n=N_STAIRS):
+    rank = index if order == "near_first" else n - 1 - index
+    return Z0 + DZ * rank
+
+
+def plate_transform(pkg, z, half_px, centre_px=W_PIXEL):
+    """the Transform of a plate (a unit mesh) facing the camera at depth z that covers centre_px +- half_px pixels"""
+    x0, y0 = pixel_tangent(centre_px[0] - half_px[0], centre_px[1] - half_px[1])
+    x1, y1 = pixel_tangent(centre_px[0] + half_px[0], centre_px[1] + half_px[1])
+    return pkg.Transform(((x0 + x1) / 2 * z, (y0 + y1) / 2 * z, z), (0, 0, 0), ((x1 - x0) * z, (y1 - y0) * z, THICK))
+
+
+def plate_half_size(order, index, n=N_STAIRS):
+    if index not in WITNESS:
+        return SMALL
+    by_depth = sorted(WITNESS, key=lambda i: plate_depth(order, i, n))
+    return _witness_half_size(by_depth.index(index))
+
+
+def plate_of_depth(order, z, n=N_STAIRS):
+    """the index of the plate a hit at depth z lies on (its front face is THICK / 2 in front of its centre, its rounded edge behind that)"""
+    rank = np.rint((np.asarray(z, dtype=np.float64) + THICK / 2 - Z0) / DZ).astype(np.int64)
+    return rank if order == "near_first" else n - 1 - rank
+
+
+def _material(pkg, i, rng):
+    """tests/test_gpu_fuzz.py::crowded_scene's mix: every fourth model glass, every ninth emitting"""
+    return pkg.RayTracingMaterial(flag=int(i % 4 == 3) * 2, diffuseCol=tuple(rng.uniform(0.2, 1, 3)) + (1,), ior=1.4,
+                                  emissionStrength=float(i % 9 == 0) * 3.0, emissionCol=(1, 0.9, 0.7, 1))
+
+
+SETTINGS = dict(maxBounceCount=5, numRaysPerPixel=2, defocusStrength=0.0, divergeStrength=0.5, useSky=True, accumulate=True, bvhQuality=1)
+
+
+def _crowd(pkg, n):
+    import test_gpu_fuzz as tf
+    sc = tf.crowded_scene(pkg, n, 0)
+    assert len(sc.models) == n and not sc.spheres
+    return dt.description(pkg, f"crowd{n}", sc.models, sc.camera, w=CROWD_SIZE[0], h=CROWD_SIZE[1], **dict(SETTINGS, **sc.settings))
+
+
+def _stairs(pkg, order, n=N_STAIRS):
+    assert order in ("near_first", "near_last")
+    rng = np.random.default_rng(5)
+    mesh = pkg.meshes.rounded_cube(3)
+    models = [pkg.Model(mesh, _material(pkg, i, rng), plate_transform(pkg, plate_depth(order, i, n), plate_half_size(order, i, n))) for i in range(n)]
+    cam = pkg.Camera(pkg.Transform((0, 0, 0), (0, 0, 0)), fieldOfView=STAIRS_FOV)
+    return dt.description(pkg, f"stairs-{order}", models, cam, w=STAIRS_SIZE[0], h=STAIRS_SIZE[1], **SETTINGS)
+
+
+def unusable_leaf_mesh(pkg):
+    """a leaf root of two triangles, one of them with a vertex at infinity: rt_scene_prep.h finds no usable box for it (count 0, never
+    filtered); the other triangle is an ordinary one, so the model can be seen"""
+    abi = pkg.abi
+    tris = np.zeros(2, dtype=abi.triangle_dtype)
+    tris["posA"], tris["posB"], tris["posC"] = [(-0.5, -0.5, 0), (0, 0, 0)], [(0.5, -0.5, 0), (np.inf, 0, 0)], [(0, 0.5, 0), (0, 1, 0)]
+    tris["normA"] = tris["normB"] = tris["normC"] = (0, 0, -1)
+    nodes = np.zeros(1, dtype=abi.node_dtype)
+    nodes[0] = ((-1, -1, -1), (1, 1, 1), 0, 2)
+    return dt.HandMesh("unusable-leaf", tris, nodes)
+
+
+def _always(pkg):
+    desc = _crowd(pkg, 1300)
+    inner, leaf = pkg.meshes.rounded_cube(3), unusable_leaf_mesh(pkg)
+    for i in ALWAYS:
+        desc.models[i].Mesh = leaf if i == ALWAYS_LEAF else inner
+        desc.models[i].material.flag = 2   # glass: not culled, whichever way the flattened model faces
+    desc.name = "always1300"
+
+    def records(models):
+        for i in ALWAYS:
+            if i != ALWAYS_LEAF:
+                models[i]["localToWorld"], models[i]["worldToLocal"] = hz.matrix_pair(hz._from_abi(models[i]["localToWorld"]), "singular")
+    return desc, records
+
+
+def _comb_beside(pkg, n_other, comb_first):
+    """deep_trees.comb(32) untransformed, glass, beside n_other small models placed for deep_trees.camera as tests/test_gpu_deep_trees.py
+    places its crowds, shrunk so that together they cover about a quarter of the view: with the comb last, the rays that fill its stack
+    are the ones that have hit nothing yet"""
+    rng = np.random.default_rng(3)
+    M, T = pkg.RayTracingMaterial, pkg.Transform
+    meshes = [pkg.meshes.cube(), pkg.meshes.rounded_cube(3), pkg.meshes.quad()]
+    shrink = min(1.0, math.sqrt(96.0 / n_other))
+    others = [pkg.Model(meshes[i % 3], M(flag=int(i % 4 == 3) * 2, diffuseCol=tuple(rng.uniform(0.2, 1, 3)) + (1,), ior=1.4,
+                                         emissionStrength=float(i % 9 == 0) * 3.0, emissionCol=(1, 0.9, 0.7, 1)),
+                        T((float(rng.uniform(-2.5, 2.5)), float(rng.uniform(-1.6, 1.6)), float(rng.uniform(2.0, 3.6))), tuple(rng.uniform(0, 360, 3)),
+                          float(rng.uniform(0.12, 0.35)) * shrink))
+              for i in range(n_other)]
+    comb = pkg.Model(dt.HandMesh("comb32", *dt.comb(pkg.abi, 32, "alternate")), dt.materials(pkg)["glass"], T())
+    models = [comb] + others if comb_first else others + [comb]
+    name = f"comb_{'first' if comb_first else 'last'}{n_other}"
+    return dt.description(pkg, name, models, None, w=COMB_SIZE[0], h=COMB_SIZE[1], **dict(SETTINGS, divergeStrength=0.0))
+
+
+def _flat(pkg, n):
+    desc = _crowd(pkg, n)
+    desc.settings["bvhQuality"] = 2
+    desc.width, desc.height = FLAT_SIZE
+    desc.name = f"flat{n}"
+    return desc
+
+
+CATALOGUE = ([f"crowd{n}" for n in N_EDGES] + ["stairs-near_first", "stairs-near_last", "always1300"] +
+             [f"comb_{o}{n}" for n in COMB_OTHERS for o in ("first", "last")] + ["flat1300"])
+COMB_SCENES = [n for n in CATALOGUE if n.startswith("comb_")]
+
+
+def describe(pkg, name):
+    """-> (SceneDescription, records hook or None) of a catalogue name; crowd<n> and flat<n> for any n"""
+    m = re.fullmatch(r"(crowd|flat|comb_first|comb_last)(\d+)", name)
+    if m and m.group(1) == "crowd":
+        return _crowd(pkg, int(m.group(2))), None
+    if m and m.group(1) == "flat":
+        return _flat(pkg, int(m.group(2))), None
+    if m:
+        return _comb_beside(pkg, int(m.group(2)), m.group(1) == "comb_first"), None
+    if name.startswith("stairs-"):
+        return _stairs(pkg, name[len("stairs-"):]), None
+    if name == "always1300":
+        return _always(pkg)
+    raise KeyError(name)
+
+
+class Scene:
+    """what a tracer is given: the arrays of rt_upload_scene and the RtParams.  `builder`: a library with the BVH builder and
+    rt_camera_view_params (the HIP library or the oracle: the same bytes)."""
+
+    def __init__(self, pkg, builder, name):
+        desc, records = describe(pkg, name)
+        mgr = desc.make_manager(hz._NoTracer(), builder, desc.width, desc.height)
+        mgr.renderSeed = RENDER_SEED
+        data = mgr.CreateAllMeshData(mgr.models)
+        self.models, self.triangles, self.nodes = data["meshInfo"].copy(), data["triangles"], data["nodes"]
+        if records:
+            records(self.models)
+        self.spheres = np.zeros(0, dtype=pkg.abi.sphere_dtype)
+        self.p = mgr.params()
+        self.name, self.w, self.h, self.n = name, desc.width, desc.height, len(self.models)
+        self.tri_count = np.array([m.Mesh.triangle_count for m in mgr.models], dtype=np.int64)
+        self.materials = self.models["material"]   # by object index: there are no spheres
+        self.n_spheres = 0
+        self.order = name[len("stairs-"):] if name.startswith("stairs-") else None
+        for a in (self.models, self.triangles, self.nodes):
+            a.setflags(write=False)
+
+    def params(self, frame=1, **fields):
+        """a copy of the RtParams at frame `frame`, with `fields` set on top"""
+        p = type(self.p).from_buffer_copy(self.p)
+        p.frame = frame
+        for k, v in fields.items():
+            setattr(p, k, v)
+        return p
+
+    def upload(self, tr, models=None):
+        tr.resize(self.w, self.h)
+        tr.upload_scene(self.models if models is None else models, self.triangles, self.nodes, self.spheres)
+        tr.set_params(self.params(1))
+        tr.reset_accumulation()
+
+
+_scenes = {}
+
+
+def scene(pkg, builder, name):
+    """the Scene of a name: built once, shared, never written"""
+    if name not in _scenes:
+        _scenes[name] = Scene(pkg, builder, name)
+    return _scenes[name]
+
+
+def render_steps(sc, tr, first_frame=1):
+    """one single frame, then one fused launch of two -> [(acc, frame) after either]; the context holds sc already"""
+    out = []
+    for frame, n in ((first_frame, 1), (first_frame + 1, 2)):
+        tr.set_params(sc.params(frame))
+        tr.render_frame() if n == 1 else tr.render_frames(n)
+        out.append((tr.read_accumulated().copy(), tr.read_frame().copy()))
+    return out
+
+
+def drive(sc, tr):
+    """-> ((acc, frame) after a single-frame launch, (acc, frame) after a fused launch of two more, the counters)"""
+    sc.upload(tr)
+    single, fused = render_steps(sc, tr)
+    return single, fused, tr.counters()
+
+
+_expected = {}
+
+
+def expected(pkg, orc, name):
+    """the oracle's drive() of a catalogue scene: computed once, shared, never written"""
+    if name not in _expected:
+        tr = orc.create_tracer(8)
+        try:
+            out = drive(scene(pkg, orc, name), tr)
+        finally:
+            tr.close()
+        for part in out[:2]:
+            for img in part:
+                img.setflags(write=False)
+        _expected[name] = out
+    return _expected[name]
+
+
+def pixel_centre_rays(sc):
+    """one ray per pixel centre: (H, W, 3) origins and directions in fp32 (hazard_scenes.pixel_centre_rays reads .p, .w and .h)"""
+    return hz.pixel_centre_rays(sc)
+
+
+_first_hits = {}
+
+
+def first_hit_models(pkg, orc, sc):
+    """(H, W) index of the plate each pixel-centre ray of a staircase hits first, -1 = none: oracle_ray_collision's hit, named by its depth"""
+    import ctypes as C
+    if sc.name not in _first_hits:
+        assert sc.order is not None
+        F3 = C.c_float * 3
+        origins, dirs = pixel_centre_rays(sc)
+        out, first = (C.c_float * 10)(), np.full((sc.h, sc.w), -1, dtype=np.int64)
+        ot = orc.create_tracer(1)
+        try:
+            sc.upload(ot)
+            for y in range(sc.h):
+                for x in range(sc.w):
+                    orc.ray_collision(ot.h, F3(*origins[y, x]), F3(*dirs[y, x]), out)
+                    if out[0] != 0:
+                        first[y, x] = plate_of_depth(sc.order, out[8], sc.n)
+        finally:
+            ot.close()
+        first.setflags(write=False)
+        _first_hits[sc.name] = first
+    return _first_hits[sc.name]
+
+
+def with_emitters(sc, indices=EMITTERS):
+    """a copy of the scene's model records with the emissive, opaque material on `indices`"""
+    models = sc.models.copy()
+    for i in indices:
+        mat = models["material"][i:i + 1]
+        mat["flag"], mat["emissionCol"], mat["emissionStrength"] = 0, (1.0, 0.9, 0.7, 1.0), 5.0
+    return models

@@ -414,13 +414,15 @@ def test_filter_pair_records(drivers, n):
 
 
 # ---------------------------------------------------------------- 5.4 chunks
-@pytest.mark.parametrize("n", [64, 65, 200])
+@pytest.mark.parametrize("n", [64, 65, 200, 1086, 1087, 1088, 1300])
 def test_chunks(drivers, n):
     f = _random_filters(np.random.default_rng(100 + n), n, always_every=10)
     req = [f"chunks {n} {f.tobytes().hex()}", f"filtering {n}"]
     info, raw, plan, info2, raw2, _ = ask(drivers["san"], req + req)
     assert (info, raw) == (info2, raw2)  # the same input, the same bytes
     assert (info["n_filtered"], info["ext_words"]) == (plan["n_filtered"], plan["ext_words"])
+    if n > 1087:  # the cap: 63 + 32 extension words of 32 models; the models behind it are in no chunk
+        assert info["n_filtered"] == 1087 and info["ext_words"] == 32
     if n <= 64:
         assert info["n_chunks"] == 0 and raw == b"" and plan == {"n_filtered": n, "ext_words": 0}
         return
