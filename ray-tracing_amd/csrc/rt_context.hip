@@ -152,6 +152,7 @@ struct RtContext {
     bool tileCandOn = true;        /* RT_TILE_CAND=0: the per-ray pre-test stays (A/B runs, tests) */
     int lastTileCand = -1;         /* whether the most recent trace launch read a table (rt_debug_tile_cand); -1 = none yet */
     bool tileTriOn = true;         /* RT_TILE_TRI=0: the table's triangle half stays off alone: every triangle mask is all ones (A/B runs, tests) */
+    bool skySunOn = true;          /* RT_SKY_SUN=0: no launch carries RT_USESKY_SUN_UNSEEN, every miss evaluates the sun (A/B runs, tests) */
     int lastTileTri = -1;          /* whether that launch's table held triangle masks (rt_debug_tile_tri); -1 = none yet */
     uint32_t* dTileCand[2] = {nullptr, nullptr};
     int tileCandTiles = 0;         /* tiles the two tables are sized for; 0 = none */
@@ -576,6 +577,7 @@ int rt_create(int device_id, RtContext** out)
     if (const char* g = getenv("RT_PRIMARY")) ctx->primaryOn = atoi(g) != 0;
     if (const char* g = getenv("RT_TILE_CAND")) ctx->tileCandOn = atoi(g) != 0;
     if (const char* g = getenv("RT_TILE_TRI")) ctx->tileTriOn = atoi(g) != 0;
+    if (const char* g = getenv("RT_SKY_SUN")) ctx->skySunOn = atoi(g) != 0;
     if (const char* g = getenv("RT_POOL_FAULT")) { if (atoi(g)) ctx->poolSpinLimit = 64u | 0x80000000u; }
     if (getenv("RT_VERBOSE")) ctx->verbose = true;
     if (const char* f = getenv("RT_FUSE_FRAMES")) ctx->fuseFrames = atoi(f) != 0;
@@ -1076,8 +1078,12 @@ int rt_reset_accumulation(RtContext* ctx)
 }
 
 /* withTable: the launch is one of the trace kernels' (launch_frames, adaptive_launch) — the only readers of the table of per-launch
- * origin constants (rt_primary.h); every other launch carries it switched off and pays nothing for it */
-static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool withTable = false)
+ * origin constants (rt_primary.h); every other launch carries it switched off and pays nothing for it.
+ * traceBody: the launch runs trace_body (launch_frames, adaptive_launch, rt_render_cost), whose every ray direction is rt_normalize's
+ * result: it may carry RT_USESKY_SUN_UNSEEN (rt_sky.h).  The side passes (AOV, query, radiance, NEE) must NOT: their first segment
+ * carries the caller's direction, unnormalised — dir = (0, -1e30, 0) is NaN (inf * 0) in the full GetEnvironmentLight and 0.35 without
+ * the sun's addend — so their fill leaves the bit clear, and their kernels do not even test it. */
+static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool withTable = false, bool traceBody = false)
 {
     memset(&a, 0, sizeof(a));
     a.spheres = ctx->dSpheres;
@@ -1114,7 +1120,8 @@ static void fill_args(RtContext* ctx, int frame0, int nFrames, KArgs& a, bool wi
     a.frame0 = frame0;
     a.nFrames = nFrames;
     a.seed = p.renderSeed;
-    a.useSky = p.useSky;
+    a.useSky = p.useSky ? RT_USESKY_ON : 0;
+    if (traceBody && ctx->skySunOn && sky_sun_unseen(p)) a.useSky |= RT_USESKY_SUN_UNSEEN; /* decided per launch, from this launch's uniforms */
     a.accumulate = p.accumulate;
     a.defocus = p.defocusStrength;
     a.diverge = p.divergeStrength;
@@ -1557,7 +1564,7 @@ int HipOrder::accumulate(int s)
 static int launch_frames(RtContext* ctx, int frame0, int nFrames)
 {
     KArgs a;
-    fill_args(ctx, frame0, nFrames, a, true);
+    fill_args(ctx, frame0, nFrames, a, true, true);
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
     LaunchPlan plan;
@@ -1971,7 +1978,7 @@ int rt_render_cost(RtContext* ctx, int frame, RtPixelCost* out, size_t bytes)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     RT_FLUSH(ctx);
     KArgs a;
-    fill_args(ctx, frame, 1, a);
+    fill_args(ctx, frame, 1, a, false, true);
     const int tiles = a.tilesX * a.tilesY;
     if (tiles == 0) return RT_OK;
     rt_plan::SceneShape sc; /* no cache, no pool: single waves */
@@ -2203,7 +2210,7 @@ static int adaptive_launch(RtContext* ctx, int frame0, int nFrames, bool* unstag
 {
     *unstaged = false;
     KArgs a;
-    fill_args(ctx, frame0, nFrames, a, true);
+    fill_args(ctx, frame0, nFrames, a, true, true);
     LaunchPlan plan;
     int rc = choose_variant(ctx, a, plan);
     if (rc) return rc;

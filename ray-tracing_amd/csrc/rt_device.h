@@ -30,6 +30,7 @@
 
 #include "rt_records.h"
 #include "rt_primary.h"
+#include "rt_sky.h"
 
 struct KArgs {
     /* scene */
@@ -66,7 +67,7 @@ struct KArgs {
     int32_t wavesPerGroup, hotUnits, waveLdsDwords;
     uint32_t travLimit;          /* traversal watchdog: iterations of one traverse() call no validated scene can reach (rt_kernels.h) */
     /* uniforms (RtParams) */
-    int32_t maxBounce, spp, frame0, nFrames, seed, useSky, accumulate;
+    int32_t maxBounce, spp, frame0, nFrames, seed, useSky, accumulate; /* useSky: RT_USESKY_ON | RT_USESKY_SUN_UNSEEN (rt_sky.h) */
     float defocus, diverge, sunFocus, sunIntensity;
     float sunColour[3], dirToSun[3], viewParams[3];
     float cam[16];

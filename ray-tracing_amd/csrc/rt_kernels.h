@@ -149,6 +149,36 @@ __device__ __forceinline__ rt_f3 environment_light(const Args& a, rt_f3 dir)
     return rt_lerp3(rt_v3(0.35f, 0.3f, 0.35f), skyGradient, groundToSkyT)
            + sun * rt_v3(a.sunColour[0], a.sunColour[1], a.sunColour[2]) * gate;
 }
+/* The frame and cost kernels' form (trace_body: every direction is rt_normalize's).  A launch for which the host proved that the sun's
+ * addend never changes a bit of the sum (rt_sky.h, sky_sun_unseen: the default sun, straight down) carries RT_USESKY_SUN_UNSEEN in the
+ * word the caller has just tested — no further scalar load — and the wave takes a uniform branch around the addend: the dot product, the
+ * max, the divide, one log, one exp, seven multiplies, three adds and the scalar loads of the sun's uniforms.  The STATS instantiations
+ * evaluate both forms for such a launch and count a difference (other than NaN against NaN) as a filter violation.  The side passes
+ * (AOV, radiance, NEE: caller-made directions of any length) call environment_light itself, and their launches never carry the bit. */
+template <bool STATS, class Args>
+__device__ __forceinline__ rt_f3 environment_light_frame(const Args& a, const int32_t useSky, rt_f3 dir, Stats& st)
+{
+    /* the same statements as environment_light, the first addend written once in front of the branch */
+    float skyGradientT = rtd_pow(rtd_smoothstep_edges(0.0f, 0.4f, dir.y), 0.35f);
+    float groundToSkyT = rtd_smoothstep_edges(-0.01f, 0.0f, dir.y);
+    rt_f3 skyGradient = rt_lerp3(rt_v3(1, 1, 1), rt_v3(0.08f, 0.37f, 0.73f), skyGradientT);
+    const rt_f3 blend = rt_lerp3(rt_v3(0.35f, 0.3f, 0.35f), skyGradient, groundToSkyT);
+    const bool unseen = (useSky & RT_USESKY_SUN_UNSEEN) != 0;
+    if (unseen && !STATS) return blend;
+    float s = rt_div(1000 * 1, a.sunFocus);
+    rt_f3 toSun = rt_v3(a.dirToSun[0], a.dirToSun[1], a.dirToSun[2]);
+    float sun = rtd_pow(rt_max(0.0f, rt_dot(dir, toSun)), s) * a.sunIntensity;
+    float gate = (groundToSkyT >= 1.0f) ? 1.0f : 0.0f;
+    const rt_f3 full = blend + sun * rt_v3(a.sunColour[0], a.sunColour[1], a.sunColour[2]) * gate;
+    if (STATS && unseen) { /* the audit: the launch's predicate against every direction this wave meets */
+        const bool same = (rt_f2u(full.x) == rt_f2u(blend.x) || (full.x != full.x && blend.x != blend.x)) &&
+                          (rt_f2u(full.y) == rt_f2u(blend.y) || (full.y != full.y && blend.y != blend.y)) &&
+                          (rt_f2u(full.z) == rt_f2u(blend.z) || (full.z != full.z && blend.z != blend.z));
+        if (!same) st.filterViolations++;
+        return blend;
+    }
+    return full;
+}
 
 /* CalculateReflectance — RC:383-405 */
 __device__ __forceinline__ float reflectance(rt_f3 inDir, rt_f3 normal, float iorA, float iorB)
@@ -1160,6 +1190,7 @@ __device__ __forceinline__ void trace_body(const KArgs& a, uint32_t* const cost 
     extern __shared__ uint32_t s_lds[];
     /* FLAT && HOT: the FLAT variant launched as multi-wave workgroups that share the CHAIN POOL (pool_exchange) in place of a tree cache */
     constexpr bool POOL = FLAT && HOT;
+    constexpr bool SKY_SUN = true; /* every direction here is rt_normalize's: the sky may leave out a sun the host proved unseen (environment_light_frame) */
     const int lane = HOT ? (int)(threadIdx.x & (RT_WAVE - 1)) : (int)threadIdx.x;
     const int wave = HOT ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
     const uint32_t hotUnits = HOT ? (uint32_t)a.hotUnits : 0u;
@@ -1742,6 +1773,7 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     extern __shared__ uint32_t s_lds[];
     /* the names rt_shade_phase.inl reads that have one value here */
     constexpr bool STATS = false, HOT = false, COST = false;
+    constexpr bool SKY_SUN = false; /* the rays are the caller's, of any length: the full GetEnvironmentLight (rt_sky.h) */
     const RT_LDS char* const hotLds = (const RT_LDS char*)s_lds;
     const uint32_t hotUnits = 0u;
     uint32_t* const cost = nullptr;
@@ -1874,7 +1906,7 @@ template <bool FLAT, bool MANY>
 __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_radiance_nee_kernel(const KArgs a, const float4* __restrict__ rays, const int n, float4* __restrict__ out, const NeeTable lt, const uint32_t* __restrict__ unitTri)
 {
     extern __shared__ uint32_t s_lds[];
-    constexpr bool STATS = false; /* (rt_shade_block.inl reads it) */
+    constexpr bool STATS = false, SKY_SUN = false; /* (rt_shade_block.inl reads them; SKY_SUN: as in rt_radiance_kernel) */
     const int lane = (int)threadIdx.x;
     uint32_t* const stackBase = &s_lds[lane];
     uint32_t* const extBase = &s_lds[(size_t)(a.stackEntries + RT_PIXEL_FIELDS) * RT_WAVE + lane];

@@ -1,7 +1,7 @@
 /* rt_shade_block.inl — the rest of one iteration of Trace's bounce loop (RC:488-538) for a lane whose intersection `h` is complete: the
  * one statement of the results contract's shade rules (draw order, RC:499-538).  Textually included by rt_shade_phase.inl (the frame,
  * cost and rt_radiance kernels) and by rt_radiance_nee_kernel (rt_kernels.h).  Not a header: it reads and writes the including
- * function's locals (a, h, rng, rpos, rdir, transmittance, pathLight, bounce, extBase, st, endPath; STATS, MANY), and sets endPath
+ * function's locals (a, h, rng, rpos, rdir, transmittance, pathLight, bounce, extBase, st, endPath; STATS, MANY, SKY_SUN), and sets endPath
  * where the path ends; what an ended path does is the including site's.
  * Three hooks, one per amendment of include/rt_nee.h, defined by the including site and undefined right after the include (macros: a
  * callable changed the register allocation of the > 64-model trace kernel):
@@ -11,7 +11,11 @@
             if (h.obj < 0) {
                 phase_mark<STATS>(st, PH_SKY);
                 const RT_CAS KArgs& c = cold_args();
-                if (c.useSky) pathLight = pathLight + transmittance * environment_light(c, rdir);
+                const int32_t useSky = c.useSky; /* bit 0: UseSky; bit 1: the launch's sun is never seen (rt_sky.h; frame and cost launches only) */
+                if (useSky) {
+                    if constexpr (SKY_SUN) pathLight = pathLight + transmittance * environment_light_frame<STATS>(c, useSky, rdir, st);
+                    else pathLight = pathLight + transmittance * environment_light(c, rdir);
+                }
                 endPath = true;
             } else {
                 /* resolve the winner: position, normal, material */

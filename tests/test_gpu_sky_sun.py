@@ -1,0 +1,250 @@
+"""The sky without a sun that is never seen (ray-tracing_amd/csrc/rt_sky.h) on the GPU.
+
+A launch whose uniforms pass sky_sun_unseen carries a bit in KArgs::useSky, and the frame kernels take a wave-uniform branch around the
+sun's addend of GetEnvironmentLight; the result must not move by a bit.  Every case is rendered with the branch allowed and with
+RT_SKY_SUN=0, by the shipped and by the STATS instantiation — the FLAT scene as pooled workgroups (RT_POOL_MIN_ITEMS=0: also at these
+sizes) and as single waves (RT_POOL=0) — and each image is compared bit for bit with ONE render of the CPU oracle (where the oracle has
+a NaN, a NaN: a NaN's sign and payload are not part of the contract), the segment counters with the oracle's, and the audit (in the
+STATS build a launch with the bit evaluates both forms and counts a difference as a filter violation) with 0.
+
+  accepted suns: what tests/test_sky_sun.py proves on the host, through the kernels;
+  refused suns: above the horizon, tilted by 1e-30, longer than 1, and each refusing value of focus, intensity and colour: the whole
+      function still runs, and a predicate that let one of them pass would show as a different bit or as a violation;
+  one context whose sun changes while frames are held back (RT_HOLD_BACK=1): the bit follows the launch, not the context;
+  a radiance batch with an unnormalised direction on a context whose frame launches carry the bit: the side passes keep the whole function.
+
+At most 64 x 36 pixels, two rays per pixel, three frames."""
+import contextlib
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+F3 = C.c_float * 3
+ENV = ("RT_SKY_SUN", "RT_POOL", "RT_POOL_MIN_ITEMS", "RT_HOLD_BACK", "RT_COALESCE")
+FLAT_WAYS = [("pooled", {"RT_POOL_MIN_ITEMS": "0"}), ("single waves", {"RT_POOL": "0"})]
+BVH_WAYS = [("bvh", {})]
+B = float(2 ** 20)   # RT_SKY_SCALE_MAX
+
+
+class Sun:
+    """stands in for a sun object's transform: RCM:176 takes dirToSun = -forward, whatever its length"""
+
+    def __init__(self, x, y, z):
+        self.forward = -np.array([x, y, z], dtype=np.float64)
+
+
+ACCEPTED = {
+    "default": {},
+    "half length": dict(sunTransform=Sun(0.0, -0.5, 0.0)),
+    "dirToSun.y = -0": dict(sunTransform=Sun(0.0, -0.0, 0.0)),
+    "x and z = -0": dict(sunTransform=Sun(-0.0, -1.0, -0.0)),
+    "focus 15.625 (s = 64)": dict(sunFocus=15.625),
+    "focus 560 (near the bound)": dict(sunFocus=560.0),
+    "intensity and colour at their bounds": dict(sunFocus=100.0, sunIntensity=B, sunColor=(-B, B, B)),
+}
+REFUSED = {
+    "sun above the horizon": dict(sunTransform=Sun(0.3, 0.8, -0.52)),
+    "tilted by 1e-30": dict(sunTransform=Sun(1e-30, -1.0, 0.0)),
+    "straight up": dict(sunTransform=Sun(0.0, 1.0, 0.0)),
+    "length 1.5": dict(sunTransform=Sun(0.0, -1.5, 0.0)),
+    "focus 0": dict(sunFocus=0.0),
+    "focus 1e30": dict(sunFocus=1e30),
+    "focus negative": dict(sunFocus=-500.0),
+    "intensity inf": dict(sunIntensity=float("inf")),
+    "intensity NaN": dict(sunIntensity=float("nan")),
+    "colour 1e30": dict(sunColor=(1.0, 1e30, 1.0)),
+}
+
+
+@contextlib.contextmanager
+def environment(env):
+    """all of them are read when a context is made or a scene is uploaded"""
+    old = {k: os.environ.get(k) for k in ENV}
+    for k in ENV:
+        os.environ.pop(k, None)
+    os.environ.update(env)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            os.environ.pop(k, None)
+            if v is not None:
+                os.environ[k] = v
+
+
+def same(got, want):
+    """bit for bit; where the expected float is a NaN, a NaN"""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    return got.shape == want.shape and bool(np.where(np.isnan(want), np.isnan(got), got.view(np.uint32) == want.view(np.uint32)).all())
+
+
+def flat_scene(pkg):
+    sc = pkg.scenes.get(2)   # 16 spheres and a ground quad: FLAT, within the caps of the tables
+    sc.settings.update(numRaysPerPixel=2, maxBounceCount=4, useSky=True)
+    return sc, (64, 36)
+
+
+def bvh_scene(pkg):
+    sc = pkg.scenes.get(3)   # a room of meshes with trees; without its back wall, so that paths leave it for the sky
+    sc.settings.update(numRaysPerPixel=2, maxBounceCount=4, useSky=True)
+    sc.models = [m for m in sc.models if m.name != "WallBack"]
+    return sc, (48, 27)
+
+
+def driver(pkg, make_scene, sun, steps):
+    def drive(lib, tr):
+        sc, (w, h) = make_scene(pkg)
+        sc.settings.update(sun)
+        mgr = sc.make_manager(tr, lib, w, h)
+        mgr.OnEnable(renderSeed=3)
+        return steps(mgr, tr)
+    return drive
+
+
+def three_frames(mgr, tr):
+    mgr.RenderFrame()    # a single frame, then a fused launch of two
+    mgr.RenderFrames(2)
+    return [tr.read_accumulated()]
+
+
+def check(api, orc, drive, ways):
+    c = orc.create_tracer(8)
+    want = drive(orc, c)
+    wantSeg = c.counters()["segments"]
+    c.close()
+    for name, env in ways:
+        for sky_sun in ("1", "0"):
+            with environment(dict(env, RT_SKY_SUN=sky_sun)):
+                for stats in (False, True):
+                    g = api.create_tracer(0)
+                    g.enable_stats(stats)
+                    got = drive(api, g)
+                    seg = g.counters()["segments"]
+                    prof = g.phase_profile() if stats else None
+                    g.close()
+                    what = f"{name}, RT_SKY_SUN={sky_sun}, stats={stats}"
+                    assert len(got) == len(want)
+                    for i, (a, b) in enumerate(zip(got, want)):
+                        assert same(a, b), f"{what}: image {i} differs from the oracle's"
+                    assert seg == wantSeg, f"{what}: {seg} segments, the oracle {wantSeg}"
+                    if stats:
+                        assert prof["filter_violations"][0] == 0, what
+                        assert prof["sky"][0] > 0, f"{what}: no wave ran the sky phase"
+    return want
+
+
+@pytest.mark.parametrize("sun", list(ACCEPTED), ids=[k.replace(" ", "_") for k in ACCEPTED])
+def test_accepted_suns_flat(pkg, api, orc, sun):
+    want = check(api, orc, driver(pkg, flat_scene, ACCEPTED[sun], three_frames), FLAT_WAYS)
+    assert np.isfinite(want[0]).all()
+
+
+@pytest.mark.parametrize("sun", list(REFUSED), ids=[k.replace(" ", "_") for k in REFUSED])
+def test_refused_suns_flat(pkg, api, orc, sun):
+    check(api, orc, driver(pkg, flat_scene, REFUSED[sun], three_frames), FLAT_WAYS)
+
+
+@pytest.mark.parametrize("sun", ["default", "focus 560 (near the bound)"])
+def test_accepted_suns_bvh(pkg, api, orc, sun):
+    check(api, orc, driver(pkg, bvh_scene, ACCEPTED[sun], three_frames), BVH_WAYS)
+
+
+@pytest.mark.parametrize("sun", ["sun above the horizon", "tilted by 1e-30", "intensity inf"])
+def test_refused_suns_bvh(pkg, api, orc, sun):
+    check(api, orc, driver(pkg, bvh_scene, REFUSED[sun], three_frames), BVH_WAYS)
+
+
+def test_a_visible_sun_changes_the_image(pkg, orc):
+    """the refused case above is a different picture: the comparison with the oracle can tell the two functions apart"""
+    images = []
+    for sun in ({}, REFUSED["sun above the horizon"]):
+        c = orc.create_tracer(8)
+        images.append(driver(pkg, flat_scene, sun, three_frames)(orc, c)[0])
+        c.close()
+    assert not np.array_equal(images[0].view(np.uint32), images[1].view(np.uint32))
+
+
+@pytest.mark.parametrize("make_scene", [flat_scene, bvh_scene], ids=["flat", "bvh"])
+def test_the_bit_follows_the_launch_not_the_context(pkg, api, orc, make_scene):
+    """default sun, a visible sun, the default again on ONE context, two single frames each; with RT_HOLD_BACK=1 every rt_render_frame is held
+    back and launched, fused, when rt_set_params is about to change the uniforms — with the uniforms, and the bit, of ITS frames"""
+    def steps(mgr, tr, read_between):
+        out = []
+        for sun in (None, Sun(0.3, 0.8, -0.52), None):
+            mgr.sunTransform = sun
+            mgr.RenderFrame()
+            mgr.RenderFrame()
+            if read_between:
+                out.append(tr.read_accumulated())
+        out.append(tr.read_accumulated())
+        out.append(tr.read_frame())
+        return out
+
+    def run(lib, env, read_between, stats=False):
+        with environment(env):
+            tr = lib.create_tracer(0) if lib is api else lib.create_tracer(8)
+            if lib is api:
+                tr.enable_stats(stats)
+            got = driver(pkg, make_scene, {}, lambda mgr, t: steps(mgr, t, read_between))(lib, tr)
+            violations = tr.phase_profile()["filter_violations"][0] if stats else 0
+            tr.close()
+        assert violations == 0
+        return got
+
+    want = run(orc, {}, True)
+    eager = run(api, {"RT_COALESCE": "0"}, True)
+    assert len(eager) == len(want) == 5
+    for i, (a, b) in enumerate(zip(eager, want)):
+        assert same(a, b), f"eager twin, image {i}: differs from the oracle's"
+    for stats in (False, True):
+        held = run(api, {"RT_HOLD_BACK": "1"}, True, stats)
+        for i, (a, b) in enumerate(zip(held, eager)):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"held back, stats={stats}, image {i}: differs from the eager twin's"
+        last = run(api, {"RT_HOLD_BACK": "1"}, False, stats)   # nothing read in between: only rt_set_params flushes
+        for a, b in zip(last, eager[-2:]):
+            assert np.array_equal(a.view(np.uint32), b.view(np.uint32)), f"held back, stats={stats}, read at the end only: differs from the eager twin's"
+    assert not np.array_equal(want[0].view(np.uint32), want[1].view(np.uint32))
+
+
+def test_a_side_pass_keeps_the_whole_function(pkg, api, orc):
+    """rt_radiance_trace takes the caller's direction as it is.  (0, -1e30, 0) past the ground's edge under the default sun:
+    pow(1e30, 2) = inf and inf * 0 = NaN in GetEnvironmentLight, 0.35 / 0.3 / 0.35 without the sun's addend.  The context's frame
+    launches carry the bit; the batch must not."""
+    sc, (w, h) = flat_scene(pkg)
+    with environment({}):
+        tr = api.create_tracer(0)
+        try:
+            mgr = sc.make_manager(tr, api, w, h)
+            mgr.OnEnable(renderSeed=3)
+            mgr.RenderFrames(2)
+            p = mgr.params()
+            origins = np.array([[1000.0, 5.0, 1000.0], [0.0, 50.0, 0.0], [1000.0, 5.0, 1000.0]], dtype=F)
+            dirs = np.array([[0.0, -1e30, 0.0], [0.0, 1.0, 0.0], [0.0, -1.0, 0.0]], dtype=F)
+            rays = pkg.abi.make_path_rays(origins, dirs, np.array([1, 2, 3], dtype=np.uint32))
+            got = tr.radiance_trace(rays)
+            nee = tr.radiance_trace_nee(rays)
+            hits = tr.query_closest(pkg.abi.make_rays(origins, dirs))
+            mgr.RenderFrames(1)   # and the frames go on
+            image = tr.read_accumulated()
+        finally:
+            tr.close()
+    assert (hits["object"] < 0).all(), "the three rays are meant to miss"
+    want = np.zeros((3, 3), dtype=F)
+    out3 = F3()
+    with np.errstate(all="ignore"):
+        for i in range(3):
+            orc.environment_light(C.byref(p), F3(*dirs[i]), out3)
+            want[i] = F(0) + F(1) * np.array(out3[:], dtype=F)   # RC:490
+    assert np.isnan(want[0]).all() and np.isfinite(want[1:]).all()
+    assert same(got["rgb"], want), (got["rgb"], want)
+    assert same(nee["rgb"], want), (nee["rgb"], want)
+    c = orc.create_tracer(8)
+    mgr = flat_scene(pkg)[0].make_manager(c, orc, w, h)
+    mgr.OnEnable(renderSeed=3)
+    mgr.RenderFrames(3)
+    assert same(image, c.read_accumulated())
+    c.close()
