@@ -13,7 +13,14 @@ rt_reset_accumulation): a table left over from the previous case's key would sho
 
 Side passes (hazard_scenes.SIDE_CASES on SIDE_BASES): rt_render_aov, rt_query_closest / rt_query_occluded / rt_debug_intersect,
 rt_radiance_trace and (NEE_CASES) rt_nee_trace against the oracle's functions.  Floats are compared bit for bit, except that where
-the expected value is a NaN the device's must be one too (a NaN's sign and payload are not part of the contract)."""
+the expected value is a NaN the device's must be one too (a NaN's sign and payload are not part of the contract).
+
+The triangle and mesh cases ride through all of the above; on top, for them: (object, triangle) of the AOV and query records is the
+triangle oracle_ray_triangle names; rays at the corners and edges of the most seen triangles and one at tri_test's determinant threshold
+exactly; three cases under the layout that moves and pre-differences the triangle records; the light table's area rule with an emissive
+model of planted triangles; rt_build_bvh_gpu_batch on every planted mesh.  Only values are planted: every index, count and offset stays
+what validation accepted."""
+import copy
 import ctypes as C
 import time
 
@@ -95,7 +102,7 @@ def _check(pkg, api, orc, case, base, name, env, tr, stats):
 
 @pytest.mark.parametrize("case", ALL, ids=IDS)
 def test_every_case_on_every_base_equals_the_oracle(pkg, api, orc, contexts, case):
-    bases = [b for b in hz.BASES if case is None or case.applies(b)]
+    bases = [b for b in hz.BASES if case is None or case.builds(b)]   # (a pair the builders refuse: test_gpu_builder_on_every_mesh_case)
     for base in bases:
         hz.expected(pkg, orc, base, case)   # (the oracle's renders, on the CPU: not part of the time printed below)
     t0 = time.perf_counter()
@@ -162,6 +169,21 @@ def _side_setup(pkg, api, orc, contexts, base, case):
     return rig, tr, ot
 
 
+def _assert_named(pkg, orc, rig, origins, dirs, hits10, objects, triangles, what):
+    """the device's (object, triangle) of every ray is one the oracle's hit can be (hazard_scenes.hit_candidates: oracle_ray_triangle over
+    every model's range gives the hit's dst bit for bit): THE one where there is one; of a tie — coincident triangles, a shared edge —
+    the walk order decides, and the record's normal and backface bit, compared with the oracle's elsewhere, say which.
+    -> (rays named, ties among them)"""
+    _, cands = hz.hit_candidates(pkg, orc, rig, np.ascontiguousarray(origins, dtype=F), np.ascontiguousarray(dirs, dtype=F), hits10)
+    named = ties = 0
+    for i, c in enumerate(cands):
+        if c:
+            got = (int(objects[i]) - rig.n_spheres, int(triangles[i]))
+            assert got in c, f"{what}: ray {i}: (model, triangle) {got}, the oracle's hit is on {c}"
+            named, ties = named + 1, ties + (len(c) > 1)
+    return named, ties
+
+
 SIDE = [hz.BY_NAME[n] for n in hz.SIDE_CASES]
 
 
@@ -206,6 +228,9 @@ def test_aov_records_of_a_hazard_scene(pkg, api, orc, contexts, case):
                 mi = int(aov["object"][i]) - rig.n_spheres
                 off = int(rig.models["triOffset"][mi])
                 assert off <= int(aov["triangle"][i]) < off + int(rig.tri_count[mi]), (what, i)
+            if case.kind in ("triangle", "mesh"):   # object and triangle are the oracle's, named by oracle_ray_triangle
+                named = _assert_named(pkg, orc, rig, o, d, hits10, aov["object"], aov["triangle"], what)
+                print(f"{what}: (object, triangle) named for {named[0]} pixels, {named[1]} of them ties")
             print(f"{what}: {int(hit.sum())} of {len(hit)} pixels hit, {int(np.isnan(hits10).any(axis=1).sum())} records with a NaN")
         finally:
             ot.close()
@@ -229,6 +254,8 @@ def test_ray_queries_into_a_hazard_scene(pkg, api, orc, contexts, case):
             got = tr.query_closest(abi.make_rays(o, d))
             assert np.array_equal(got["object"] >= 0, hit), what + ": rt_query_closest: object >= 0 exactly where the oracle hits"
             _assert_fields(got, want, ("dst", "normal", "pos", "hit"), what + ": rt_query_closest")
+            if case.kind in ("triangle", "mesh"):
+                _assert_named(pkg, orc, rig, o, d, hits10, got["object"], got["triangle"], what + ": rt_query_closest")
             dbg = tr.debug_intersect(o, d)
             ok = _same(dbg, hits10)
             ok[~hit, 3:] = True   # (a miss: didHit, isBackface and dst are the contract)
@@ -382,3 +409,195 @@ def test_one_context_through_hazards_and_back(pkg, api, orc, contexts):
                 assert gd == ((1, 1, 1) if expect_on else (0, 0, 0)), f"{what}: rt_debug_primary_table / _tile_cand / _tile_tri = {gd}"
         if stats:
             assert tr.phase_profile()["filter_violations"][0] == 0
+
+
+# ---- the triangle values ----------------------------------------------------------------------------------------------------------------
+
+def _boundary_rays(rig, t):
+    """rays from the camera origin and from 3 other origins to every corner, every edge midpoint and the centroid of the 16 most seen
+    triangles: where tri_test's u, v, w >= 0 tests sit at 0.  The points are computed in fp32 from the uploaded records and taken to
+    world space with the record's own localToWorld; in order, then reversed.  -> (origins, directions), fp32"""
+    pts = []
+    with np.errstate(all="ignore"):
+        for mi, ti, _ in t.most_seen[:16]:
+            T = rig.triangles[ti]
+            a, b, c = (T[p].astype(F) for p in hz.POS)
+            local = [a, b, c, (a + b) * F(0.5), (b + c) * F(0.5), (c + a) * F(0.5), (a + b + c) / F(3)]
+            pts.append(hz._mul_point(rig.models["localToWorld"][mi], np.stack(local), 1))
+        pts = np.concatenate(pts).astype(F)
+        cam = np.array(list(rig.p.camLocalToWorld), dtype=F)[12:15]
+        centre = pts.mean(axis=0, dtype=F)
+        # beside and above the camera, and the camera mirrored through the middle of the points (their back faces)
+        origins = [cam, cam + np.array([0.9, 0.4, 0.0], dtype=F), cam + np.array([-0.6, 0.8, 0.3], dtype=F), centre + (centre - cam)]
+        o = np.concatenate([np.broadcast_to(q, pts.shape) for q in origins]).astype(F)
+        d = np.concatenate([pts - q for q in origins]).astype(F)
+        d = (d / np.sqrt((d * d).sum(axis=1, keepdims=True), dtype=F)).astype(F)
+    o, d = np.concatenate([o, o[::-1]]), np.concatenate([d, d[::-1]])
+    return np.ascontiguousarray(o), np.ascontiguousarray(d)
+
+
+@pytest.mark.parametrize("base", ("bvh", "many"))
+@pytest.mark.parametrize("name", (None, "tri-coincident"), ids=("unplanted", "tri-coincident"))
+def test_rays_at_the_corners_and_edges_of_the_most_seen_triangles(pkg, api, orc, contexts, base, name):
+    """rt_query_closest and rt_debug_intersect on rays aimed at the boundaries of tri_test's >= 0 tests: every field == oracle_ray_collision,
+    and (object, triangle) one the oracle's hit can be.  A ray through an edge two triangles share, and every hit on a coincident pair, is
+    a tie that the walk order and the strict < decide: the normal and the backface bit say which of the two won."""
+    abi = pkg.abi
+    case = hz.BY_NAME[name] if name else None
+    t = hz.aim(pkg, base)
+    rig, tr, ot = _side_setup(pkg, api, orc, contexts, base, case)
+    try:
+        o, d = _boundary_rays(hz.Rig(pkg, api, base), t)   # aimed at the unplanted records: the coincident pairs keep every even triangle
+        assert 800 <= len(o) <= 1200 and np.isfinite(o).all() and np.isfinite(d).all()
+        hits10 = _oracle_hits(orc, ot, o, d)
+        want, hit = _hit_records(abi, abi.RAYHIT_DTYPE, hits10)
+        what = f"{name or 'unplanted'} on {base}, boundary rays"
+        got = tr.query_closest(abi.make_rays(o, d))
+        assert np.array_equal(got["object"] >= 0, hit), what + ": rt_query_closest: object >= 0 exactly where the oracle hits"
+        _assert_fields(got, want, ("dst", "normal", "pos", "hit"), what + ": rt_query_closest")
+        named, ties = _assert_named(pkg, orc, rig, o, d, hits10, got["object"], got["triangle"], what)
+        dbg = tr.debug_intersect(o, d)
+        ok = _same(dbg, hits10)
+        ok[~hit, 3:] = True
+        assert ok.all(), f"{what}: rt_debug_intersect: {int((~ok.all(axis=1)).sum())} rays differ from oracle_ray_collision"
+        back = int((hits10[hit, 1] != 0).sum())
+        print(f"{what}: {len(o)} rays, {int(hit.sum())} hit ({back} a back face), {named} named, {ties} ties")
+        assert hit.sum() >= len(o) // 4 and named >= len(o) // 4 and (ties > 0 or name is None), what
+    finally:
+        ot.close()
+
+
+@pytest.mark.parametrize("base", hz.BASES)
+def test_determinant_exactly_at_the_threshold(pkg, api, orc, contexts, base):
+    """tri_test keeps a triangle with `determinant >= 1E-8f`: a ray whose determinant is the float below 1E-8f, 1E-8f itself and the float
+    above it (hazard_scenes.threshold_rig; tests/test_hazards.py holds the premises) through rt_query_closest, rt_debug_intersect and
+    rt_query_occluded == oracle_ray_collision: a miss of the planted triangle, a hit, a hit.  (`>` for `>=` differs at the middle one alone,
+    and nowhere else in this suite.)"""
+    abi = pkg.abi
+    tr = next(t for name, _, t, stats in contexts if name == "default" and not stats)
+    for which, (s1, s2) in hz.threshold_edges().items():
+        rig, o, d = hz.threshold_rig(pkg, api, base, s1, s2)
+        rig.upload(tr)
+        ot = orc.create_tracer(1)
+        try:
+            hz.threshold_rig(pkg, orc, base, s1, s2)[0].upload(ot)
+            hits10 = _oracle_hits(orc, ot, o, d)
+        finally:
+            ot.close()
+        want, hit = _hit_records(abi, abi.RAYHIT_DTYPE, hits10)
+        what = f"determinant {which} 1E-8f on {base}"
+        near = bool(hit[0]) and abs(float(hits10[0, 2]) - 0.01) < 1e-4
+        assert near == (which != "below"), what
+        got = tr.query_closest(abi.make_rays(o, d))
+        assert np.array_equal(got["object"] >= 0, hit), what
+        _assert_fields(got, want, ("dst", "normal", "pos", "hit"), what + ": rt_query_closest")
+        if near:
+            lo = int(rig.models["triOffset"][0])
+            assert int(got["object"][0]) >= rig.n_spheres and lo <= int(got["triangle"][0]) < lo + int(rig.tri_count[0]), what
+        dbg = tr.debug_intersect(o, d)
+        ok = _same(dbg, hits10)
+        ok[~hit, 3:] = True
+        assert ok.all(), what + ": rt_debug_intersect"
+        occ = tr.query_occluded(abi.make_rays(o, d, np.full(1, 0.02, dtype=F)))
+        assert int(occ[0]) == int(bool(hit[0]) and hits10[0, 2] < F(0.02)) == int(near), what + ": rt_query_occluded within 0.02"
+        print(f"{what}: hit {bool(hit[0])} at {hits10[0, 2]}")
+
+
+@pytest.mark.parametrize("base", hz.LAYOUT_BASES)
+@pytest.mark.parametrize("name", hz.LAYOUT_CASES)
+def test_triangle_values_under_the_layout_that_moves_the_records(pkg, api, orc, name, base):
+    """RT_LAYOUT=pre,arena,cache (read by rt_upload_scene): the triangle records are pre-differenced and moved into the arena; the same
+    frames, counters and audit as under the default layout"""
+    layout = "pre,arena,cache"
+    case = hz.BY_NAME[name]
+    rig = hz.Rig(pkg, api, base, case)
+    used = api.layout_arrays(rig.models, rig.triangles, rig.nodes, layout)["used"]
+    assert "pre" in used.split(",") and "arena" in used.split(","), f"asked for {layout}, the scene is laid out as {used}"
+    with environment({"RT_LAYOUT": layout}):
+        for stats in (False, True):
+            tr = api.create_tracer(0)
+            try:
+                tr.enable_stats(stats)
+                _check(pkg, api, orc, case, base, "RT_LAYOUT=" + layout, {"RT_LAYOUT": layout}, tr, stats)
+            finally:
+                tr.close()
+
+
+def _emissive(case, name):
+    """the case with its triangle model made an opaque emitter"""
+    def scene(pkg_, sc, t_):
+        if case.scene:
+            case.scene(pkg_, sc, t_)
+        m = sc.models[t_.tri_model].material = copy.deepcopy(sc.models[t_.tri_model].material)
+        m.flag, m.emissionCol, m.emissionStrength = 0, (1.0, 0.9, 0.7, 1.0), 5.0
+    return hz.Case(name + "-emitter", case.kind, case.guard, case.tables, scene=scene, triangles=case.triangles)
+
+
+@pytest.mark.parametrize("name", hz.NEE_TRI_CASES)
+def test_nee_with_an_emissive_model_of_planted_triangles(pkg, api, orc, contexts, name):
+    """the light table's area rule (rt_light_table.h: S > 0 and finite, ng finite) on planted triangles: rt_debug_light_table == the numpy
+    table of tests/nee_reference.py bit for bit, rt_nee_light_count, the planted triangles left out exactly where their area (float64
+    from the fp32 world corners, rounded to fp32) is 0 or not finite; rt_nee_trace on every 7th pixel's camera ray == the restated estimator"""
+    abi = pkg.abi
+    for base in hz.SIDE_BASES:
+        t = hz.aim(pkg, base)
+        rig = hz.Rig(pkg, api, base, _emissive(hz.BY_NAME[name], name))
+        tr = next(x for n, _, x, stats in contexts if n == "default" and not stats)
+        rig.upload(tr)
+        what = f"{name} on {base}"
+        want = nr.light_table(abi, rig.models, rig.triangles, rig.spheres)
+        got = api.light_table_arrays(rig.models, rig.triangles, rig.spheres)
+        assert got["entries"].tobytes() == want["entries"].tobytes() and got["cdf"].tobytes() == want["cdf"].tobytes(), what
+        counts = (want["n_sphere_entries"], want["n_triangle_entries"])
+        assert (got["n_sphere_entries"], got["n_triangle_entries"]) == counts and tr.nee_light_count() == counts, what
+        # which triangles of the emissive model are entries: its range without the planted ones
+        obj = rig.n_spheres + t.tri_model
+        lo = int(rig.models["triOffset"][t.tri_model])
+        mine = set(range(lo, lo + int(rig.tri_count[t.tri_model])))
+        planted = mine if name in ("tri-degenerate", "tri-tiny-1e-20") else {t.seen}
+        listed = set(int(k) for k in want["entries"]["triangle"][want["entries"]["object"] == obj])
+        assert listed == mine - planted, f"{what}: entries of the emissive model {sorted(listed)}, planted {sorted(planted)}"
+        assert want["in_table"][obj] == bool(mine - planted), what
+        assert np.isfinite(want["cdf"]).all() and np.isfinite(want["entries"]["prob"]).all() and np.isfinite(want["entries"]["ng"]).all()
+        rig.p.numRaysPerPixel = 1
+        p = rig.params(1)
+        tr.set_params(p)
+        o, d, state = rr.camera_rays(orc, p, rig.w, rig.h, frame=rig.frame0 + 1)
+        rays = abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel())[::7]
+        est = nr.Estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
+        expect = est.trace(rays)
+        out = tr.radiance_trace_nee(rays)
+        ok = _same(out["rgb"], expect["rgb"]).all(axis=1) & (out["rng"] == expect["rng"])
+        print(f"{what}: lights {counts}, {len(listed)} of {len(mine)} triangles of the emissive model listed, {est.samples} samples, "
+              f"{est.shadow_rays} shadow rays, {est.unshadowed} unshadowed")
+        assert ok.all(), f"{what}: rt_nee_trace: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+
+
+MESH = [c for c in hz.CASES if c.kind == "mesh"]
+
+
+@pytest.mark.parametrize("case", MESH, ids=[c.name for c in MESH])
+def test_gpu_builder_on_every_mesh_case(pkg, api, orc, case):
+    """every planted mesh, with the other meshes of its base, through rt_build_bvh_gpu_batch: the host builder's bytes where it builds,
+    its refusal (RT_ERR_SCENE) where it refuses; then a plain mesh again — the device and the builder's scratch pool stay usable"""
+    plain = pkg.meshes.cube()
+    host_plain = api.build_bvh_arrays(plain.vertices, plain.normals, plain.triangles)
+    for base in hz.BASES:
+        rig = hz.Rig(pkg, api, base, case)   # (the host builder)
+        uniq = []
+        for m in rig.meshes:
+            if not any(m is u for u in uniq):
+                uniq.append(m)
+        try:
+            nd, trs, per = api.build_bvh_arrays_gpu_batch([(m.vertices, m.normals, m.triangles) for m in uniq], rig.bvh_quality)
+            outcome = None
+        except pkg.abi.RtError as e:
+            outcome = ("build_bvh", e.status)
+        print(f"{case.name} on {base}: {len(uniq)} meshes, host {rig.refused or 'builds'}, device {outcome or 'builds'}")
+        assert outcome == rig.refused and (rig.refused is None) == case.builds(base), (case.name, base, outcome, rig.refused)
+        if outcome is None:
+            assert nd.tobytes() == rig.nodes.tobytes() and trs.tobytes() == hz.Rig(pkg, orc, base, case).triangles.tobytes(), (case.name, base)
+            assert trs.tobytes() == rig.triangles.tobytes()
+        nd, trs, per = api.build_bvh_arrays_gpu_batch([(plain.vertices, plain.normals, plain.triangles)])
+        assert nd.tobytes() == host_plain[0].tobytes() and trs.tobytes() == host_plain[1].tobytes(), (case.name, base, "a plain mesh afterwards")
+    api.build_bvh_gpu_release()
