@@ -137,6 +137,25 @@ class RtLightTableDump(C.Structure):
         ("entries", C.c_void_p), ("cdf", C.c_void_p)]
 
 
+# ---- rt_mis.h ---------------------------------------------------------------
+MIS_HOST, MIS_DEVICE = 0, 1
+MIS_NO_ENTRY = 0xFFFFFFFF
+
+
+class MisBatch(C.Structure):
+    """include/rt_mis.h: RtMisBatch, the call descriptor of rt_mis_trace (40 bytes; struct_size is the handshake)."""
+    _fields_ = [
+        ("struct_size", C.c_uint32), ("memory", C.c_uint32), ("ctx", C.c_void_p), ("rays", C.c_void_p), ("out", C.c_void_p),
+        ("n", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RtLightMapDump(C.Structure):
+    """include/rt_mis.h: the reverse map of the light table as rt_debug_light_map builds it (freed with rt_debug_light_map_free)."""
+    _fields_ = [
+        ("n_objects", C.c_int32), ("n_triangle_words", C.c_int32), ("n_entries", C.c_int32), ("reserved", C.c_int32),
+        ("objects", C.c_void_p), ("triangles", C.c_void_p)]
+
+
 class RtDenoiseParams(C.Structure):
     """include/rt_denoise.h: the parameters of the a-trous filter (32 bytes; struct_size is the handshake)."""
     _fields_ = [

@@ -38,6 +38,7 @@
 #include "../../include/rt_query.h"
 #include "../../include/rt_radiance.h"
 #include "../../include/rt_nee.h"
+#include "../../include/rt_mis.h"
 
 #include "rt_denoise_launch.h"
 #include "rt_denoise_math.h"
@@ -47,6 +48,7 @@
 #include "rt_query_launch.h"
 #include "rt_radiance_launch.h"
 #include "rt_nee_launch.h"
+#include "rt_mis_launch.h"
 #include "rt_light_table.h"
 #include "rt_layout.h"
 #include "rt_launch_order.h"
@@ -85,7 +87,7 @@ struct SidePass {
     const char* whose;
     const char* what;
 };
-enum { SIDE_AOV, SIDE_QUERY, SIDE_RADIANCE, SIDE_NEE, SIDE_COUNT };
+enum { SIDE_AOV, SIDE_QUERY, SIDE_RADIANCE, SIDE_NEE, SIDE_MIS, SIDE_COUNT };
 
 struct RtContext {
     int device = 0;
@@ -234,6 +236,7 @@ struct RtContext {
         {nullptr, false, "the pass of an rt_query_closest_buffers or rt_query_occluded_buffers call", "records or answers"},
         {nullptr, false, "the pass of an rt_radiance_trace_buffers call", "records"},
         {nullptr, false, "the pass of an rt_nee_trace_buffers call", "records"},
+        {nullptr, false, "the pass of a device-form rt_mis_trace call", "records"},
     };
     /* rt_nee (include/rt_nee.h): the light table.  hCorners: the local-space corners of the uploaded triangles, nine floats each, kept
      * because rt_update_models can turn any model into an emitter.  The table is rebuilt from the host mirrors by the first call of
@@ -245,6 +248,10 @@ struct RtContext {
     rt_nee::TableBytes lightLayout;
     void* dLightTable = nullptr;
     size_t lightTableBytes = 0;
+    /* rt_mis (include/rt_mis.h): the reverse map of that table, from a hit to its entry — an allocation of its own (rt_mis_launch.h,
+     * map_bytes: the objects' records, the triangle words behind them), rebuilt and uploaded with the table, on the same stream and behind the same passes */
+    void* dLightMap = nullptr;
+    size_t lightMapBytes = 0;
     /* rt_render_aov (include/rt_aov.h): the host variant's device records, kept between calls (grows on demand) */
     void* dAovOut = nullptr;
     size_t aovOutBytes = 0;
@@ -634,6 +641,7 @@ void rt_destroy(RtContext* ctx)
     hipFree(ctx->dRayOut);
     for (SidePass& sp : ctx->side) hipFree(sp.words);
     hipFree(ctx->dLightTable);
+    hipFree(ctx->dLightMap);
     hipFree(ctx->dDnScratch);
     hipFree(ctx->dDnAov);
     hipFree(ctx->dMoments);
@@ -2500,6 +2508,24 @@ static int nee_refresh_table(RtContext* ctx, const char* call)
     if ((rc = upload(tb.entries, t.entries.data(), t.entries.size() * sizeof(RtLightEntry)))) return rc;
     if ((rc = upload(tb.cdf, t.cdf.data(), t.cdf.size() * sizeof(float)))) return rc;
     if ((rc = upload(tb.flags, t.inTable.data(), t.inTable.size() * sizeof(uint32_t)))) return rc;
+    {   /* the reverse map of this table (include/rt_mis.h), behind it on the same stream */
+        std::vector<uint32_t> words;
+        rt_mis::MapBytes mb;
+        try {
+            rt_lt::LightMap map;
+            rt_lt::build_map(t, ctx->hModels.data(), ctx->nModels, ctx->nTris, ctx->nSpheres, map);
+            mb = rt_mis::map_bytes(map.objects.size(), map.triangles.size());
+            rt_mis::pack_map(map, words);
+        } catch (const std::bad_alloc&) {
+            return fail(ctx, RT_ERR_OOM, "%s: out of host memory building the light map", call);
+        }
+        if ((rc = grow_scratch(ctx, &ctx->dLightMap, &ctx->lightMapBytes, mb.total))) return rc;
+        const size_t bytes = words.size() * sizeof(uint32_t);
+        for (size_t done = 0; done < bytes; done += rt_nee::UPLOAD_CHUNK_BYTES) {
+            const size_t piece = bytes - done < rt_nee::UPLOAD_CHUNK_BYTES ? bytes - done : (size_t)rt_nee::UPLOAD_CHUNK_BYTES;
+            if ((rc = stage_upload(ctx, (char*)ctx->dLightMap + done, (const char*)words.data() + done, piece))) return rc;
+        }
+    }
     ctx->lightLayout = tb;
     ctx->lightSpheres = t.nSphere;
     ctx->lightTriangles = t.nTriangle;
@@ -2525,6 +2551,22 @@ static int nee_enqueue(RtContext* ctx, const char* call, const void* dRays, int 
 static int nee_enqueue_host(RtContext* ctx, const void* dRays, int n, void* dOut) { return nee_enqueue(ctx, "rt_nee_trace", dRays, n, dOut); }
 static int nee_enqueue_buffers(RtContext* ctx, const void* dRays, int n, void* dOut) { return nee_enqueue(ctx, "rt_nee_trace_buffers", dRays, n, dOut); }
 
+/* The side pass of rt_mis_trace (include/rt_mis.h): the MIS instantiation of rt_radiance_nee_kernel, whose table carries the reverse
+ * map in the place of the per-object flags. */
+static int mis_enqueue(RtContext* ctx, const void* dRays, int n, void* dOut)
+{
+    if (int rc = nee_refresh_table(ctx, "rt_mis_trace")) return rc;
+    void (*kern)(const KArgs, const float4*, int, float4*, const rtk::NeeTable, const uint32_t*) = RT_SCENE_KERNEL(ctx, rtk::rt_radiance_nee_kernel, true);
+    const char* const d = (const char*)ctx->dLightTable;
+    rtk::NeeTable lt;
+    lt.entries = (const float4*)(d + ctx->lightLayout.entries);
+    lt.cdf = (const float*)(d + ctx->lightLayout.cdf);
+    lt.inTable = (const uint32_t*)ctx->dLightMap; /* (rt_mis_launch.h: the objects' records, the triangle words behind them) */
+    lt.n = ctx->lightSpheres + ctx->lightTriangles;
+    return path_enqueue(ctx, SIDE_MIS, RT_SUSPEND_NUM /* (unused: both walks of the pass run to completion) */, n, kern, (const float4*)dRays, n, (float4*)dOut, lt,
+                        (const uint32_t*)ctx->dUnitTri);
+}
+
 /* ---- the host form and the buffer form of the eight ray-batch calls ----------------------------------------------------------------------
  * What tells the three kinds of batch apart: the pass and its enqueue function, the size of a ray's output, the buffer form's name for
  * the output pointer, the host form's word for the output, and whether the pass reads the parameters. */
@@ -2541,6 +2583,7 @@ static const RayBatch kOccluded = {SIDE_QUERY, occluded_enqueue, sizeof(uint32_t
 static const RayBatch kRadiance = {SIDE_RADIANCE, radiance_enqueue, sizeof(RtRadiance), "d_out", "records", true};
 static const RayBatch kNee = {SIDE_NEE, nee_enqueue_host, sizeof(RtRadiance), "d_out", "records", true}; /* (two rows: a table error names the call it came from) */
 static const RayBatch kNeeBuffers = {SIDE_NEE, nee_enqueue_buffers, sizeof(RtRadiance), "d_out", "records", true};
+static const RayBatch kMis = {SIDE_MIS, mis_enqueue, sizeof(RtRadiance), "out", "records", true};
 
 /* what the calls check before they touch the device; *rayBytes and *outBytes: the sizes of the batch (rt_rd::check_batch is
  * rt_qr::check_batch with an RtRadiance per ray) */
@@ -2626,6 +2669,58 @@ int rt_debug_light_table(const RtModel* models, int n_models, const RtTriangle* 
 }
 
 void rt_debug_light_table_free(RtLightTableDump* d) { rt_lt::dump_free(d); }
+
+/* include/rt_mis.h: the descriptor first — nothing is touched before it is known to be this library's — then the host or the device
+ * form of the ray-batch calls above */
+int rt_mis_trace(const RtMisBatch* batch)
+{
+    if (!batch) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_mis_trace: null descriptor");
+    if (batch->struct_size != sizeof(RtMisBatch)) /* (a foreign layout: nothing else of it is read) */
+        return fail(nullptr, RT_ERR_INVALID_ARG, "rt_mis_trace: struct_size is %u, this library's RtMisBatch has %zu bytes", batch->struct_size, sizeof(RtMisBatch));
+    RtContext* const ctx = batch->ctx; /* (null: the text goes to the global message) */
+    if (batch->reserved != 0) return fail(ctx, RT_ERR_INVALID_ARG, "rt_mis_trace: reserved must be 0");
+    if (batch->memory > RT_MIS_DEVICE) return fail(ctx, RT_ERR_INVALID_ARG, "rt_mis_trace: memory is %u: RT_MIS_HOST (0) or RT_MIS_DEVICE (1)", batch->memory);
+    if (!ctx) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_mis_trace: null context");
+    if (batch->memory == RT_MIS_DEVICE) return rays_to_device(ctx, "rt_mis_trace", kMis, batch->rays, batch->n, batch->out);
+    return rays_to_host(ctx, "rt_mis_trace", kMis, batch->rays, batch->n, batch->out);
+}
+
+int rt_debug_light_map(const RtModel* models, int n_models, const RtTriangle* triangles, int n_triangles, const RtSphere* spheres, int n_spheres, RtLightMapDump* out)
+{
+    if (!out) return fail(nullptr, RT_ERR_INVALID_ARG, "rt_debug_light_map: null output");
+    memset(out, 0, sizeof(*out));
+    const char* why = "";
+    try {
+        rt_lt::LightTable t;
+        if (const int rc = rt_lt::build(models, n_models, reinterpret_cast<const float*>(triangles), sizeof(RtTriangle) / sizeof(float), n_triangles, spheres, n_spheres, t, &why))
+            return fail(nullptr, rc, "rt_debug_light_map: %s", why);
+        rt_lt::LightMap map;
+        rt_lt::build_map(t, models, n_models, n_triangles, n_spheres, map);
+        out->objects = (uint32_t*)malloc(map.objects.size() ? map.objects.size() * sizeof(uint32_t) : 1);
+        out->triangles = (uint32_t*)malloc(map.triangles.size() ? map.triangles.size() * sizeof(uint32_t) : 1);
+        if (!out->objects || !out->triangles) {
+            rt_debug_light_map_free(out);
+            return fail(nullptr, RT_ERR_OOM, "rt_debug_light_map: out of host memory");
+        }
+        if (!map.objects.empty()) memcpy(out->objects, map.objects.data(), map.objects.size() * sizeof(uint32_t));
+        if (!map.triangles.empty()) memcpy(out->triangles, map.triangles.data(), map.triangles.size() * sizeof(uint32_t));
+        out->n_objects = (int32_t)map.objects.size();
+        out->n_triangle_words = (int32_t)map.triangles.size();
+        out->n_entries = (int32_t)t.entries.size();
+    } catch (const std::bad_alloc&) {
+        rt_debug_light_map_free(out);
+        return fail(nullptr, RT_ERR_OOM, "rt_debug_light_map: out of host memory");
+    }
+    return RT_OK;
+}
+
+void rt_debug_light_map_free(RtLightMapDump* d)
+{
+    if (!d) return;
+    free(d->objects);
+    free(d->triangles);
+    memset(d, 0, sizeof(*d));
+}
 
 /* ---- rt_denoise_buffers / rt_denoise / rt_denoise_to_device (include/rt_denoise.h) --------------------------------------------
  * The kernels are rt_denoise.hip's (rt_dn::enqueue); here are the argument checks, the scratch and the order on the joined main

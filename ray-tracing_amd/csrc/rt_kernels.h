@@ -36,6 +36,7 @@
 #include "rt_device.h"
 #include "rt_tile_cand.h"
 #include "rt_nee_launch.h"
+#include "rt_mis_launch.h"
 
 /* Tuning knobs (values measured on MI355X). */
 /* traverse() is left once active <= entered * NUM/DEN lanes are still traversing */
@@ -1894,6 +1895,99 @@ __device__ __forceinline__ bool nee_sample(const NeeTable& lt, uint32_t* rng, co
     return true;
 }
 
+/* rt_mis_trace (include/rt_mis.h): the same paths with the light sample and the emission of the next hit weighted against each other by
+ * the balance heuristic — the MIS instantiations of rt_radiance_nee_kernel below.  The header defines every operation; these are its
+ * three pieces. */
+/* g and wb of the header: pa / (pa + pb), and `otherwise` where that is not within [0, 1] (a NaN) */
+__device__ __forceinline__ float mis_balance(const float pa, const float pb, const float otherwise)
+{
+    const float w = rt_div(pa, pa + pb);
+    return (w >= 0.0f && w <= 1.0f) ? w : otherwise;
+}
+
+/* The light sample for one lane: nee_sample's draws, entry, direction and "nothing is added" rules, line for line (written beside it,
+ * not shared with it: the NEE kernels' code objects stay what they were), and the header's g in the place of rt_nee.h's. */
+__device__ __forceinline__ bool mis_sample(const NeeTable& lt, uint32_t* rng, const rt_f3 x, const rt_f3 n, rt_f3& omega, float& g, rt_f3& Le, int& obj, int& tri)
+{
+    const float u0 = rt_random_value(rng);
+    const float u1 = rt_random_value(rng);
+    const float u2 = rt_random_value(rng);
+    const int li = rt_nee::pick(lt.cdf, lt.n, u0); /* (rt_nee_launch.h: bounded, clamped to the table) */
+    const float4* const e = lt.entries + 5 * (size_t)li; /* li < n: inside the n * 80 bytes the host made */
+    const float4 q0 = e[0], q1 = e[1], q2 = e[2], q3 = e[3], q4 = e[4];
+    const float prob = q1.w;
+    obj = (int)__float_as_uint(q2.w);
+    tri = (int)__float_as_uint(q3.w);
+    Le = rt_v3(q4.x, q4.y, q4.z);
+    omega = rt_v3s(0.0f);
+    g = 0.0f;
+    if (tri < 0) { /* a sphere: uniform in the cone it subtends */
+        const rt_f3 w = rt_v3(q0.x, q0.y, q0.z) - x;
+        const float d2 = rt_dot(w, w);
+        const float r2 = q0.w;
+        if (!(d2 > r2)) return false;
+        const float s2 = rt_div(r2, d2);
+        const float cmax = rt_sqrt(1.0f - s2);
+        const float q = rt_div(s2, 1.0f + cmax);
+        const float ct = 1.0f - u1 * q;
+        const float st = rt_sqrt(rt_max(0.0f, 1.0f - ct * ct));
+        float sn, cs;
+        rtd_sincos(2 * 3.1415926f * u2, &sn, &cs);
+        const rt_f3 z = rt_normalize(w);
+        const float sg = rt_u2f(0x3f800000u | (rt_f2u(z.z) & 0x80000000u));
+        const float a = -rt_rcp(sg + z.z);
+        const float b = z.x * z.y * a;
+        const rt_f3 b1 = rt_v3(1.0f + sg * z.x * z.x * a, sg * b, -sg * z.x);
+        const rt_f3 b2 = rt_v3(b, sg + z.y * z.y * a, -z.y);
+        omega = b1 * (st * cs) + b2 * (st * sn) + z * ct;
+        const float cn = rt_dot(n, omega);
+        if (!(cn > 0.0f)) return false;
+        g = mis_balance(rt_div(cn, 3.1415926f), rt_div(prob, 2 * 3.1415926f * q), 0.0f);
+        return true;
+    }
+    /* a triangle: uniform on it by the fold map */
+    const bool fold = u1 + u2 > 1.0f;
+    const float v1 = fold ? 1.0f - u1 : u1, v2 = fold ? 1.0f - u2 : u2;
+    const rt_f3 y = rt_v3(q0.x, q0.y, q0.z) + rt_v3(q1.x, q1.y, q1.z) * v1 + rt_v3(q2.x, q2.y, q2.z) * v2;
+    const rt_f3 v = y - x;
+    const float d2 = rt_dot(v, v);
+    omega = rt_normalize(v);
+    const float cl = rt_dot(rt_v3(q3.x, q3.y, q3.z), -omega);
+    const float cn = rt_dot(n, omega);
+    if (!(cl > 0.0f && cn > 0.0f)) return false;
+    g = mis_balance(rt_div(cn, 3.1415926f), rt_div(prob * d2, cl * q0.w), 0.0f);
+    return true;
+}
+
+/* wb of the header for a hit on entry e of the table (a sphere's or a triangle's, as the hit says), behind a vertex that took a sample
+ * with cn' = cnPrev > 0: x and dir are the segment's origin and direction, hpos the hit.  Only the words of the entry that the rule
+ * reads are loaded (RtLightEntry's layout, include/rt_nee.h). */
+__device__ __forceinline__ float mis_emission_weight(const NeeTable& lt, const uint32_t e, const bool sphere, const float cnPrev, const rt_f3 x, const rt_f3 dir, const rt_f3 hpos)
+{
+    const float pbPrev = rt_div(cnPrev, 3.1415926f);
+    const float* const q = reinterpret_cast<const float*>(lt.entries + 5 * (size_t)e); /* e < n: the caller checks */
+    const float prob = q[7];
+    float pl;
+    if (sphere) {
+        const float4 q0 = lt.entries[5 * (size_t)e];
+        const rt_f3 w = rt_v3(q0.x, q0.y, q0.z) - x;
+        const float d2 = rt_dot(w, w);
+        const float r2 = q0.w;
+        if (!(d2 > r2)) return 1.0f;
+        const float s2 = rt_div(r2, d2);
+        const float cmax = rt_sqrt(1.0f - s2);
+        const float qq = rt_div(s2, 1.0f + cmax);
+        pl = rt_div(prob, 2 * 3.1415926f * qq);
+    } else {
+        const rt_f3 v = hpos - x;
+        const float d2 = rt_dot(v, v);
+        const float cl = rt_dot(rt_v3(q[12], q[13], q[14]), -dir);
+        if (!(cl > 0.0f)) return 1.0f;
+        pl = rt_div(prob * d2, cl * q[3]);
+    }
+    return mis_balance(pbPrev, pl, 1.0f);
+}
+
 /* One path per lane, blocks of 64 consecutive rays, the refill of idle lanes and the block counter are rt_radiance_kernel's (whose
  * comment describes them): the same rt_ray_feed.inl; LDS the same wave region (rt_plan::wave_lds_bytes).  A wave iteration is: the path
  * segments' walk, the shade block — rt_shade_block.inl, the text the frame kernels run, with the three amendments in its three hooks —
@@ -1901,8 +1995,15 @@ __device__ __forceinline__ bool nee_sample(const NeeTable& lt, uint32_t* rng, co
  * EVERY lane of the wave inside: a lane without a path, or without a shadow ray, carries the null ray and is parked (walk_all states
  * the rule).  The roulette draw follows the sample's three draws at once — it does not depend on the shadow ray — and only the
  * sample's light waits for the walk.
- * Written besides `out`: a.counters + 7 (the watchdog word of traverse()) and the block counter a.tileQueue, both words of this pass's own. */
-template <bool FLAT, bool MANY>
+ * Written besides `out`: a.counters + 7 (the watchdog word of traverse()) and the block counter a.tileQueue, both words of this pass's own.
+ * MIS: the pass of rt_mis_trace (include/rt_mis.h) — the same wave iteration with that header's rules in the three hooks, so that the
+ * block has one direct includer.  A vertex samples only while the path could go on behind it (the MANY variant keeps its bounce count
+ * in the LDS word the shade block increments); it remembers cn', the cosine of the direction it took (cnPrev: one register, 0 where no
+ * sample was taken — wb is 1 unless cn' > 0, and emission times 1.0f is emission in full, bit for bit, so the one value says both);
+ * and the emission of the next hit is weighted, not left out.  lt.inTable then points at the reverse map (rt_mis_launch.h: four
+ * words per object, behind them the triangle words): the lookup is two dependent loads, issued — like the entry's loads — only by
+ * lanes that hit a table object behind a sampled vertex.  With MIS false every `if constexpr (MIS)` below is discarded. */
+template <bool FLAT, bool MANY, bool MIS = false>
 __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : MANY ? RT_MIN_WAVES_PER_SIMD_MANY : RT_MIN_WAVES_PER_SIMD) rt_radiance_nee_kernel(const KArgs a, const float4* __restrict__ rays, const int n, float4* __restrict__ out, const NeeTable lt, const uint32_t* __restrict__ unitTri)
 {
     extern __shared__ uint32_t s_lds[];
@@ -1920,6 +2021,7 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     uint32_t rng = 0;
     bool pathActive = false;  /* the lane holds a path */
     bool prevSampled = false; /* the path's previous vertex was a diffuse vertex at which an emitter was sampled (amendment 3) */
+    float cnPrev = 0.0f;      /* MIS: cn' of that vertex, 0 where it took no sample */
     int bounce = 0, rayIndex = 0;
     rt_f3 rpos = rt_v3s(0.0f), rdir = rt_v3s(0.0f), transmittance = rt_v3s(0.0f), pathLight = rt_v3s(0.0f);
     Stats st = {};
@@ -1927,7 +2029,7 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
     for (;;) {
 #define RT_FEED_ROUND
 #define RT_FEED_ARGS a
-#define RT_FEED_START(i) rayIndex = (i); prevSampled = false;
+#define RT_FEED_START(i) rayIndex = (i); prevSampled = false; cnPrev = 0.0f;
 #include "rt_ray_feed.inl"
 #undef RT_FEED_ROUND
 #undef RT_FEED_ARGS
@@ -1961,20 +2063,38 @@ __global__ void __launch_bounds__(RT_WAVE, FLAT ? RT_MIN_WAVES_PER_SIMD_FLAT : M
             bool sample = false; /* this vertex is a diffuse vertex at which an emitter is sampled (amendment 2) */
 /* amendment 3: the previous vertex's sample stood for this emission, unless it could not (no entry; a sphere from inside);
  * h.obj < nSpheres + nModels: inside the table's flags */
-#define RT_SHADE_EMIT(e) \
-    if (!(prevSampled && lt.inTable[h.obj] != 0u && !(h.obj < a.nSpheres && h.backface))) pathLight = pathLight + (e)
-#define RT_SHADE_OPAQUE_END sample = lt.n > 0 && lerpT == 0.0f; /* amendment 2: a diffuse vertex */
+/* MIS: the emission in full, or times wb where the previous vertex's sample could have found this entry; rpos and rdir are still the
+ * segment's, and h.obj < nSpheres + nModels: inside the map's records */
+#define RT_SHADE_EMIT(e)                                                                                                                       \
+    if constexpr (MIS) {                                                                                                                       \
+        float wb = 1.0f;                                                                                                                       \
+        const bool sphere = h.obj < a.nSpheres;                                                                                                \
+        if (cnPrev > 0.0f && !(sphere && h.backface)) {                                                                                        \
+            const uint32_t le = rt_mis::entry_of(lt.inTable, lt.inTable + (size_t)rt_mis::OBJECT_WORDS * (size_t)(a.nSpheres + a.nModels), h.obj, sphere, \
+                                                 sphere ? -1 : hit_triangle(h, unitTri));                                                      \
+            if (le < (uint32_t)lt.n) wb = mis_emission_weight(lt, le, sphere, cnPrev, rpos, rdir, hpos);                                       \
+        }                                                                                                                                      \
+        pathLight = pathLight + (e) * wb;                                                                                                      \
+    } else if (!(prevSampled && lt.inTable[h.obj] != 0u && !(h.obj < a.nSpheres && h.backface))) pathLight = pathLight + (e)
+/* amendment 2: a diffuse vertex; MIS: behind which the path could still continue */
+#define RT_SHADE_OPAQUE_END                                                                                    \
+    sample = lt.n > 0 && lerpT == 0.0f;                                                                        \
+    if constexpr (MIS) sample = sample && (MANY ? (int)extBase[(1 + a.extWords) * RT_WAVE] : bounce) < a.maxBounce;
 /* amendment 2: the three draws, ahead of the roulette draw; the sample's light waits for the shadow walk */
-#define RT_SHADE_NEXT_RAY                                                          \
-    prevSampled = sample;                                                          \
-    if (sample) {                                                                  \
-        rt_f3 Le;                                                                  \
-        float g;                                                                   \
-        if (nee_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri)) {   \
-            shadow = true;                                                         \
-            spos = rpos;                                                           \
-            sampled = (transmittance * Le) * g;                                    \
-        }                                                                          \
+#define RT_SHADE_NEXT_RAY                                                                \
+    prevSampled = sample;                                                                \
+    if constexpr (MIS) cnPrev = sample ? rt_dot(normal, rdir) : 0.0f;                    \
+    if (sample) {                                                                        \
+        rt_f3 Le;                                                                        \
+        float g;                                                                         \
+        bool want;                                                                       \
+        if constexpr (MIS) want = mis_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri); \
+        else want = nee_sample(lt, &rng, rpos, normal, sdir, g, Le, wantObj, wantTri);   \
+        if (want) {                                                                      \
+            shadow = true;                                                               \
+            spos = rpos;                                                                 \
+            sampled = (transmittance * Le) * g;                                          \
+        }                                                                                \
     }
 #include "rt_shade_block.inl"
 #undef RT_SHADE_EMIT

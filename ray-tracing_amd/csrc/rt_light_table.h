@@ -163,6 +163,46 @@ inline int build(const RtModel* models, int nModels, const float* corners, size_
     return RT_OK;
 }
 
+/* The reverse map of include/rt_mis.h: from a hit (object, triangle) to the index of its entry in `t`, NO_ENTRY (0xffffffff) where it
+ * has none.  objects: one word per object — a sphere's entry, or the index into `triangles` of the word of a model's first triangle.
+ * triangles: for every model with an entry, one word per triangle of its range [triOffset, end), in model order; triCount[o] is that
+ * range's length (0 for a sphere or a model without an entry).  `t` must be build()'s table of the same arrays. */
+struct LightMap {
+    enum : uint32_t { NO_ENTRY = 0xffffffffu };
+    std::vector<uint32_t> objects, triOffset, triCount, triangles;
+};
+
+inline void build_map(const LightTable& t, const RtModel* models, int nModels, int nTris, int nSpheres, LightMap& map)
+{
+    const size_t nObjects = (size_t)nSpheres + (size_t)nModels;
+    map.objects.assign(nObjects, (uint32_t)LightMap::NO_ENTRY);
+    map.triOffset.assign(nObjects, 0u);
+    map.triCount.assign(nObjects, 0u);
+    map.triangles.clear();
+    std::vector<int> end;
+    triangle_ends(models, nModels, nTris, end);
+    size_t words = 0;
+    for (int m = 0; m < nModels; m++) {
+        const size_t o = (size_t)nSpheres + m;
+        if (o >= t.inTable.size() || !t.inTable[o]) continue;
+        map.objects[o] = (uint32_t)words;
+        map.triOffset[o] = (uint32_t)models[m].triOffset;
+        map.triCount[o] = (uint32_t)(end[m] - models[m].triOffset);
+        words += map.triCount[o];
+    }
+    map.triangles.assign(words, (uint32_t)LightMap::NO_ENTRY);
+    for (size_t i = 0; i < t.entries.size(); i++) {
+        const RtLightEntry& e = t.entries[i];
+        if (e.object < 0 || (size_t)e.object >= nObjects) continue;
+        if (e.triangle < 0) {
+            map.objects[e.object] = (uint32_t)i;
+            continue;
+        }
+        const uint32_t rel = (uint32_t)e.triangle - map.triOffset[e.object];
+        if (map.objects[e.object] != LightMap::NO_ENTRY && rel < map.triCount[e.object]) map.triangles[(size_t)map.objects[e.object] + rel] = (uint32_t)i;
+    }
+}
+
 /* rt_debug_light_table / rt_debug_light_table_free without the error text */
 inline int dump(const RtModel* models, int nModels, const RtTriangle* triangles, int nTris, const RtSphere* spheres, int nSpheres, RtLightTableDump* out, const char** why)
 {

@@ -62,6 +62,8 @@ QUERY_SYMBOLS = ["rt_query_closest", "rt_query_closest_buffers", "rt_query_occlu
 RADIANCE_SYMBOLS = ["rt_radiance_trace", "rt_radiance_trace_buffers"]
 # every symbol include/rt_nee.h declares
 NEE_SYMBOLS = ["rt_nee_trace", "rt_nee_trace_buffers", "rt_nee_light_count", "rt_debug_light_table", "rt_debug_light_table_free"]
+# every symbol include/rt_mis.h declares
+MIS_SYMBOLS = ["rt_mis_trace", "rt_debug_light_map", "rt_debug_light_map_free"]
 # RtPixelCost (include/rt_cost.h): the eight uint32 columns of HipTracer.render_cost, in order
 COST_FIELDS = ("segments", "innerSteps", "leafSteps", "triTests", "primaryInnerSteps", "primaryLeafSteps", "primaryTriTests", "firstHit")
 
@@ -164,6 +166,9 @@ class HipApi(abi.CApi):
         "nee_light_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "debug_light_table": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(abi.RtLightTableDump)]),
         "debug_light_table_free": (None, [C.POINTER(abi.RtLightTableDump)]),
+        "mis_trace": (C.c_int, [C.POINTER(abi.MisBatch)]),
+        "debug_light_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(abi.RtLightMapDump)]),
+        "debug_light_map_free": (None, [C.POINTER(abi.RtLightMapDump)]),
     }
 
     def __init__(self, path=LIB_PATH):
@@ -208,6 +213,23 @@ class HipApi(abi.CApi):
             return {"entries": entries, "cdf": cdf, "n_sphere_entries": int(d.n_sphere_entries), "n_triangle_entries": int(d.n_triangle_entries)}
         finally:
             self.debug_light_table_free(C.byref(d))
+
+    def light_map_arrays(self, models, triangles, spheres=None):
+        """rt_debug_light_map (include/rt_mis.h): the reverse map of the light table of these arrays (no device needed), as numpy
+        copies: {objects (uint32 per object), triangles (uint32 words), n_entries}; abi.MIS_NO_ENTRY = no entry."""
+        m, nm = abi._ptr(models, abi.model_dtype)
+        t, nt = abi._ptr(triangles, abi.triangle_dtype)
+        sp, ns = abi._ptr(spheres, abi.sphere_dtype)
+        d = abi.RtLightMapDump()
+        rc = self.debug_light_map(m.ctypes.data if nm else None, nm, t.ctypes.data if nt else None, nt, sp.ctypes.data if ns else None, ns, C.byref(d))
+        if rc != abi.RT_OK:
+            raise abi.RtError(rc, (self.last_error(None) or b"").decode(errors="replace"))
+        try:
+            def words(ptr, n):
+                return np.frombuffer((C.c_char * (n * 4)).from_address(ptr), dtype=np.uint32).copy() if n else np.zeros(0, dtype=np.uint32)
+            return {"objects": words(d.objects, d.n_objects), "triangles": words(d.triangles, d.n_triangle_words), "n_entries": int(d.n_entries)}
+        finally:
+            self.debug_light_map_free(C.byref(d))
 
     def layout_arrays(self, models, triangles, nodes, layout=None):
         """rt_debug_layout: the device-memory layout rt_upload_scene would produce (no device needed), as numpy copies:
@@ -703,6 +725,26 @@ class HipTracer(abi.Tracer):
     def radiance_trace_nee_buffers(self, rays_ptr, n, out_ptr):
         """rt_nee_trace_buffers: the same on device memory, enqueued like radiance_trace_buffers."""
         self._check(self.api.nee_trace_buffers(self.h, rays_ptr, int(n), out_ptr))
+
+    def _mis_batch(self, memory, rays_ptr, n, out_ptr):
+        b = abi.MisBatch()
+        b.struct_size, b.memory, b.ctx, b.rays, b.out, b.n, b.reserved = C.sizeof(abi.MisBatch), memory, self.h, rays_ptr, out_ptr, int(n), 0
+        return b
+
+    def radiance_trace_mis(self, rays):
+        """rt_mis_trace, host form (include/rt_mis.h): radiance_trace with one emitter sampled directly at every diffuse vertex that
+        has a bounce left, combined with the cosine lobe by the balance heuristic — the same records, radiance_trace's expectation
+        at every maxBounceCount, and every contribution at most T * Le.  Changes no state of the context."""
+        r = np.ascontiguousarray(rays, dtype=abi.PATHRAY_DTYPE).reshape(-1)
+        out = np.zeros(len(r), dtype=abi.RADIANCE_DTYPE)
+        b = self._mis_batch(abi.MIS_HOST, r.ctypes.data if len(r) else None, len(r), out.ctypes.data if len(r) else None)
+        self._check(self.api.mis_trace(C.byref(b)))
+        return out
+
+    def radiance_trace_mis_buffers(self, rays_ptr, n, out_ptr):
+        """rt_mis_trace, device form: the same on device memory, enqueued like radiance_trace_buffers."""
+        b = self._mis_batch(abi.MIS_DEVICE, rays_ptr, n, out_ptr)
+        self._check(self.api.mis_trace(C.byref(b)))
 
     def nee_light_count(self):
         """rt_nee_light_count: (sphere entries, triangle entries) of the light table as the next radiance_trace_nee would use it."""
