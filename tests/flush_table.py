@@ -2,9 +2,10 @@
 
 rt_render_frame holds a frame back while the GPU is still busy: it counts it (ctx->pending, rt_get_frame) and the held frames leave later
 as one fused launch, with the state the context has at that moment.  So every entry point that reads what those frames produce, or changes
-what they depend on, has to launch them first.  ROWS names, for every function declared in include/*.h whose first parameter is an
-RtContext* or an RtMulti* (and the two that create one), which side of that contract it is on and how tests/test_gpu_held_back.py calls it
-with three frames held back (RT_HOLD_BACK=1 forces the hold, rt_debug_pending_frames shows it):
+what they depend on, has to launch them first.  ROWS has a row for every function declared in include/*.h that takes a context: its
+first parameter is an RtContext*, an RtMulti*, or a call descriptor with such a member, as rt_mis_trace's RtMisBatch.  The two functions
+that create a context have rows too.  A row says which side of the contract the function is on and how tests/test_gpu_held_back.py
+calls it with three frames held back (RT_HOLD_BACK=1 forces the hold, rt_debug_pending_frames shows it):
 
     flushes   after the call nothing is pending (rt_debug_pending_frames == 0): the held frames were launched before the call read or
               changed anything
@@ -742,4 +743,8 @@ ROWS = [
     R("rt_nee_trace_buffers", FLUSHES, "96 rays in device memory", c_buffers("radiance_trace_nee_buffers", "path_rays", "RADIANCE_DTYPE"),
       prepare=p_ray_buffers(16)),
     R("rt_nee_light_count", FLUSHES, "read", lambda c: {"lights": c.tr.nee_light_count()}),
+    # ---- include/rt_mis.h: one function, which takes a call descriptor; its two forms are the descriptor's `memory`
+    R("rt_mis_trace", FLUSHES, "96 rays, the host form (memory = RT_MIS_HOST)", lambda c: {"radiance": c.tr.radiance_trace_mis(path_rays(c))}),
+    R("rt_mis_trace", FLUSHES, "96 rays in device memory (memory = RT_MIS_DEVICE)", c_buffers("radiance_trace_mis_buffers", "path_rays", "RADIANCE_DTYPE"),
+      prepare=p_ray_buffers(16), case="device_form"),
 ]

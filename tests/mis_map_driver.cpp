@@ -125,6 +125,8 @@ int main()
     check_scene(9, 0, 0);   /* spheres only */
     check_scene(0, 3, 7);   /* models only */
     check_scene(1, 1, 1);
+    check_scene(0, 40, 1300); /* object indices up to 1,299, as the > 64-model scenes have them: the lookup at rel == triCount - 1 and == triCount of each,
+                                 and zero-area triangles in the middle of a range that has a base (NO_ENTRY words inside it) */
     for (int round = 0; round < 20; round++) check_scene(1 + (int)(rnd() * 20.0f), 1 + (int)(rnd() * 6.0f), 1 + (int)(rnd() * 25.0f));
     {   /* the empty map's bytes */
         const rt_mis::MapBytes mb = rt_mis::map_bytes(0, 0);

@@ -6,7 +6,8 @@ rule, the scenes and Estimator's helpers:
   * the draws and the shader's functions come from the oracle, sqrt / divide / reciprocal / rsqrt / exp / sin / cos from
     oracle_math_eval; everything else is numpy float32, one rounding per operation, in the header's order;
   * per path it logs each light sample (sample_log: g, sphere or triangle, seen or not), each emission behind a sampled vertex
-    (emission_log: wb and the rule that made it what it is) and each last-vertex sample that was skipped (skipped_log).
+    (emission_log: wb and the rule that made it what it is; emission_hits: the object and triangle that was hit) and each last-vertex
+    sample that was skipped (skipped_log).
 
 Test infrastructure: nothing here is imported by the product."""
 import ctypes as C
@@ -71,6 +72,7 @@ class Estimator(nr.Estimator):
         self.entry = light_map(self.table, len(spheres) + len(models))
         self.sample_log = []    # (ray, vertex, g, "sphere" | "triangle", seen) of every sample that reached its shadow walk
         self.emission_log = []  # (ray, vertex, wb, rule, "sphere" | "triangle") of every opaque hit behind a vertex that took a sample
+        self.emission_hits = []  # (object, triangle) of the hit of every row of emission_log, in its order
         self.skipped_log = []   # (ray, vertex) of every diffuse vertex that took no sample because it was the path's last
         self.plain_emission_log = []  # (ray, vertex) of every opaque hit on an emitter whose previous vertex took no sample
 
@@ -221,6 +223,7 @@ class Estimator(nr.Estimator):
                         if prev[i]:
                             wb, rule = self.emission_weight(obj, int(h["triangle"]), backface, cn_prev[i], pos[i].copy(), rdir, hpos)
                             self.emission_log.append((int(i), vertex, float(wb), rule, "sphere" if obj < self.n_spheres else "triangle"))
+                            self.emission_hits.append((obj, int(h["triangle"])))
                             L[i] = L[i] + (emitted * T[i]) * wb
                         else:
                             if self.table["in_table"][obj]:

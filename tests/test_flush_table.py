@@ -1,5 +1,6 @@
 """tests/flush_table.py covers the C ABI: every function of include/*.h that takes a context has exactly one place in the table of the
 hold-back contract, so a new entry point cannot be added without saying whether it launches the frames rt_render_frame holds back.
+A function takes a context as its first parameter, or inside the call descriptor its first parameter points to, as rt_mis_trace does.
 No GPU: the headers are parsed the way tests/test_abi.py parses them."""
 import glob
 import os
@@ -11,17 +12,37 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CONTEXT_TYPES = ("RtContext", "RtMulti")
 
 
+def _blank_comments(text):
+    """comments blanked, not removed: offsets into `text` stay valid for finding the comment above a declaration"""
+    return re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), text, flags=re.S)
+
+
+def descriptor_types(paths):
+    """the structs declared in these headers (`typedef struct [Tag] { ... } Name;`) that have an RtContext* / RtMulti* member: a call
+    descriptor names the context it is for, so a function whose first parameter points to one is a call on that context"""
+    out = set()
+    member = re.compile(r"(?:^|[;{])\s*(?:const\s+)?(?:%s)\s*\*\s*[A-Za-z_0-9]+\s*(?=;)" % "|".join(CONTEXT_TYPES))
+    for path in paths:
+        code = _blank_comments(open(path).read())
+        for m in re.finditer(r"\btypedef\s+struct\s*[A-Za-z_0-9]*\s*\{([^{}]*)\}\s*([A-Za-z_0-9]+)\s*;", code):
+            if member.search(m.group(1)):
+                out.add(m.group(2))
+    return out
+
+
 def declared(headers=None):
     """{function: (header, the comment right above its declaration)} for every function declared in include/*.h whose first parameter is
-    an RtContext* / RtMulti* (const or not), plus the two that create one"""
+    an RtContext* / RtMulti* (const or not) or a pointer to a call descriptor (descriptor_types of the same headers), plus the two that
+    create one"""
     out = {}
-    for path in sorted(headers or glob.glob(os.path.join(ROOT, "include", "*.h"))):
+    paths = sorted(headers or glob.glob(os.path.join(ROOT, "include", "*.h")))
+    takes = "|".join(sorted(set(CONTEXT_TYPES) | descriptor_types(paths)))
+    for path in paths:
         text = open(path).read()
-        # comments blanked, not removed: offsets into `text` stay valid for finding the comment above a declaration
-        code = re.sub(r"/\*.*?\*/", lambda m: re.sub(r"[^\n]", " ", m.group(0)), text, flags=re.S)
+        code = _blank_comments(text)
         for m in re.finditer(r"\b(rt_[a-z_0-9]+)\s*\(([^;{()]*)\)\s*;", code):
             name, first = m.group(1), re.sub(r"\s+", " ", m.group(2).split(",")[0]).strip()
-            takes_context = re.fullmatch(r"(?:const )?(%s) ?\* ?[A-Za-z_0-9]*" % "|".join(CONTEXT_TYPES), first) is not None
+            takes_context = re.fullmatch(r"(?:const )?(%s) ?\* ?[A-Za-z_0-9]*" % takes, first) is not None
             if not takes_context and name not in ft.CREATES_ALLOWED:
                 continue
             start = code.rfind("\n", 0, m.start()) + 1          # the declaration's line (its return type sits in front of the name)
@@ -76,7 +97,8 @@ def problems(decl, rows):
 
 def test_every_context_function_has_exactly_one_row():
     decl = declared()
-    assert len(decl) >= 99, len(decl)      # 99 when this test was written: the parser still finds the headers' functions
+    assert len(decl) >= 100, len(decl)     # 99 when this test was written, + rt_mis_trace: the parser still finds the headers' functions
+    assert decl["rt_mis_trace"][0] == "rt_mis.h" and "rt_debug_light_map_free" not in decl
     assert problems(decl, ft.ROWS) == []
 
 
@@ -117,6 +139,36 @@ def test_a_new_declaration_without_a_row_is_found(tmp_path):
         decl = declared([str(h)])
         assert list(decl) == [f"rt_x{i}"]
         assert f"rt_x{i} (rt_new{i}.h) has no row" in problems(decl, ft.ROWS)
+
+
+def test_a_descriptor_call_without_a_row_is_found_and_a_plain_struct_is_not_taken(tmp_path):
+    """`int rt_y(const RtYBatch*)` where RtYBatch has a context member is a call on that context, in each form the member takes, with a
+    comment and a nested-looking member in the way; a struct of plain data (as RtLightMapDump) in the first place makes no such call"""
+    for i, member in enumerate(("RtContext* ctx;", "const RtContext *ctx;", "RtMulti*  multi;", "const RtMulti * m;")):
+        h = tmp_path / f"rt_desc{i}.h"
+        h.write_text("typedef struct RtYBatch%d {\n    uint32_t struct_size; /* RtContext* not here */\n    %s\n    const void* rays;\n} RtYBatch%d;\n"
+                     "typedef struct RtYDump%d { int32_t n; uint32_t* objects; /* RtContext* ctx; */ } RtYDump%d;\n"
+                     "/* a new pass */\nint rt_y%d(const RtYBatch%d* batch);\nint rt_z%d(RtYBatch%d *b, int n);\nvoid rt_y_free%d(RtYDump%d* d);\n" % ((i, member) + (i,) * 9))
+        assert descriptor_types([str(h)]) == {f"RtYBatch{i}"}
+        decl = declared([str(h)])
+        assert sorted(decl) == [f"rt_y{i}", f"rt_z{i}"]
+        assert decl[f"rt_y{i}"] == (f"rt_desc{i}.h", "/* a new pass */")
+        bad = problems(decl, ft.ROWS)
+        assert f"rt_y{i} (rt_desc{i}.h) has no row" in bad and f"rt_z{i} (rt_desc{i}.h) has no row" in bad
+        assert not any(f"rt_y_free{i}" in b for b in bad)
+
+
+def test_a_struct_without_a_context_member_is_not_taken(tmp_path):
+    """the headers' own: RtMisBatch is a descriptor, RtLightMapDump (plain data, next to it in rt_mis.h) is not; and a struct that only
+    MENTIONS a context type — in a comment, or as a value of another name (RtContextInfo*) — is not one"""
+    types = descriptor_types(glob.glob(os.path.join(ROOT, "include", "*.h")))
+    assert "RtMisBatch" in types and "RtLightMapDump" not in types
+    decl = declared()
+    assert "rt_mis_trace" in decl and "rt_debug_light_map" not in decl and "rt_debug_light_map_free" not in decl
+    h = tmp_path / "rt_plain.h"
+    h.write_text("typedef struct RtPlain { int n; /* RtContext* ctx; */ RtContextInfo* info; float* x; } RtPlain;\nint rt_plain(const RtPlain* p);\n")
+    assert descriptor_types([str(h)]) == set() and declared([str(h)]) == {}
+    assert not any("rt_plain" in b for b in problems(declared([str(h)]), ft.ROWS) if "has no row" in b)
 
 
 def test_only_the_listed_functions_leave_held_frames_alone_without_saying_so():

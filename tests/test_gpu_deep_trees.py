@@ -18,7 +18,11 @@ reference's text compiled as C++ where it travelled:
   f. rt_nee_trace, the one kernel with two run-to-completion walks per wave iteration through one stack region: emissive, diffuse combs
      of height 1, 31 and 32, the tied comb and the 65-model scene, a wave's worth of identical witness rays whose shadow ray AND next
      segment hold H entries, against tests/nee_reference.py bit for bit (in order, reversed, as prefixes, the buffer form with guard
-     bytes), the coverage asserted from that reference's ray logs."""
+     bytes), the coverage asserted from that reference's ray logs;
+  g. rt_mis_trace, the same two walks with two things of its own behind them: the bounce row (in the > 64-model instantiation the LDS
+     word behind the candidate-mask extension, which decides whether a vertex samples — on the 65-model scene it lies directly behind a
+     32-entry stack) and the reverse lookup entry(hit object, hit triangle) on a leaf at level H.  The batch of (f), its witness chosen
+     by tests/mis_reference.py, bit for bit against that reference; rt_debug_light_map against the reference's map."""
 import ctypes as C
 import re
 import time
@@ -27,12 +31,14 @@ import numpy as np
 import pytest
 
 import deep_trees as dt
+import mis_reference as mr
 import motion_reference as mref
 import nee_reference as nr
 import radiance_reference as rr
 import test_gpu_aov as ta
 import test_gpu_cost_view as tc
 import test_gpu_fuzz as tf
+import test_gpu_mis as tm
 import test_gpu_query as tq
 from test_deep_trees import CATCHER_POINT, CATCHER_Z, CONE_SCALE, cone_camera, cone_mesh
 from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
@@ -535,11 +541,17 @@ def nee_arrays(pkg, api, name):
     return (data["meshInfo"], data["triangles"], data["nodes"], np.zeros(0, dtype=pkg.abi.sphere_dtype)), p
 
 
-def nee_case(pkg, api, orc, name):
+def nee_case(pkg, api, orc, name, estimator=nr.Estimator, accept=None, prefer=None, camera_states=None):
     """The scene's arrays and parameters, the witness state, witness_batch()'s pattern for this pass — 33 rays onto the catcher, the
-    witness ray 64 times over, 33 camera rays onto the comb — and the reference's records and logs of that batch: computed once."""
-    if name in _NEE:
-        return _NEE[name]
+    witness ray 64 times over, 33 camera rays onto the comb — and the reference's records and logs of that batch: computed once.
+    `estimator`: the reference's class (tests/nee_reference.py's, or tests/mis_reference.py's: the draws in front of a path's first
+    sample are the same).  `accept(probe, i)`: what else the probing run must say of ray i for its state to be the witness's;
+    `prefer(probe, i)`: of the accepted states the first for which this holds too is taken, the first accepted one if there is none;
+    `camera_states`: {k: state} for the k-th of the 33 camera rays in place of the state the frame gives it (a choice of inputs, like
+    the witness's).  The defaults are the NEE case, byte for byte."""
+    key = name if estimator is nr.Estimator else (name, estimator)
+    if key in _NEE:
+        return _NEE[key]
     abi = pkg.abi
     arrays, p = nee_arrays(pkg, api, name)
     height = height_of(name)
@@ -562,12 +574,12 @@ def nee_case(pkg, api, orc, name):
         c_states = 1000 + 7919 * k
         table = nr.light_table(abi, arrays[0], arrays[1], arrays[3])
         candidates = states_whose_first_sample_picks(orc, table, {0}, 33 * 4).reshape(33, 4)
-        probe = nr.Estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
+        probe = estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
         probe.trace(abi.make_path_rays(np.concatenate([np.tile(w_origin, (64, 1)), np.repeat(c_origins, 4, axis=0)]), np.tile(w_dir, (64 + 132, 1)),
                                        np.concatenate([np.arange(1, 65), candidates.reshape(-1)])))
         first_shadow = {i: (o, d, obj, tri, seen) for (i, b, o, d, obj, tri, seen) in probe.shadow_log if b == 0}
         second_segment = {i: (o, d) for (i, b, o, d) in probe.segment_log if b == 1}
-        state, tally = None, [sum(1 for i in first_shadow if i < 64), 0, 0]
+        state, preferred, tally = None, None, [sum(1 for i in first_shadow if i < 64), 0, 0]
         for i in range(64):
             if i not in first_shadow:
                 continue
@@ -575,9 +587,12 @@ def nee_case(pkg, api, orc, name):
             if not (obj == 0 and 0 <= tri <= height and occ(o, d) == height):
                 continue
             tally[1] += 1
-            if i in second_segment and occ(*second_segment[i]) == height:
+            if i in second_segment and occ(*second_segment[i]) == height and (accept is None or accept(probe, i)):
                 tally[2] += 1
                 state = i + 1 if state is None else state
+                if prefer is not None and preferred is None and prefer(probe, i):
+                    preferred = i + 1
+        state = preferred if preferred is not None else state
         print(f"{name}: of the states 1 ... 64, {tally[0]} give the first vertex a shadow ray, {tally[1]} of those go to the comb with occupancy {height}, "
               f"{tally[2]} of those have a second segment of occupancy {height}; the witness state is {state}")
         assert state is not None, f"{name}: no witness among the states 1 ... 64: {tally}"
@@ -590,33 +605,27 @@ def nee_case(pkg, api, orc, name):
         idx = np.arange(W * H)[2::11][:33]
         o = np.concatenate([c_origins, np.tile(w_origin, (64, 1)), origins.reshape(-1, 3)[idx]]).astype(F)
         d = np.concatenate([np.tile(w_dir, (33 + 64, 1)), dirs.reshape(-1, 3)[idx]]).astype(F)
-        s = np.concatenate([c_states, np.full(64, state), states.reshape(-1)[idx]]).astype(np.uint32)
+        cam_states = states.reshape(-1)[idx].astype(np.int64)
+        for k, v in (camera_states or {}).items():
+            cam_states[k] = v
+        s = np.concatenate([c_states, np.full(64, state), cam_states]).astype(np.uint32)
         rays = abi.make_path_rays(o, d, s)
         assert len(rays) == 130
-        est = nr.Estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
+        est = estimator(pkg, orc, tr, *[arrays[j] for j in (0, 1, 3)], p)
         want = est.trace(rays)
     finally:
         tr.close()
     for a in (rays, want):
         a.setflags(write=False)
-    _NEE[name] = (arrays, p, height, occ, rays, want, est)
-    return _NEE[name]
+    _NEE[key] = (arrays, p, height, occ, rays, want, est)
+    return _NEE[key]
 
 
-@pytest.mark.parametrize("name", NEE_SCENES)
-def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
-    """rt_radiance_nee_kernel runs two run-to-completion walks per wave iteration through one LDS stack region: the path segments'
-    (written out) and the shadow rays' (walk_all), with the feed's bookkeeping on the row behind the stack, extBase behind that, and
-    lanes without a shadow ray parked while their neighbours push.  Here both walks stand on the last row, in the same iteration, for a
-    whole wave's worth of lanes; everything bit for bit against tests/nee_reference.py, whose own walks (rt_query_closest) are tied to
-    rt_debug_intersect on the same rays."""
-    abi = pkg.abi
-    t0 = time.perf_counter()
-    arrays, p, height, occ, rays, want, est = nee_case(pkg, api, orc, name)
-    t_ref = time.perf_counter() - t0
+def assert_two_walk_coverage(name, height, occ, rays, est):
+    """What the 130-ray batch covers, from the reference's logs (either estimator's: the logs have one shape): the 64 witness rays' first
+    shadow rays and second segments stand on the last stack row, shadow rays there are blocked and let through, and some block has lanes
+    with and without a shadow ray at vertex 0.  -> (full_shadows, full_segments, mixed)"""
     n = len(rays)
-    assert p.maxBounceCount == 2 and np.isfinite(want["rgb"]).all() and want["rgb"].any()
-    # ---- what the batch covers, from the reference's logs
     shadow0 = {i: (o, d, seen) for (i, b, o, d, _, _, seen) in est.shadow_log if b == 0}
     full_shadows = [(i, b, seen) for (i, b, o, d, _, _, seen) in est.shadow_log if occ(o, d) == height]
     full_segments = [(i, b) for (i, b, o, d) in est.segment_log if occ(o, d) == height]
@@ -632,23 +641,57 @@ def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
         mixed.append((sum(1 for i in lanes if i in shadow0), len(lanes)))
     assert any(0 < with_shadow < lanes for (with_shadow, lanes) in mixed), mixed
     assert est.triangle_samples > 0 and est.shadow_rays > est.unshadowed > 0
+    return full_shadows, full_segments, mixed
+
+
+def assert_batch_in_every_order(name, tr, rays, want, host, buffers):
+    """The batch through `host` (a tracer's host-form call) in order, reversed and as prefixes 1, 33, 96, 97 and 130, and through
+    `buffers` (its device form) with 64 guard bytes of 0xa5 behind the records: the reference's records every time, the guard intact,
+    and the 64 witness slots one and the same record.  -> the records in order"""
+    n, guard = len(rays), 64
+    got = host(rays)
+    rev = host(rays[::-1])[::-1]
+    prefixes = {k: host(rays[:k]) for k in (1, 33, 96, 97, 130)}
+    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16 + guard, fill=0xa5)
+    try:
+        buffers(d_rays.ptr, n, d_out.ptr)
+        tr.synchronize()
+        raw = d_out.download(np.uint8)
+    finally:
+        d_rays.free(), d_out.free()
+    for what, rec in [("in order", got), ("reversed", rev)] + [(f"n = {k}", part) for k, part in prefixes.items()]:
+        ref = want[:len(rec)]
+        bad = np.argwhere((rr.bits(rec["rgb"]) != rr.bits(ref["rgb"])).any(axis=1) | (rec["rng"] != ref["rng"])).ravel()
+        assert not len(bad), f"{name}, {what}: {len(bad)} of {len(rec)} records differ; first is ray {bad[0]}: got {rec[bad[0]]}, want {ref[bad[0]]}"
+        assert rec.tobytes() == ref.tobytes(), (name, what)
+    assert raw[:n * 16].tobytes() == want.tobytes() and (raw[n * 16:] == 0xa5).all(), f"{name}: buffer form"
+    assert len({r.tobytes() for r in got[33:97]}) == 1, "the 64 witness slots hold one and the same record"
+    return got
+
+
+@pytest.mark.parametrize("name", NEE_SCENES)
+def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
+    """rt_radiance_nee_kernel runs two run-to-completion walks per wave iteration through one LDS stack region: the path segments'
+    (written out) and the shadow rays' (walk_all), with the feed's bookkeeping on the row behind the stack, extBase behind that, and
+    lanes without a shadow ray parked while their neighbours push.  Here both walks stand on the last row, in the same iteration, for a
+    whole wave's worth of lanes; everything bit for bit against tests/nee_reference.py, whose own walks (rt_query_closest) are tied to
+    rt_debug_intersect on the same rays."""
+    abi = pkg.abi
+    t0 = time.perf_counter()
+    arrays, p, height, occ, rays, want, est = nee_case(pkg, api, orc, name)
+    t_ref = time.perf_counter() - t0
+    assert p.maxBounceCount == 2 and np.isfinite(want["rgb"]).all() and want["rgb"].any()
+    # ---- what the batch covers, from the reference's logs
+    full_shadows, full_segments, mixed = assert_two_walk_coverage(name, height, occ, rays, est)
     table = nr.light_table(abi, arrays[0], arrays[1], arrays[3])
     assert table["n_triangle_entries"] >= height + 1 and table["n_sphere_entries"] == 0
     # ---- the device
-    guard = 64
     tr = api.create_tracer(0)
     try:
         tr.upload_scene(*arrays)
         tr.set_params(p)
         assert tr.nee_light_count() == (table["n_sphere_entries"], table["n_triangle_entries"])
-        got = tr.radiance_trace_nee(rays)
-        rev = tr.radiance_trace_nee(rays[::-1])[::-1]
-        prefixes = {k: tr.radiance_trace_nee(rays[:k]) for k in (1, 33, 96, 97, 130)}
-        d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16 + guard, fill=0xa5)
-        tr.radiance_trace_nee_buffers(d_rays.ptr, n, d_out.ptr)
-        tr.synchronize()
-        raw = d_out.download(np.uint8)
-        d_rays.free(), d_out.free()
+        got = assert_batch_in_every_order(name, tr, rays, want, tr.radiance_trace_nee, tr.radiance_trace_nee_buffers)
         # the reference's own walks at this depth against the second device path
         seen_rays = {}
         for (_, _, o, d, _, _, _) in est.shadow_log:
@@ -664,15 +707,83 @@ def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
             assert stripped.tobytes() == plain.tobytes() and (stripped["rng"] != rays["rng"]).any() and stripped.tobytes() != got.tobytes()
     finally:
         tr.close()
-    for what, rec in [("in order", got), ("reversed", rev)] + [(f"n = {k}", part) for k, part in prefixes.items()]:
-        ref = want[:len(rec)]
-        bad = np.argwhere((rr.bits(rec["rgb"]) != rr.bits(ref["rgb"])).any(axis=1) | (rec["rng"] != ref["rng"])).ravel()
-        assert not len(bad), f"{name}, {what}: {len(bad)} of {len(rec)} records differ; first is ray {bad[0]}: got {rec[bad[0]]}, want {ref[bad[0]]}"
-        assert rec.tobytes() == ref.tobytes(), (name, what)
-    assert raw[:n * 16].tobytes() == want.tobytes() and (raw[n * 16:] == 0xa5).all(), f"{name}: buffer form"
-    assert len({r.tobytes() for r in got[33:97]}) == 1, "the 64 witness slots hold one and the same record"
     assert tq.bits(dbg[:, 2]).tolist() == tq.bits(hits["dst"]).tolist()
     assert tq.bits(dbg[:, 3:6]).tolist() == tq.bits(hits["normal"]).tolist() and tq.bits(dbg[:, 6:9]).tolist() == tq.bits(hits["pos"]).tolist()
     assert np.array_equal(dbg[:, 0] != 0, (hits["hit"] & 3) != 0) and np.array_equal(dbg[:, 1] != 0, (hits["hit"] & 0x100) != 0)
     print(f"{name}: {len(full_shadows)} shadow rays and {len(full_segments)} path segments with {height} stack entries; lanes of vertex 0 with a shadow ray per block {mixed}; "
           f"{len(so)} distinct shadow rays against rt_debug_intersect; reference {t_ref:.1f} s, all {time.perf_counter() - t0:.1f} s")
+
+
+# ---------------------------------------------------------------- g. rt_mis: the bounce row and the reverse lookup behind the same two walks
+def _mis_witness(probe, i):
+    """ray i of the probing run: the hit that ends its second segment has its emission weighted by the balance heuristic with
+    0 < wb < 1 — the lookup found an entry for the hit triangle, and both densities were computed"""
+    return any(r == i and v == 1 and rule == mr.WEIGHTED and 0.0 < wb < 1.0 and kind == "triangle" for (r, v, wb, rule, kind) in probe.emission_log)
+
+
+MIS_CAMERA_STATES = {"comb1alternate-emissive": {16: 77, 22: 81}}   # {scene: {k-th camera ray: generator state}}: see the test's text
+
+
+def _mis_reaches_its_last_vertex(probe, i):
+    """ray i of the probing run goes on to a diffuse vertex 2, where it must not sample"""
+    return (i, 2) in probe.skipped_log
+
+
+@pytest.mark.parametrize("name", NEE_SCENES)
+def test_mis_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
+    """The MIS instantiations of rt_radiance_nee_kernel on the batch of (f) at maxBounceCount 2: vertices 0 and 1 sample, vertex 2 must
+    not — the decision RT_SHADE_OPAQUE_END takes from the bounce count, which the > 64-model instantiation keeps in the LDS row behind
+    the extension words, here (crowd65_first-emissive: one extension word) two rows behind a stack of 32 that both walks fill between
+    the increment and the next read.  The witness's second segment ends on a comb triangle — a leaf at level H, named by
+    hit_triangle() and looked up by rt_mis::entry_of — and its emission is weighted with 0 < wb < 1.  Everything bit for bit against
+    tests/mis_reference.py; the witness rests on the geometric conditions tests/test_deep_trees.py holds for (f), no further one.
+    Of the accepted states the witness prefers one whose path goes on to a skipped vertex 2.  comb(1) needs more: leaf 0 faces the
+    camera and leaf 1 away from it, so a vertex on the comb or on the blocker sees no emitter's front, and only the 0.6 x 0.6 catcher
+    can be a sampling vertex 1 or a diffuse vertex 2.  With the states the frame gives the camera rays no path of the batch gets there
+    (0 rows in either log); MIS_CAMERA_STATES gives two of those rays a state, found by one search of 3,000 states per ray, whose path
+    goes comb or blocker -> catcher (vertex 1: a sample that reaches its shadow walk) -> a diffuse vertex 2 (skipped)."""
+    abi = pkg.abi
+    t0 = time.perf_counter()
+    arrays, p, height, occ, rays, want, est = nee_case(pkg, api, orc, name, mr.Estimator, _mis_witness, _mis_reaches_its_last_vertex, MIS_CAMERA_STATES.get(name))
+    t_ref = time.perf_counter() - t0
+    assert p.maxBounceCount == 2 and np.isfinite(want["rgb"]).all() and want["rgb"].any()
+    # ---- what the batch covers, from the reference's logs
+    full_shadows, full_segments, mixed = assert_two_walk_coverage(name, height, occ, rays, est)
+    weights = {(r, v): (wb, rule, kind) for (r, v, wb, rule, kind) in est.emission_log}
+    for w in range(33, 97):
+        wb, rule, kind = weights[(w, 1)]
+        assert rule == mr.WEIGHTED and 0.0 < wb < 1.0 and kind == "triangle", (w, wb, rule, kind)
+    sampled = {v for (_, v, *_r) in est.sample_log}
+    assert sampled == {0, 1}, f"vertices 0 and 1 sample, no other: {sampled}"
+    assert est.skipped_log and all(v == 2 for (_, v) in est.skipped_log), "the last vertex takes no sample"
+    tm.rules_allowed(est, name)
+    models, triangles, spheres = arrays[0], arrays[1], arrays[3]
+    objects, words, table = mr.map_arrays(abi, models, triangles, spheres)
+    assert table["n_triangle_entries"] >= height + 1 and table["n_sphere_entries"] == 0
+    got_map = api.light_map_arrays(models, triangles, spheres)
+    assert got_map["objects"].tobytes() == objects.tobytes() and got_map["triangles"].tobytes() == words.tobytes(), f"{name}: rt_debug_light_map"
+    assert got_map["n_entries"] == len(table["entries"]) and objects[0] == 0 and (words[:height + 1] != mr.NO_ENTRY).all(), "every leaf of the comb has an entry"
+    # ---- the device
+    second = next((o, d) for (i, b, o, d) in est.segment_log if i == 33 and b == 1)
+    tr = api.create_tracer(0)
+    try:
+        tr.upload_scene(*arrays)
+        tr.set_params(p)
+        end = tr.query_closest(abi.make_rays(second[0][None], second[1][None]))[0]
+        assert int(end["object"]) == 0 and 0 <= int(end["triangle"]) <= height, f"{name}: the witness's second segment ends on {end}"
+        assert words[int(end["triangle"])] != mr.NO_ENTRY
+        got = assert_batch_in_every_order(name, tr, rays, want, tr.radiance_trace_mis, tr.radiance_trace_mis_buffers)
+        plain, nee = tr.radiance_trace(rays), tr.radiance_trace_nee(rays)
+        assert got.tobytes() != plain.tobytes() and got.tobytes() != nee.tobytes(), "the batch tells the three estimators apart"
+        if name == "comb32alternate-emissive":  # with the emitter put out the pass is rt_radiance_trace, bit for bit
+            dark = arrays[0].copy()
+            dark["material"]["emissionStrength"] = 0
+            tr.update_models(dark)
+            assert tr.nee_light_count() == (0, 0)
+            plain, stripped = tr.radiance_trace(rays), tr.radiance_trace_mis(rays)
+            assert stripped.tobytes() == plain.tobytes() and (stripped["rng"] != rays["rng"]).any() and stripped.tobytes() != got.tobytes()
+    finally:
+        tr.close()
+    print(f"{name}: {len(full_shadows)} shadow rays and {len(full_segments)} path segments with {height} stack entries; lanes of vertex 0 with a shadow ray per block {mixed}; "
+          f"the witness's second hit is triangle {int(end['triangle'])} with wb = {weights[(33, 1)][0]:.6f}; {len(est.sample_log)} shadow rays at vertices 0 and 1, "
+          f"{len(est.skipped_log)} samples skipped at vertex 2; reference {t_ref:.1f} s, all {time.perf_counter() - t0:.1f} s")

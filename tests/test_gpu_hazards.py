@@ -12,7 +12,7 @@ The contexts are shared by the cases of this module (a case starts with rt_resiz
 rt_reset_accumulation): a table left over from the previous case's key would show as a wrong pixel.
 
 Side passes (hazard_scenes.SIDE_CASES on SIDE_BASES): rt_render_aov, rt_query_closest / rt_query_occluded / rt_debug_intersect,
-rt_radiance_trace and (NEE_CASES) rt_nee_trace against the oracle's functions.  Floats are compared bit for bit, except that where
+rt_radiance_trace and (NEE_CASES) rt_nee_trace and rt_mis_trace against the oracle's functions.  Floats are compared bit for bit, except that where
 the expected value is a NaN the device's must be one too (a NaN's sign and payload are not part of the contract).
 
 The triangle and mesh cases ride through all of the above; on top, for them: (object, triangle) of the AOV and query records is the
@@ -28,8 +28,10 @@ import numpy as np
 import pytest
 
 import hazard_scenes as hz
+import mis_reference as mr
 import nee_reference as nr
 import radiance_reference as rr
+import test_gpu_mis as tm
 from test_gpu_tile_tri import KEYS, environment
 
 pytestmark = pytest.mark.gpu
@@ -314,11 +316,10 @@ def _nee_rig(pkg, api, base, name):
     return hz.Rig(pkg, api, base, made), (t.sphere if name == "radius-0" else None)
 
 
-@pytest.mark.parametrize("name", hz.NEE_CASES)
-def test_nee_with_emission_and_area_hazards(pkg, api, orc, contexts, name):
-    """rt_debug_light_table against the numpy table of tests/nee_reference.py, bit for bit; rt_nee_light_count; the header's rules leave
-    out an emitter whose emission is not finite and a sphere of radius 0 (asserted); rt_nee_trace on every 7th pixel's camera ray against
-    the estimator restated in tests/nee_reference.py"""
+def _emission_and_area_hazards(pkg, api, orc, contexts, name, estimator, trace, call):
+    """The body of the NEE test below, for either light-sampling pass: `estimator` the reference's class, `trace` the tracer's method
+    by name, `call` the C function for the messages.  Yields, per base, what a caller asserts more from:
+    (what, rig, the planted object, the numpy table, the estimator with its logs, the expected records)"""
     abi = pkg.abi
     for base in hz.SIDE_BASES:
         if not hz.BY_NAME[name].applies(base):
@@ -344,12 +345,58 @@ def test_nee_with_emission_and_area_hazards(pkg, api, orc, contexts, name):
         tr.set_params(p)
         o, d, state = rr.camera_rays(orc, p, rig.w, rig.h, frame=rig.frame0 + 1)
         rays = abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel())[::7]
-        est = nr.Estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
+        est = estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
         expect = est.trace(rays)
-        out = tr.radiance_trace_nee(rays)
+        out = getattr(tr, trace)(rays)
         ok = _same(out["rgb"], expect["rgb"]).all(axis=1) & (out["rng"] == expect["rng"])
         print(f"{what}: lights {counts}, {est.samples} samples, {est.shadow_rays} shadow rays, {est.unshadowed} unshadowed")
-        assert ok.all(), f"{what}: rt_nee_trace: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+        assert ok.all(), f"{what}: {call}: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+        yield what, rig, planted, want, est, expect
+
+
+@pytest.mark.parametrize("name", hz.NEE_CASES)
+def test_nee_with_emission_and_area_hazards(pkg, api, orc, contexts, name):
+    """rt_debug_light_table against the numpy table of tests/nee_reference.py, bit for bit; rt_nee_light_count; the header's rules leave
+    out an emitter whose emission is not finite and a sphere of radius 0 (asserted); rt_nee_trace on every 7th pixel's camera ray against
+    the estimator restated in tests/nee_reference.py"""
+    assert len(list(_emission_and_area_hazards(pkg, api, orc, contexts, name, nr.Estimator, "radiance_trace_nee", "rt_nee_trace"))) >= 2
+
+
+def _not_vacuous(what, est, expect, t0):
+    """the two conditions that keep a MIS hazard case from passing on nothing, measured on the reference: at least a quarter of the
+    compared records are finite and not zero, and samples were taken"""
+    rgb = expect["rgb"]
+    live = int((np.isfinite(rgb).all(axis=1) & (rgb != 0).any(axis=1)).sum())
+    rules = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
+    print(f"{what}: {live} of {len(rgb)} records finite and not zero, {int((~np.isfinite(rgb)).any(axis=1).sum())} not finite; {est.samples} samples, "
+          f"{len(est.sample_log)} shadow rays, g == 0 in {sum(1 for s in est.sample_log if s[2] == 0.0)}; emissions behind a sample {rules}; "
+          f"{time.perf_counter() - t0:.2f} s for this base, the reference included")
+    assert 4 * live >= len(rgb), f"{what}: only {live} of {len(rgb)} compared records are finite and not zero"
+    assert est.samples > 0, what
+    tm.rules_allowed(est, what)
+
+
+def _assert_map(pkg, api, what, rig):
+    """rt_debug_light_map == tests/mis_reference.py::map_arrays, bit for bit -> (objects, words)"""
+    objects, words, table = mr.map_arrays(pkg.abi, rig.models, rig.triangles, rig.spheres)
+    got = api.light_map_arrays(rig.models, rig.triangles, rig.spheres)
+    assert got["objects"].tobytes() == objects.tobytes() and got["triangles"].tobytes() == words.tobytes() and got["n_entries"] == len(table["entries"]), what
+    return objects, words
+
+
+@pytest.mark.parametrize("name", hz.NEE_CASES)
+def test_mis_with_emission_and_area_hazards(pkg, api, orc, contexts, name):
+    """The NEE twin's rigs, rays and assertions with rt_mis_trace against tests/mis_reference.py — records that hold an inf or a NaN
+    included, under the NaN-position rule; on top the reverse map bit for bit, with RT_MIS_NO_ENTRY in the object record of an emitter
+    the table's rules exclude as a whole (emission-inf, radius-0)."""
+    bases, t0 = 0, time.perf_counter()
+    for what, rig, planted, table, est, expect in _emission_and_area_hazards(pkg, api, orc, contexts, name, mr.Estimator, "radiance_trace_mis", "rt_mis_trace"):
+        objects, words = _assert_map(pkg, api, what, rig)
+        assert (objects[planted] == mr.NO_ENTRY) == (name in ("emission-inf", "radius-0")) == (not table["in_table"][planted]), what
+        _not_vacuous(what, est, expect, t0)
+        t0 = time.perf_counter()
+        bases += 1
+    assert bases >= 2
 
 
 # ---- one context through hazards and back -----------------------------------------------------------------------------------------------
@@ -533,13 +580,11 @@ def _emissive(case, name):
     return hz.Case(name + "-emitter", case.kind, case.guard, case.tables, scene=scene, triangles=case.triangles)
 
 
-@pytest.mark.parametrize("name", hz.NEE_TRI_CASES)
-def test_nee_with_an_emissive_model_of_planted_triangles(pkg, api, orc, contexts, name):
-    """the light table's area rule (rt_light_table.h: S > 0 and finite, ng finite) on planted triangles: rt_debug_light_table == the numpy
-    table of tests/nee_reference.py bit for bit, rt_nee_light_count, the planted triangles left out exactly where their area (float64
-    from the fp32 world corners, rounded to fp32) is 0 or not finite; rt_nee_trace on every 7th pixel's camera ray == the restated estimator"""
+def _planted_triangle_emitters(pkg, api, orc, contexts, name, estimator, trace, call, bases=hz.SIDE_BASES):
+    """The body of the NEE test below, for either light-sampling pass (as _emission_and_area_hazards).  Yields per base
+    (what, rig, the emissive model's object index, its triangle range, the planted triangles, the estimator, the expected records)"""
     abi = pkg.abi
-    for base in hz.SIDE_BASES:
+    for base in bases:
         t = hz.aim(pkg, base)
         rig = hz.Rig(pkg, api, base, _emissive(hz.BY_NAME[name], name))
         tr = next(x for n, _, x, stats in contexts if n == "default" and not stats)
@@ -564,13 +609,49 @@ def test_nee_with_an_emissive_model_of_planted_triangles(pkg, api, orc, contexts
         tr.set_params(p)
         o, d, state = rr.camera_rays(orc, p, rig.w, rig.h, frame=rig.frame0 + 1)
         rays = abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel())[::7]
-        est = nr.Estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
+        est = estimator(pkg, orc, tr, rig.models, rig.triangles, rig.spheres, p)
         expect = est.trace(rays)
-        out = tr.radiance_trace_nee(rays)
+        out = getattr(tr, trace)(rays)
         ok = _same(out["rgb"], expect["rgb"]).all(axis=1) & (out["rng"] == expect["rng"])
         print(f"{what}: lights {counts}, {len(listed)} of {len(mine)} triangles of the emissive model listed, {est.samples} samples, "
               f"{est.shadow_rays} shadow rays, {est.unshadowed} unshadowed")
-        assert ok.all(), f"{what}: rt_nee_trace: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+        assert ok.all(), f"{what}: {call}: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
+        yield what, rig, obj, (lo, lo + int(rig.tri_count[t.tri_model])), planted, est, expect
+
+
+@pytest.mark.parametrize("name", hz.NEE_TRI_CASES)
+def test_nee_with_an_emissive_model_of_planted_triangles(pkg, api, orc, contexts, name):
+    """the light table's area rule (rt_light_table.h: S > 0 and finite, ng finite) on planted triangles: rt_debug_light_table == the numpy
+    table of tests/nee_reference.py bit for bit, rt_nee_light_count, the planted triangles left out exactly where their area (float64
+    from the fp32 world corners, rounded to fp32) is 0 or not finite; rt_nee_trace on every 7th pixel's camera ray == the restated estimator"""
+    assert len(list(_planted_triangle_emitters(pkg, api, orc, contexts, name, nr.Estimator, "radiance_trace_nee", "rt_nee_trace"))) == len(hz.SIDE_BASES)
+
+
+@pytest.mark.parametrize("name", hz.NEE_TRI_CASES)
+def test_mis_with_an_emissive_model_of_planted_triangles(pkg, api, orc, contexts, name):
+    """The NEE twin's rigs, rays and assertions with rt_mis_trace against tests/mis_reference.py; on top the reverse map bit for bit: a
+    planted triangle the area rule leaves out has the word RT_MIS_NO_ENTRY INSIDE the range of a model whose object record has a base
+    (a hole in the middle of the range: a hit there is added in full, the triangles around it are weighted), and a model all of whose
+    triangles are left out has RT_MIS_NO_ENTRY in its object record and no words."""
+    # tri-degenerate and tri-tiny-1e-20 plant every triangle of the emissive model's mesh, and on the bvh base that mesh is the cube the
+    # room's light shares: the table is empty there, and an empty table is rt_radiance_trace (tests/test_gpu_mis.py holds that identity)
+    # — no sample would be taken.  Those two cases take flat-tables, whose emissive spheres stay, in its place.
+    whole_mesh = name in ("tri-degenerate", "tri-tiny-1e-20")
+    bases = tuple("flat-tables" if (b == "bvh" and whole_mesh) else b for b in hz.SIDE_BASES)
+    holes, t0 = 0, time.perf_counter()
+    for what, rig, obj, (lo, hi), planted, est, expect in _planted_triangle_emitters(pkg, api, orc, contexts, name, mr.Estimator, "radiance_trace_mis", "rt_mis_trace", bases):
+        objects, words = _assert_map(pkg, api, what, rig)
+        whole = planted == set(range(lo, hi))
+        assert (objects[obj] == mr.NO_ENTRY) == whole, what
+        if not whole:
+            base = int(objects[obj])
+            assert base + (hi - lo) <= len(words), what
+            for k in range(lo, hi):
+                assert (words[base + (k - lo)] == mr.NO_ENTRY) == (k in planted), f"{what}: triangle {k} of the emissive model"
+            holes += len(planted)
+        _not_vacuous(what, est, expect, t0)
+        t0 = time.perf_counter()
+    assert (holes > 0) == (name in ("tri-vertex-1e20", "tri-vertex-nan")), f"{name}: {holes} words without an entry inside a range that has a base"
 
 
 MESH = [c for c in hz.CASES if c.kind == "mesh"]

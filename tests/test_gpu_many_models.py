@@ -15,7 +15,9 @@ Here the device renders each scene and must equal the oracle, every comparison b
   d. the height-32 comb beside 1,086 and 1,299 models, first and last: 32 stack entries under 32 extension words, launched as the one
      group of 9 waves around a 24-record cache that the CPU half computed; rt_render_cost and rt_render_aov on the same scenes;
   e. the side passes on crowd1300 and the staircase: rt_render_cost, rt_render_aov and its centre form, the ray queries with tmax at, above
-     and below the hit, rt_radiance_trace, and rt_nee_trace with emitters on either side of the mask's boundaries;
+     and below the hit, rt_radiance_trace, and rt_nee_trace with emitters on either side of the mask's boundaries; rt_mis_trace on the same
+     scenes and on crowd96 and crowd1087, at maxBounceCount 1, 2 and 5: its bounce row lies behind 1, 2 and 32 extension words, its reverse
+     lookup takes object indices up to 1,299;
   f. one context through rt_update_models steps on the staircase and through uploads of 1,300, 1,087, 64 and 1,300 models;
   g. flat1300: the FLAT kernel with 1,300 models."""
 import ctypes as C
@@ -26,11 +28,13 @@ import pytest
 
 import hazard_scenes as hz
 import many_models as mm
+import mis_reference as mr
 import motion_reference as mref
 import nee_reference as nr
 import radiance_reference as rr
 import test_gpu_aov as ta
 import test_gpu_cost_view as tc
+import test_gpu_mis as tm
 import test_gpu_query as tq
 from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
 from test_gpu_deep_trees import launches
@@ -428,6 +432,109 @@ def test_nee_with_emitters_on_either_side_of_the_boundaries(pkg, api, orc, name)
         assert ok.all(), f"{name}: rt_nee_trace: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator"
     finally:
         tr.close()
+
+
+MIS_SCENES = SIDE_SCENES + ["crowd96", "crowd1087"]   # crowd96: the step from 1 to 2 extension words; crowd1087: the cap, 32 words
+MIS_BOUNCES = (1, 2, 5)                               # (5: the catalogue's own)
+MIS_STRIDE = {}                                       # every other pixel's camera ray, as the NEE test's; a coarser stride per scene if need be
+
+
+def mis_emitters(sc):
+    """EMITTERS where the scene has them all, otherwise those of 62, 63, 1086 and n - 1 that exist"""
+    return mm.EMITTERS if sc.n > max(mm.EMITTERS) else tuple(sorted({i for i in (62, 63, 1086) if i < sc.n} | {sc.n - 1}))
+
+
+def gap_rays(sc, k=16):
+    """A staircase's plates face the camera: a camera path's lobe ray leaves a plate's front towards the camera and meets no emitter's
+    front.  So k rays from inside the 2 mm gap between plates 1086 and 1087 — both planted emitters, both WITNESS plates, neighbours in
+    depth in either order — at the front of the farther one, 2 % off grazing, around the plates' common centre (the ray of W_PIXEL): the
+    vertex there samples, and its lobe ray crosses the gap to the BACK of the nearer plate, an emitter at or above index 1,086 (the
+    rounded cube is closed, its back an outward face).  From the plate geometry of tests/many_models.py alone.
+    -> (origins, directions, the nearer plate, the farther plate)"""
+    near, far = sorted((1086, 1087), key=lambda i: mm.plate_depth(sc.order, i, sc.n))
+    z_back, z_front = mm.plate_depth(sc.order, near, sc.n) + mm.THICK / 2, mm.plate_depth(sc.order, far, sc.n) - mm.THICK / 2
+    assert 0.0015 < z_front - z_back < 0.0025
+    tx, ty = mm.pixel_tangent(*mm.W_PIXEL)
+    o, d = [], []
+    for j in range(k):
+        target = np.array([tx * z_front + 0.01 * (j % 4 - 1.5), ty * z_front + 0.01 * (j // 4 - 1.5), z_front])
+        origin = target + np.array([0.04, 0.03, -(z_front - z_back) / 2])
+        v = target - origin
+        o.append(origin), d.append(v / np.linalg.norm(v))
+    return np.array(o, dtype=F), np.array(d, dtype=F), near, far
+
+
+@pytest.mark.parametrize("bounce", MIS_BOUNCES)
+@pytest.mark.parametrize("name", MIS_SCENES)
+def test_mis_with_emitters_on_either_side_of_the_boundaries(pkg, api, orc, name, bounce, monkeypatch, capfd):
+    """The emissive material on models 62, 63, 1086, 1087 and n - 1 (those the scene has): rt_debug_light_table and rt_debug_light_map
+    against the numpy table and map, and rt_mis_trace on every other pixel's camera ray (on a staircase also gap_rays) against
+    tests/mis_reference.py bit for bit, at maxBounceCount 1, 2 and 5.  In the > 64-model instantiation the kernel takes "does this vertex
+    sample" from the LDS row behind the extension words (1 at 65 ... 95 models, 2 at 96, 32 from 1,087 on), which every walk's
+    begin_intersect clears up to — a row too low and the count is 0 at every vertex, so the last vertex samples: the logs say that no
+    vertex at maxBounceCount did.  The reverse lookup takes the hit object: an emission weighted on an object of the extension words
+    and, on the staircases, on a planted emitter of the last word or the unfiltered tail."""
+    abi = pkg.abi
+    t0 = time.perf_counter()
+    sc = mm.scene(pkg, api, name)
+    planted = mis_emitters(sc)
+    models = mm.with_emitters(sc, planted)
+    objects, words, table = mr.map_arrays(abi, models, sc.triangles, sc.spheres)
+    got_table, got_map = api.light_table_arrays(models, sc.triangles, sc.spheres), api.light_map_arrays(models, sc.triangles, sc.spheres)
+    assert got_table["entries"].tobytes() == table["entries"].tobytes() and got_table["cdf"].tobytes() == table["cdf"].tobytes(), name
+    assert got_map["objects"].tobytes() == objects.tobytes() and got_map["triangles"].tobytes() == words.tobytes() and got_map["n_entries"] == len(table["entries"]), name
+    assert all(table["in_table"][i] and objects[i] != mr.NO_ENTRY for i in planted), "every planted emitter is in the table and in the map"
+    monkeypatch.setenv("RT_DEBUG_LAUNCH", "1")
+    tr = api.create_tracer(0)
+    try:
+        sc.upload(tr, models)
+        # which instantiation: the side passes report no launch shape, and take theirs by the rule the frame launch takes its own by
+        # (rt_plan::many_models of the context's chunk count; tests/test_launch_plan.py holds the rule) — so a frame's report says it
+        capfd.readouterr()
+        tr.render_frame()
+        tr.synchronize()
+        variants = {r[0] for r in launches(capfd)}
+        monkeypatch.delenv("RT_DEBUG_LAUNCH")
+        assert variants and variants <= set(MANY_VARIANTS), f"{name}: the context launches variants {variants}"
+        p = sc.params(2, numRaysPerPixel=1, maxBounceCount=bounce)
+        tr.set_params(p)
+        o, d, state = rr.camera_rays(orc, p, sc.w, sc.h, frame=2)
+        rays = abi.make_path_rays(o.reshape(-1, 3), d.reshape(-1, 3), state.ravel())[::MIS_STRIDE.get(name, 2)]
+        n_gap, near = 0, None
+        if sc.order is not None:
+            go, gd, near, _ = gap_rays(sc)
+            n_gap = len(go)
+            rays = np.concatenate([rays, abi.make_path_rays(go, gd, 4000 + 977 * np.arange(n_gap))])
+        est = mr.Estimator(pkg, orc, tr, models, sc.triangles, sc.spheres, p)
+        expect = est.trace(rays)
+        t_ref = time.perf_counter() - t0
+        out, plain = tr.radiance_trace_mis(rays), tr.radiance_trace(rays)
+    finally:
+        tr.close()
+    ok = (rr.bits(out["rgb"]) == rr.bits(expect["rgb"])).all(axis=1) & (out["rng"] == expect["rng"])
+    assert len(est.emission_hits) == len(est.emission_log)
+    tm.rules_allowed(est, f"{name} bounce={bounce}")
+    weighted_on = sorted({obj for (obj, _), e in zip(est.emission_hits, est.emission_log) if e[3] == mr.WEIGHTED})
+    rules = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
+    sampled, skipped = sorted({v for (_, v, *_r) in est.sample_log}), sorted({v for (_, v) in est.skipped_log})
+    reached = [i for i in weighted_on if i in planted and i >= 1086]
+    print(f"{name} bounce={bounce}: {len(rays)} rays ({n_gap} into the gap), lights ({table['n_sphere_entries']}, {table['n_triangle_entries']}), {est.samples} samples, "
+          f"{est.shadow_rays} shadow rays, {est.unshadowed} unshadowed; sampled at vertices {sampled}, skipped at {skipped} ({len(est.skipped_log)}); emissions behind a sample {rules}; "
+          f"weighted on {len(weighted_on)} objects, {sum(1 for i in weighted_on if i >= 64)} of them >= 64, {sum(1 for i in weighted_on if i >= mm.FILTER_CAP)} in the tail, "
+          f"planted emitters >= 1086 among them {reached}; reference {t_ref:.1f} s, all {time.perf_counter() - t0:.1f} s")
+    assert all(v < bounce for (_, v, *_r) in est.sample_log) and all(v == bounce for (_, v) in est.skipped_log), (sampled, skipped)
+    if bounce == 2:
+        assert {0, 1} <= set(sampled), sampled
+    if bounce <= 2:   # (at 5, crowd96's few paths are all over before their sixth vertex)
+        assert est.skipped_log, "no path reached its last vertex: the decision was never taken"
+    assert est.shadow_rays > 0 and len(est.sample_log) > 0
+    assert np.isfinite(expect["rgb"]).all() and expect["rgb"].any()
+    assert ok.all(), f"{name}: rt_mis_trace at maxBounceCount {bounce}: {int((~ok).sum())} of {len(ok)} rays differ from the restated estimator; first is ray {int(np.argmin(ok))}"
+    assert out.tobytes() != plain.tobytes(), "the records are rt_radiance_trace's: nothing was sampled"
+    if name in SIDE_SCENES:
+        assert any(i >= 64 for i in weighted_on), f"{name}: no weighted emission on an object at or above index 64"
+    if near is not None:   # the gap rays: a planted emitter of the last extension word / the first of the tail, hit from a sampled vertex
+        assert near in weighted_on, f"{name}: no weighted emission on plate {near}, the nearer of 1086 and 1087"
 
 
 # ---------------------------------------------------------------- f. one context through changes

@@ -9,13 +9,19 @@
      polygon form factor;
   5. the bound of the header, record by record, where rt_nee_trace exceeds it;
   6. the same expectation as rt_radiance_trace at maxBounceCount 1 and the scene's own, 2^20 paths;
-  7. the side-pass manners: behind held-back frames (the `flushes` row the call would have in tests/flush_table.py), behind updates,
-     mixed with the other estimators, every error row, the cap, the pass's own watchdog word, torch tensors, every device layout."""
+  7. the side-pass manners: behind held-back frames (the call's two `flushes` rows of tests/flush_table.py, once more with the records compared), behind updates,
+     mixed with the other estimators, every error row, the cap, the pass's own watchdog word, torch tensors, every device layout;
+  8. a lane that takes a second ray: one wave, a path that dies with its cosine set, then a ray whose first hit is an emitter;
+  9. the rules of emission_weight: RULE_TABLE names the case that reaches each, or why no table the library builds can; no reference
+     run of any MIS test may log one that is marked unreachable (rules_allowed).
+The stack's last row, more than 64 models and non-finite values under this kernel: tests/test_gpu_deep_trees.py (g),
+tests/test_gpu_many_models.py (e), tests/test_gpu_hazards.py."""
 import ctypes as C
 import os
 import re
 import subprocess
 import sys
+import time
 
 import numpy as np
 import pytest
@@ -77,6 +83,7 @@ def test_records_equal_the_reference_bit_for_bit(pkg, api, orc, name, bounce):
           f"; {len(est.skipped_log)} last-vertex samples skipped, {len(est.plain_emission_log)} emitter hits behind no sample")
     gn.assert_records(got, want, f"{name} bounce={p.maxBounceCount}")
     assert got.tobytes() == want.tobytes()
+    rules_allowed(est, f"{name} bounce={p.maxBounceCount}")
     for (_, _, g, _, _) in est.sample_log:
         assert 0.0 <= g <= 1.0
     for (_, _, wb, _, _) in est.emission_log:
@@ -137,6 +144,155 @@ def test_block_boundaries_and_a_grid_of_two_waves(pkg, api, orc, monkeypatch):
         tr.close()
     gn.assert_records(got, want, "RT_GRID=2")
     assert rev.tobytes() == want.tobytes(), "reversed"
+
+
+def test_a_reused_lane_starts_without_the_dead_paths_cosine(pkg, api, orc, monkeypatch):
+    """One wave (RT_GRID=1, read at rt_create) and 128 rays: every lane takes a second ray when its first path has ended, and the feed's
+    RT_FEED_START resets the lane's cnPrev (rt_nee_trace: prevSampled).  Half A, 64 of the 200 camera rays of nee_flat at
+    maxBounceCount 1 whose path samples at vertex 0 and goes on into a segment that leaves the scene: no further vertex is shaded (one
+    would set cnPrev to 0 itself: vertex 1 takes no sample), so the lane's path ends with cnPrev = cn' > 0.  Half B, 64 rays aimed
+    straight at the emissive sphere, which has an entry: the first hit is an emitter, added in full — weighted by a dead path's cosine it
+    would be wb < 1 of it.  A then B, and B then A: the reference's records, and B's the same bytes in both orders."""
+    t0 = time.perf_counter()
+    abi = pkg.abi
+    sc, p, cam, _, est = case(pkg, api, orc, "nee_flat", 1)
+    assert p.maxBounceCount == 1
+    sampled = {i for (i, v, *_r) in est.sample_log if v == 0}
+    went_on = {i for (i, v, _, _) in est.segment_log if v == 1}
+    shaded_again = {i for (i, v, *_r) in est.emission_log if v == 1}   # (no glass in nee_flat: every hit of a second segment is an opaque one, and logged here)
+    assert not (sc.models["material"]["flag"] == abi.MATERIAL_GLASS).any() and not (sc.spheres["material"]["flag"] == abi.MATERIAL_GLASS).any()
+    keep = sorted((sampled & went_on) - shaded_again)
+    assert len(keep) >= 16, f"only {len(keep)} of the 200 camera rays sample at vertex 0 and then leave the scene"
+    half_a = cam[np.resize(np.array(keep), 64)]
+    emitter = 1   # sphere 1: r = 0.4 at (-2.5, 2.5, 0.5), Le = 9, diffuseCol 0
+    centre, radius = sc.spheres["centre"][emitter].astype(np.float64), float(sc.spheres["radius"][emitter])
+    assert est.table["in_table"][emitter] and radius == F(0.4)
+    k = np.arange(64)
+    phi, cos_t = 2.399963 * k, 0.15 + 0.8 * (k + 0.5) / 64     # a spiral over the upper half of directions: nothing stands between
+    u = np.stack([np.sqrt(1 - cos_t ** 2) * np.cos(phi), cos_t, np.sqrt(1 - cos_t ** 2) * np.sin(phi)], axis=1)
+    half_b = abi.make_path_rays(centre + 1.5 * u, -u, 7000 + 31 * k)
+    tr = gn.hip_tracer(api, sc, p)
+    try:
+        first = tr.query_closest(abi.make_rays(half_b["origin"], half_b["dir"]))
+        assert (first["object"] == emitter).all() and not (first["hit"] & abi.AOV_HIT_BACKFACE).any(), "every ray of half B hits the emitter first, from outside"
+        batches = {"A then B": np.concatenate([half_a, half_b]), "B then A": np.concatenate([half_b, half_a])}
+        want, want_nee = {}, {}
+        for what, rays in batches.items():
+            e = mr.Estimator(pkg, orc, tr, sc.models, sc.triangles, sc.spheres, p)
+            want[what] = e.trace(rays)
+            b = range(64, 128) if what == "A then B" else range(64)
+            assert sorted(e.plain_emission_log) == [(i, 0) for i in b], f"{what}: half B's emitter hits behind no sample"
+            a0 = 0 if what == "A then B" else 64
+            assert {i for (i, v, *_r) in e.sample_log if v == 0} >= set(range(a0, a0 + 64)) and not any(a0 <= i < a0 + 64 and v == 1 for (i, v, *_r) in e.emission_log)
+            want_nee[what] = nr.Estimator(pkg, orc, tr, sc.models, sc.triangles, sc.spheres, p).trace(rays)
+    finally:
+        tr.close()
+    monkeypatch.setenv("RT_GRID", "1")  # read at rt_create: two blocks, one wave
+    tr = api.create_tracer(0)
+    monkeypatch.delenv("RT_GRID")
+    try:
+        sc.upload(tr)
+        tr.set_params(p)
+        got = {what: tr.radiance_trace_mis(rays) for what, rays in batches.items()}
+        got_nee = {what: tr.radiance_trace_nee(rays) for what, rays in batches.items()}
+    finally:
+        tr.close()
+    for what in batches:
+        gn.assert_records(got[what], want[what], f"rt_mis_trace, {what}")
+        assert got[what].tobytes() == want[what].tobytes()
+        gn.assert_records(got_nee[what], want_nee[what], f"rt_nee_trace, {what}")
+        assert got_nee[what].tobytes() == want_nee[what].tobytes()
+    assert got["A then B"][64:].tobytes() == got["B then A"][:64].tobytes(), "half B's records depend on what the lanes did before"
+    assert got_nee["A then B"][64:].tobytes() == got_nee["B then A"][:64].tobytes()
+    assert got["A then B"][64:]["rgb"].any() and np.isfinite(got["A then B"]["rgb"]).all()
+    print(f"{len(keep)} distinct camera rays in half A; half B's records {np.unique(got['A then B'][64:]['rgb'], axis=0).shape[0]} distinct values; "
+          f"{time.perf_counter() - t0:.2f} s with the reference's six runs")
+
+
+# ---------------------------------------------------------------- the rules of emission_weight
+# One row per rule constant of tests/mis_reference.py: the case (scene, maxBounceCount as in case()) whose emission_log must hold the rule,
+# or None and why no table the library builds reaches it.  A rule marked unreachable must not be logged by ANY case: rules_allowed() is
+# called by every MIS test that runs the reference (here and in test_gpu_deep_trees.py, test_gpu_many_models.py and
+# test_gpu_hazards.py: four modules), so a change that makes one reachable is noticed where it happens.
+RULE_TABLE = [
+    (mr.WEIGHTED, "sphere", ("nee_flat", None), ""),
+    (mr.WEIGHTED, "triangle", ("nee_flat", None), ""),
+    (mr.NO_ENTRY_RULE, None, ("config3_bvh", None), ""),
+    (mr.INSIDE, "sphere", ("nee_inside", None), ""),
+    (mr.BACK, "triangle", "mis_back_light", "reached only through a model record whose worldToLocal contradicts its localToWorld (back_light_case): an opaque model is always "
+                                             "culled from behind, so no consistent scene hits a table triangle with cl <= 0"),
+    (mr.NOT_CONE, None, None, "needs a FRONT-face hit of a sphere from a segment origin inside it (d2 <= r2): a ray that starts inside a sphere leaves it through a back face"),
+    (mr.NOT_LOBE, None, None, "needs dot(n, normalize(n + RandomDirection)) <= 0 at a vertex that sampled: RandomDirection is a unit vector, so n + it lies in n's closed half space, "
+                              "and the sum is 0 (a NaN direction, which hits nothing) only for the one draw -n"),
+    (mr.NAN, None, None, "needs prob * d2 and cl * S both 0 or both inf, or pb + pl' not finite: the table's area rule keeps S finite and > 0 and prob in (0, 1], cl is in (0, 1], and the "
+                         "surface offset keeps d2 > 0"),
+]
+UNREACHABLE = {rule for (rule, _, where, _) in RULE_TABLE if where is None}
+
+
+def rules_allowed(est, what):
+    """no emission of this reference run was given its weight by a rule RULE_TABLE marks unreachable -> {rule: count}"""
+    seen = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
+    assert not set(seen) & UNREACHABLE, f"{what}: the reference logged {seen}; RULE_TABLE marks {sorted(set(seen) & UNREACHABLE)} unreachable"
+    return seen
+
+
+_BACK = {}
+
+
+def back_light_case(pkg, api, orc):
+    """near_light_scene's ceiling with the quad light FACING DOWN 4 cm under it: the light's back is towards the ceiling.  An opaque
+    model is culled from behind (RC:355: the flag alone decides, no record has a switch for it), so a ceiling vertex's lobe ray goes
+    THROUGH the quad; to be hit from behind the quad needs a second, front face towards the ceiling that is no entry's — not this rule.
+    What reaches `cl <= 0` is a light whose table normal and whose culling disagree: the model record's worldToLocal is that of the
+    quad turned over (facing up), its localToWorld — which alone the light table reads — the quad facing down.  The walk then finds
+    the quad from above, the table says it faces down: the sample is rejected (cl <= 0), the lobe ray hits, the emission is added in
+    full.  Rays straight up at the ceiling above the quad."""
+    if not _BACK:
+        M, T = pkg.RayTracingMaterial, pkg.Transform
+        ceiling = pkg.Model(pkg.meshes.quad(), M(diffuseCol=(0.8, 0.8, 0.8, 1), specularProbability=0.0), T((0, 3, 0), (-90, 0, 0), (20, 20, 1)), "Ceiling")
+        light = pkg.Model(pkg.meshes.quad(), M(diffuseCol=(0, 0, 0, 1), emissionCol=(1, 1, 1, 1), emissionStrength=10.0), T((0, 2.96, 0), (-90, 0, 0), (1, 1, 1)), "DownLight")
+        up = T((0, 2.96, 0), (90, 0, 0), (1, 1, 1))
+        cam = pkg.Camera(T((3, 1, 0), (0, -90, 0)), fieldOfView=60.0)
+        settings = dict(maxBounceCount=2, numRaysPerPixel=1, useSky=False, accumulate=True, bvhQuality=1)
+        sc = gn.SceneArrays(api, pkg.scenes.SceneDescription("mis_back_light", 64, 36, 1, settings, cam, [ceiling, light], []))
+        sc.models = sc.models.copy()
+        sc.models[1]["worldToLocal"] = pkg.manager.matrix_to_abi(up.worldToLocalMatrix)
+        p = rg.params_of(sc, api, 64, 36, {})
+        k = np.arange(96)
+        rays = pkg.abi.make_path_rays(np.stack([-0.4 + 0.8 * (k % 12) / 11, np.full(96, 2.0), -0.4 + 0.8 * (k // 12) / 7], axis=1), np.tile([0.0, 1.0, 0.0], (96, 1)), 300 + 17 * k)
+        tr = gn.hip_tracer(api, sc, p)
+        try:
+            est = mr.Estimator(pkg, orc, tr, sc.models, sc.triangles, sc.spheres, p)
+            want = est.trace(rays)
+            got = tr.radiance_trace_mis(rays)
+        finally:
+            tr.close()
+        _BACK.update(sc=sc, p=p, rays=rays, est=est, want=want, got=got)
+    return _BACK
+
+
+def test_every_rule_of_emission_weight_is_reached_or_reasoned_unreachable(pkg, api, orc):
+    t0 = time.perf_counter()
+    for rule, kind, where, why in RULE_TABLE:
+        if where is None:
+            assert why
+            continue
+        if where == "mis_back_light":
+            b = back_light_case(pkg, api, orc)
+            est, what = b["est"], where
+            assert b["got"].tobytes() == b["want"].tobytes(), "mis_back_light: rt_mis_trace != the reference"
+            assert np.isfinite(b["want"]["rgb"]).all() and b["want"]["rgb"].any()
+        else:
+            est, what = case(pkg, api, orc, *where)[4], f"{where[0]} bounce={where[1]}"
+        rows = [e for e in est.emission_log if e[3] == rule and (kind is None or e[4] == kind)]
+        print(f"{rule} ({kind or 'any'}): {len(rows)} rows in {what}")
+        assert rows, f"{what} logs no emission under the rule {rule!r} ({kind})"
+        assert all(e[2] == 1.0 for e in rows) or rule == mr.WEIGHTED, "every rule but `weighted` adds the emission in full"
+    for (name, bounce), c in sorted(_CASES.items(), key=str):
+        rules_allowed(c[4], f"{name} bounce={bounce}")
+    rules_allowed(back_light_case(pkg, api, orc)["est"], "mis_back_light")
+    print(f"{len(_CASES)} cached cases checked against UNREACHABLE; {time.perf_counter() - t0:.2f} s with the reference runs not cached before")
 
 
 # ---------------------------------------------------------------- 3. the identities
@@ -343,7 +499,8 @@ def test_same_expectation_as_plain_radiance(pkg, api, orc, name, bounce):
 
 # ---------------------------------------------------------------- 7. the side-pass manners
 def test_device_form_launches_held_back_frames_first_like_a_flushes_row(pkg, api, orc, monkeypatch):
-    """What tests/test_gpu_held_back.py checks for a `flushes` row: with RT_HOLD_BACK=1 and three frames held, none is pending after the
+    """What tests/test_gpu_held_back.py checks for the call's `flushes` rows (tests/flush_table.py: rt_mis_trace and its device_form case,
+    which tests/test_flush_table.py finds through the descriptor's context member), here with the records of the pass compared as well: with RT_HOLD_BACK=1 and three frames held, none is pending after the
     call, and the final image, the last frame and the frame counter are those of an eager twin context (RT_COALESCE=0)."""
     abi = pkg.abi
     results = []

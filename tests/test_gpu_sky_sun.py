@@ -211,7 +211,7 @@ def test_the_bit_follows_the_launch_not_the_context(pkg, api, orc, make_scene):
 
 
 def test_a_side_pass_keeps_the_whole_function(pkg, api, orc):
-    """rt_radiance_trace takes the caller's direction as it is.  (0, -1e30, 0) past the ground's edge under the default sun:
+    """rt_radiance_trace, rt_nee_trace and rt_mis_trace take the caller's direction as it is.  (0, -1e30, 0) past the ground's edge under the default sun:
     pow(1e30, 2) = inf and inf * 0 = NaN in GetEnvironmentLight, 0.35 / 0.3 / 0.35 without the sun's addend.  The context's frame
     launches carry the bit; the batch must not."""
     sc, (w, h) = flat_scene(pkg)
@@ -227,6 +227,7 @@ def test_a_side_pass_keeps_the_whole_function(pkg, api, orc):
             rays = pkg.abi.make_path_rays(origins, dirs, np.array([1, 2, 3], dtype=np.uint32))
             got = tr.radiance_trace(rays)
             nee = tr.radiance_trace_nee(rays)
+            mis = tr.radiance_trace_mis(rays)
             hits = tr.query_closest(pkg.abi.make_rays(origins, dirs))
             mgr.RenderFrames(1)   # and the frames go on
             image = tr.read_accumulated()
@@ -242,6 +243,8 @@ def test_a_side_pass_keeps_the_whole_function(pkg, api, orc):
     assert np.isnan(want[0]).all() and np.isfinite(want[1:]).all()
     assert same(got["rgb"], want), (got["rgb"], want)
     assert same(nee["rgb"], want), (nee["rgb"], want)
+    assert same(mis["rgb"], want), (mis["rgb"], want)
+    assert np.array_equal(mis["rng"], got["rng"]) and np.array_equal(nee["rng"], got["rng"]), "a ray that misses draws nothing in any of the three passes"
     c = orc.create_tracer(8)
     mgr = flat_scene(pkg)[0].make_manager(c, orc, w, h)
     mgr.OnEnable(renderSeed=3)

@@ -144,6 +144,48 @@ def test_debug_light_map_needs_no_device_and_matches_the_numpy_map(pkg, api):
     api.debug_light_map_free(C.byref(d))
 
 
+def test_the_far_emitter_is_an_entry_that_is_neither_sampled_nor_hit(pkg, api, orc):
+    """The scene meant to give weights of exactly 0: tests/hazard_scenes.py's bvh base (config 3's room without its back wall) with an
+    emissive sphere of radius 1e19 centred 3e19 behind the missing wall.  r2 = 1e38 is finite, d2 = 9e38 overflows to inf, so s2 = q = 0,
+    pl' = inf and, by the header's rule, wb = pb / (pb + inf) = 0 for a lobe ray that reaches it — but nothing does, and no sample is
+    ever taken either, so no GPU case is built on it:
+      * the table takes the sphere (the library's and the numpy one), with prob = 1 to fp32: its power dwarfs the room's light;
+      * the sampler: z = normalize(w) = w * rsqrt(inf) = 0, ct = 1, st = 0, so omega = 0 and cn = dot(n, 0) = 0: "nothing is added";
+      * the intersection: c = dot(offset, offset) - r2 = inf, discriminant = b * b - 4 * a * c = inf - inf = NaN: a miss, for every ray.
+    Held here without a GPU, from the oracle's RaySphere and the reference's sampler, so that a change of either is noticed."""
+    import ctypes
+    import hazard_scenes as hz
+
+    def scene(pkg_, sc, t_):
+        M = pkg_.RayTracingMaterial
+        sc.spheres.append(pkg_.Sphere((0.0, 2.0, 3e19), 1e19, M(diffuseCol=(0, 0, 0, 1), emissionCol=(1, 0.9, 0.7, 1), emissionStrength=5.0)))
+    rig = hz.Rig(pkg, orc, "bvh", hz.Case("far-emitter", "model", "shade", "on", scene=scene))
+    assert len(rig.spheres) == 1 and rig.spheres["radius"][0] == np.float32(1e19)
+    est = mr.Estimator(pkg, orc, None, rig.models, rig.triangles, rig.spheres, rig.params(1))
+    table = est.table
+    got = api.light_table_arrays(rig.models, rig.triangles, rig.spheres)
+    assert got["entries"].tobytes() == table["entries"].tobytes() and got["cdf"].tobytes() == table["cdf"].tobytes()
+    assert table["in_table"][0] and table["n_sphere_entries"] == 1 and table["entries"][0]["size"] == np.float32(1e38) and table["entries"][0]["prob"] == 1.0
+    assert api.light_map_arrays(rig.models, rig.triangles, rig.spheres)["objects"][0] == 0
+    x, n = np.array([0.3, 1.0, 1.0], dtype=np.float32), np.array([0, 0, 1], dtype=np.float32)
+    with np.errstate(all="ignore"):
+        for state in range(1, 33):
+            assert est.sample(ctypes.c_uint32(state), x, n) is None
+        assert est.samples == 32 and est.triangle_samples == 0 and est.inside == 0, "every draw picks the sphere, is outside it, and is rejected at cn > 0"
+        wb, rule = est.emission_weight(0, -1, False, np.float32(0.5), x, n, np.array([0, 0, 2e19], dtype=np.float32))
+        assert (float(wb), rule) == (0.0, mr.WEIGHTED), "the weight a hit would get"
+    ot = orc.create_tracer(1)
+    try:
+        rig.upload(ot)
+        F3, out = ctypes.c_float * 3, (ctypes.c_float * 10)()
+        for d in ((0, 0, 1), (0.01, 0.02, 1), (0.2, 0.1, 1), (-0.3, 0.05, 1)):
+            d = np.array(d, dtype=np.float64) / np.linalg.norm(d)
+            orc.ray_collision(ot.h, F3(0.3, 1.0, 1.0), F3(*d), out)
+            assert out[0] == 0.0, f"the ray along {d} hits {list(out)}"
+    finally:
+        ot.close()
+
+
 def test_mis_map_driver_is_clean_under_address_and_undefined_sanitizers(tmp_path):
     """The table and the map of generated scenes (instances, mirrored, dark and glass models, zero-area triangles, excluded spheres),
     the packed device words and the lookup for every hit and for triangles outside a model's range.  A program of its own: nothing
