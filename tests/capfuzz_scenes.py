@@ -293,3 +293,36 @@ def triangle_scene_file(pkg, api, d, cfg, w, h, part=(8, 0, 1), change=None, tag
     if change:
         change(sc)
     return write_triangle_scene(pkg, api, sc, str(d / f"config{cfg}{tag}_{w}x{h}_{part[1]}of{part[2]}.txt"), w, h, part)
+
+
+WALK_SEEDS = (2, 4, 6, 12, 13, 18, 22)        # scenes with spheres and models
+OTHER_IN_CAP = (19, 11, 3, 23, 20, 6, 12)     # what upload_scene replaces them with
+STEPS = 10
+
+
+def _walk(pkg, seed):
+    """the walk of a seed as plain data, so that the library's manager and the oracle's take the very same steps.  Four of the six plain
+    kinds (which two are left out rotates with the seed) and the six that come once per walk, shuffled; the second in-cap upload comes
+    two steps after the over-the-cap one and defocus goes on early enough to go off again two steps later."""
+    d = _Draw(pkg, 7919 * seed + 1)
+    plain = ["sphere", "model", "camera", "fov", "diverge", "reset"]
+    idx = WALK_SEEDS.index(seed)
+    for k in sorted({idx % 6, (idx + 3) % 6}, reverse=True):
+        del plain[k]
+    kinds = plain + ["defocus", "resize_same_tiles", "resize", "upload_in_cap", "upload_over_a_cap", "upload_in_cap_again"]
+    assert len(kinds) == STEPS
+    for i in range(len(kinds) - 1, 0, -1):
+        j = int(d.rnd() * (i + 1))
+        kinds[i], kinds[j] = kinds[j], kinds[i]
+    if kinds.index("defocus") > STEPS - 3:
+        kinds.remove("defocus")
+        kinds.insert(int(d.rnd() * (STEPS - 2)), "defocus")
+    kinds.remove("upload_in_cap_again")   # over a cap for two steps, not for most of the walk: the steps are there to change a table's key
+    kinds.insert(min(kinds.index("upload_over_a_cap") + 2, len(kinds)), "upload_in_cap_again")
+    if kinds.index("defocus") > STEPS - 3:   # (pushed back by the insertion)
+        kinds.remove("defocus")
+        kinds.insert(0, "defocus")
+    steps = []
+    for i, kind in enumerate(kinds):
+        steps.append(dict(kind=kind, u=[d.rnd() for _ in range(12)], k=2 + int(d.rnd() * 4), over=idx % 3, other=OTHER_IN_CAP[idx] if kind == "upload_in_cap" else seed))
+    return steps

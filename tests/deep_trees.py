@@ -24,6 +24,8 @@ occupancy() is written from the prose above traverse() in ray-tracing_amd/csrc/r
 ... each lane walks its own (model, node) sequence", "push far, then near; the next pop is the near child, so it stays in `cur`") and
 from RC:219-287 — not from the kernel's code: a float32 walk, near child first, the far child pushed only if `dstFar < dst`, that
 returns the largest number of entries the stack held.  Test infrastructure: nothing here is imported by the product."""
+import re
+
 import numpy as np
 
 F = np.float32
@@ -327,3 +329,45 @@ def witness_share(nodes, triangles, p, w, h, max_height, cull=False):
     occ = occupancies(nodes, triangles, p, w, h, cull)
     assert occ.max() <= max_height, (int(occ.max()), max_height)
     return float((occ == max_height).mean())
+
+
+LAUNCH = re.compile(r"kernel variant (\d+): (\d+) stack entries, (\d+) B of LDS per workgroup of (\d+) threads \((\d+) B of it the top-of-tree cache: (\d+) records\)")
+
+
+def launches(capfd):
+    """(variant, stack entries, LDS bytes, threads, cache records) of every launch shape reported since the last call"""
+    return [tuple(int(g) for g in (m.group(1), m.group(2), m.group(3), m.group(4), m.group(6))) for m in LAUNCH.finditer(capfd.readouterr().err)]
+
+
+CATCHER_Z = -0.05              # tests/test_gpu_deep_trees.py::nee_scene: a small diffuse quad behind deep_trees.camera that faces the comb
+CATCHER_POINT = (0.1, -0.05)   # where that file's witness ray (from z = 1 along -z) meets it
+
+
+def cone_mesh(n=40, ratio=8.0, size=0.3, scale=2.0 ** 34):
+    """A self-similar cone: triangle k is centred at x = scale * ratio^-k on the x axis, its size in proportion.  Whatever the evenly
+    spaced split tests of a node are, they separate its outermost triangle from all the others (the next centre lies at 1/8 of the
+    extent, the first test at 1/6 or 1/4), so the builder peels one triangle per level until the reference's MaxDepth = 32 stops it:
+    leaves at depth 1 ... 32, the deepest with the n - 32 innermost triangles.  The coordinates span 2^34 ... 2^-83: the surface-area
+    cost (squares of them) of the smallest nodes stays a normal float32 — it would underflow to 0, and end the splitting at depth 25, if
+    the cone began at 1."""
+    v, idx = [], []
+    for k in range(n):
+        c = scale * ratio ** -k
+        s = size * c
+        v += [(c - s, -s, -0.5 * s), (c + s, -s, 0.5 * s), (c, s, 0.0)]
+        idx += [3 * k, 3 * k + 1, 3 * k + 2]
+    v = np.array(v, dtype=F)
+    v64 = v.astype(np.float64)  # (in float32 the cross products of the smallest triangles underflow)
+    nrm = np.cross(v64[1::3] - v64[0::3], v64[2::3] - v64[0::3])
+    nrm = np.repeat(nrm / np.linalg.norm(nrm, axis=1, keepdims=True), 3, axis=0).astype(F)
+    return v, nrm, np.array(idx, dtype=np.int32)
+
+
+CONE_SCALE = 2.0 ** -32   # model scale of the cone in a scene: its largest triangle then stands at x = 4
+
+
+def cone_camera(pkg, where):
+    """apex: at the cone's tip looking along its axis, every box in front of it one inside the other; outside: from the side"""
+    if where == "apex":
+        return pkg.Camera(pkg.Transform((0, 0, 0), (0, 90, 0)), fieldOfView=8.0)
+    return pkg.Camera(pkg.Transform((2.0, 0.3, -7.0), (0, 0, 0)), fieldOfView=50.0)

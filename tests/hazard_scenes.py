@@ -37,6 +37,7 @@ import sys
 import numpy as np
 
 import capfuzz_scenes as cs
+from fuzz_scenes import crowded_overflow_scene
 
 NAN, INF = float("nan"), float("inf")
 BASES = ("flat-tables", "flat-general", "bvh", "many")
@@ -88,11 +89,7 @@ def base_scene(pkg, base):
         sc.settings.update(numRaysPerPixel=2, maxBounceCount=5)
         sc.models = [m for m in sc.models if m.name != "WallBack"]
     elif base == "many":   # more than 64 models: the two-level filter
-        here = os.path.dirname(os.path.abspath(__file__))
-        if here not in sys.path:
-            sys.path.insert(0, here)
-        import test_gpu_fuzz
-        sc, seed = test_gpu_fuzz.crowded_scene(pkg, 70, 5), 11
+        sc, seed = crowded_overflow_scene(pkg, 70, 5), 11
     else:
         raise KeyError(base)
     # every base has the sky on and the sun above the horizon (the default direction is straight down: never seen), so that a sky

@@ -6,7 +6,7 @@ a 63-bit register mask for models 0 ... 62; up to 32 extension words in the lane
 word; models from index 1087 on, which no filter sees and which are walked in index order; and, in the trace kernel, one more LDS row
 behind the extension for the bounce count.  The catalogue:
 
-  crowd<n>            tests/test_gpu_fuzz.py::crowded_scene with n models and no spheres, n in N_EDGES: the last model of word 0 (94), the
+  crowd<n>            tests/fuzz_scenes.py::crowded_overflow_scene with n models and no spheres, n in N_EDGES: the last model of word 0 (94), the
                       first of word 1 (95), 96, word 1 full (127), word 31 one short of full (1086), the cap (1087), one and two models
                       behind it, a tail of 213.
   stairs-near_first   N_STAIRS plates (one small mesh with an inner root), one behind the other, all around the ray of pixel W_PIXEL: the
@@ -38,6 +38,7 @@ if HERE not in sys.path:
 
 import deep_trees as dt  # noqa: E402
 import hazard_scenes as hz  # noqa: E402
+from fuzz_scenes import crowded_overflow_scene  # noqa: E402
 
 N_EDGES = (94, 95, 96, 127, 1086, 1087, 1088, 1089, 1300)
 FILTER_CAP = 1087                      # 63 + 32 * RT_MAX_FILTER_EXT_WORDS: models from this index on are not filtered
@@ -102,7 +103,7 @@ def plate_of_depth(order, z, n=N_STAIRS):
 
 
 def _material(pkg, i, rng):
-    """tests/test_gpu_fuzz.py::crowded_scene's mix: every fourth model glass, every ninth emitting"""
+    """tests/fuzz_scenes.py::crowded_overflow_scene's mix: every fourth model glass, every ninth emitting"""
     return pkg.RayTracingMaterial(flag=int(i % 4 == 3) * 2, diffuseCol=tuple(rng.uniform(0.2, 1, 3)) + (1,), ior=1.4,
                                   emissionStrength=float(i % 9 == 0) * 3.0, emissionCol=(1, 0.9, 0.7, 1))
 
@@ -111,8 +112,7 @@ SETTINGS = dict(maxBounceCount=5, numRaysPerPixel=2, defocusStrength=0.0, diverg
 
 
 def _crowd(pkg, n):
-    import test_gpu_fuzz as tf
-    sc = tf.crowded_scene(pkg, n, 0)
+    sc = crowded_overflow_scene(pkg, n, 0)
     assert len(sc.models) == n and not sc.spheres
     return dt.description(pkg, f"crowd{n}", sc.models, sc.camera, w=CROWD_SIZE[0], h=CROWD_SIZE[1], **dict(SETTINGS, **sc.settings))
 

@@ -269,3 +269,30 @@ class Estimator(nr.Estimator):
                 gone = set(ended)
                 active = np.array([i for i in active if i not in gone], dtype=np.int64)
         return out
+
+
+# One row per rule constant above: the case (scene, maxBounceCount as in tests/test_gpu_mis.py's case()) whose emission_log must hold the rule,
+# or None and why no table the library builds reaches it.  A rule marked unreachable must not be logged by ANY case: rules_allowed() is
+# called by every MIS test that runs the reference (test_gpu_mis.py, test_gpu_deep_trees.py, test_gpu_many_models.py and
+# test_gpu_hazards.py: four modules), so a change that makes one reachable is noticed where it happens.
+RULE_TABLE = [
+    (WEIGHTED, "sphere", ("nee_flat", None), ""),
+    (WEIGHTED, "triangle", ("nee_flat", None), ""),
+    (NO_ENTRY_RULE, None, ("config3_bvh", None), ""),
+    (INSIDE, "sphere", ("nee_inside", None), ""),
+    (BACK, "triangle", "mis_back_light", "reached only through a model record whose worldToLocal contradicts its localToWorld (back_light_case): an opaque model is always "
+                                             "culled from behind, so no consistent scene hits a table triangle with cl <= 0"),
+    (NOT_CONE, None, None, "needs a FRONT-face hit of a sphere from a segment origin inside it (d2 <= r2): a ray that starts inside a sphere leaves it through a back face"),
+    (NOT_LOBE, None, None, "needs dot(n, normalize(n + RandomDirection)) <= 0 at a vertex that sampled: RandomDirection is a unit vector, so n + it lies in n's closed half space, "
+                              "and the sum is 0 (a NaN direction, which hits nothing) only for the one draw -n"),
+    (NAN, None, None, "needs prob * d2 and cl * S both 0 or both inf, or pb + pl' not finite: the table's area rule keeps S finite and > 0 and prob in (0, 1], cl is in (0, 1], and the "
+                         "surface offset keeps d2 > 0"),
+]
+UNREACHABLE = {rule for (rule, _, where, _) in RULE_TABLE if where is None}
+
+
+def rules_allowed(est, what):
+    """no emission of this reference run was given its weight by a rule RULE_TABLE marks unreachable -> {rule: count}"""
+    seen = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
+    assert not set(seen) & UNREACHABLE, f"{what}: the reference logged {seen}; RULE_TABLE marks {sorted(set(seen) & UNREACHABLE)} unreachable"
+    return seen

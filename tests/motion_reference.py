@@ -6,6 +6,7 @@ Every array operation below is one IEEE binary32 operation per element (NumPy do
 tests/reproject_reference.py's, whose divide is the oracle's."""
 import numpy as np
 
+import aov_support as ga
 import reproject_reference as ref
 
 F = np.float32
@@ -66,8 +67,7 @@ def motion_from_scene(prev_spheres, cur_spheres, prev_models, cur_models):
 # ---------------------------------------------------------------- A. the centre ray
 def centre_rays(orc, p, w, h, rows=None):
     """Origin and direction of the pixel-centre ray for every pixel of the global rows `rows` (default: all) of a w x h image, (len(rows), w,
-    3) float32 each: uv and focusPoint as tests/test_gpu_aov.py::camera_rays restates them, the origin the camera's, no draw."""
-    import test_gpu_aov as ga
+    3) float32 each: uv and focusPoint as tests/aov_support.py::camera_rays restates them, the origin the camera's, no draw."""
     ieee = b"RT_MATH_IEEE" in orc.version()
     rows = np.arange(h) if rows is None else np.asarray(rows)
     with np.errstate(all="ignore"):

@@ -7,6 +7,8 @@ import ctypes as C
 
 import numpy as np
 
+from gpu_support import bits
+
 F = np.float32
 F3 = C.c_float * 3
 
@@ -93,5 +95,25 @@ def divide(orc, x, y):
     return oracle_eval(orc, 6, x, y)
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
+FRAME = 3
+
+
+NO_DOF = dict(defocusStrength=0.0, divergeStrength=0.0)
+
+
+def params_of(sc, api, w, h, tweak):
+    """The RtParams the scene's manager would set at w x h with `tweak` applied (no tracer involved)."""
+    mgr = sc.desc.make_manager(None, api, w, h)
+    for k, v in tweak.items():
+        assert hasattr(mgr, k), k
+        setattr(mgr, k, v)
+    mgr.renderSeed = 5
+    p = mgr.params()
+    p.frame = FRAME
+    return p
+
+
+def assert_rgb(got, want, what):
+    a, b = bits(got).reshape(-1, 3), bits(want).reshape(-1, 3)
+    bad = np.argwhere((a != b).any(axis=1)).ravel()
+    assert not len(bad), f"{what}: {len(bad)} of {len(a)} rays differ; first is ray {bad[0]}: got {got.reshape(-1, 3)[bad[0]]}, want {want.reshape(-1, 3)[bad[0]]}"

@@ -6,7 +6,6 @@ the NumPy restatement of the header's prose (tests/adaptive_reference.py) bit fo
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -14,6 +13,7 @@ import numpy as np
 import pytest
 
 import adaptive_reference as ref
+import host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -125,12 +125,8 @@ def test_every_parameter_error_of_the_header_is_refused(pkg, api, driver):
 
 
 # ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
-def build_driver(exe, extra=()):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra,
-                           os.path.join(ROOT, "tests", "adaptive_math_driver.cpp"), "-o", exe])
+def build_driver(directory, exe, extra=()):
+    return host_driver.build(directory, "adaptive_math", ["-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", *extra], exe=exe)
 
 
 class Driver:
@@ -161,9 +157,7 @@ class Driver:
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("adaptive_math") / "driver")
-    build_driver(exe)
-    return Driver(exe)
+    return Driver(build_driver(tmp_path_factory.mktemp("adaptive_math"), "driver"))
 
 
 def same_bits(got, want, what):
@@ -260,9 +254,7 @@ def test_the_check_of_a_callers_tile_list(driver):
 
 # ---------------------------------------------------------------- 7. the driver under the sanitizers
 def test_driver_is_clean_under_address_and_undefined_sanitizers(orc, tmp_path):
-    exe = str(tmp_path / "driver_san")
-    build_driver(exe, extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"))
-    d = Driver(exe)
+    d = Driver(build_driver(tmp_path, "driver_san", extra=("-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all")))
     ps = ref.PARAM_SETS[0]
     s, m, _ = ref.hazard_images(9, 17, seed=26, **ps)
     got = d.select(s, m, **ps)

@@ -22,6 +22,7 @@ import numpy as np
 import pytest
 
 import deep_trees as dt
+from deep_trees import CATCHER_POINT, CATCHER_Z, CONE_SCALE, cone_camera, cone_mesh
 
 F = np.float32
 F3 = C.c_float * 3
@@ -152,8 +153,6 @@ def test_conditions_the_gpu_half_rests_on(pkg, api, height, form):
         assert share >= 0.5
 
 
-CATCHER_Z = -0.05              # tests/test_gpu_deep_trees.py::nee_scene: a small diffuse quad behind deep_trees.camera that faces the comb
-CATCHER_POINT = (0.1, -0.05)   # where that file's witness ray (from z = 1 along -z) meets it
 NEE_COMBS = [(1, "alternate"), (31, "alternate"), (32, "alternate"), (32, "tied")]
 
 
@@ -247,29 +246,6 @@ def test_oracle_traversal_of_comb_32_equals_bruteforce(pkg, orc):
 
 
 # ---------------------------------------------------------------- a depth-32 tree from the builder
-def cone_mesh(n=40, ratio=8.0, size=0.3, scale=2.0 ** 34):
-    """A self-similar cone: triangle k is centred at x = scale * ratio^-k on the x axis, its size in proportion.  Whatever the evenly
-    spaced split tests of a node are, they separate its outermost triangle from all the others (the next centre lies at 1/8 of the
-    extent, the first test at 1/6 or 1/4), so the builder peels one triangle per level until the reference's MaxDepth = 32 stops it:
-    leaves at depth 1 ... 32, the deepest with the n - 32 innermost triangles.  The coordinates span 2^34 ... 2^-83: the surface-area
-    cost (squares of them) of the smallest nodes stays a normal float32 — it would underflow to 0, and end the splitting at depth 25, if
-    the cone began at 1."""
-    v, idx = [], []
-    for k in range(n):
-        c = scale * ratio ** -k
-        s = size * c
-        v += [(c - s, -s, -0.5 * s), (c + s, -s, 0.5 * s), (c, s, 0.0)]
-        idx += [3 * k, 3 * k + 1, 3 * k + 2]
-    v = np.array(v, dtype=F)
-    v64 = v.astype(np.float64)  # (in float32 the cross products of the smallest triangles underflow)
-    nrm = np.cross(v64[1::3] - v64[0::3], v64[2::3] - v64[0::3])
-    nrm = np.repeat(nrm / np.linalg.norm(nrm, axis=1, keepdims=True), 3, axis=0).astype(F)
-    return v, nrm, np.array(idx, dtype=np.int32)
-
-
-CONE_SCALE = 2.0 ** -32   # model scale of the cone in a scene: its largest triangle then stands at x = 4
-
-
 def test_builders_agree_on_a_mesh_they_take_to_depth_32(pkg, api, orc):
     import __graft_entry__ as graft
     v, nrm, idx = cone_mesh()
@@ -298,8 +274,3 @@ def test_builders_agree_on_a_mesh_they_take_to_depth_32(pkg, api, orc):
     assert occ.max() == 32 and (occ == 32).mean() >= 0.5
 
 
-def cone_camera(pkg, where):
-    """apex: at the cone's tip looking along its axis, every box in front of it one inside the other; outside: from the side"""
-    if where == "apex":
-        return pkg.Camera(pkg.Transform((0, 0, 0), (0, 90, 0)), fieldOfView=8.0)
-    return pkg.Camera(pkg.Transform((2.0, 0.3, -7.0), (0, 0, 0)), fieldOfView=50.0)

@@ -6,7 +6,6 @@ bit, every pixel, every channel."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
@@ -14,6 +13,8 @@ import numpy as np
 import pytest
 
 import denoise_reference as ref
+import host_driver
+from gpu_support import assert_same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -95,12 +96,7 @@ def test_default_params_are_valid(pkg, api):
 # ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("denoise_math") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "denoise_math_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path_factory.mktemp("denoise_math"), "denoise_math", ["-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
 
     def run(rgba, aov, iterations, sc, sn, sp, demodulate, scale, via_file=None):
         h, w = rgba.shape[:2]
@@ -113,15 +109,6 @@ def driver(tmp_path_factory):
             out = subprocess.run([exe], input=blob, capture_output=True, timeout=600, check=True).stdout
         return np.frombuffer(out, dtype=np.float32).reshape(h, w, 4)
     return run
-
-
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    if len(bad):
-        y, x, k = bad[0]
-        raise AssertionError(f"{what}: {len(set(map(tuple, bad[:, :2])))} pixels differ; first at row {y}, column {x}, channel {k}: "
-                             f"got {got[y, x]}, want {want[y, x]}")
 
 
 def test_the_synthetic_image_covers_what_it_is_there_for(pkg):

@@ -32,6 +32,19 @@ def test_coverage_md_cites_tests_and_files_that_exist():
         assert os.path.exists(os.path.join(ROOT, path.rstrip("/"))) or path.startswith("oracle/_ref"), path
 
 
+def test_no_module_imports_a_test_module():
+    """What two files share lives in a plain module (gpu_support.py, host_driver.py, *_support.py, *_scenes.py, *_reference.py), never in a
+    test_*.py.  The raw text is scanned, so the scripts that tests keep in strings for their child processes are held to it too."""
+    bad = []
+    for d, _, files in os.walk(os.path.join(ROOT, "tests")):
+        for f in sorted(files):
+            if f.endswith(".py"):
+                for i, line in enumerate(open(os.path.join(d, f)).read().splitlines(), 1):
+                    if re.match(r"^\s*(import|from)\s+test_", line):
+                        bad.append(f"{os.path.relpath(os.path.join(d, f), ROOT)}:{i}: {line.strip()}")
+    assert not bad, "\n".join(bad)
+
+
 def test_profiles_readme_lists_files_that_exist():
     text = open(os.path.join(ROOT, "profiles", "README.md")).read()
     names = set(re.findall(r"`(r0[1-4]_[A-Za-z_0-9.]+\.(?:txt|json))`", text))

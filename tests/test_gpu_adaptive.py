@@ -24,7 +24,7 @@ import pytest
 
 import adaptive_reference as aref
 import variance_reference as vref
-from test_gpu_denoise import DevBuf
+from gpu_support import DevBuf
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

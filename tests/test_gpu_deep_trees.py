@@ -30,18 +30,17 @@ import time
 import numpy as np
 import pytest
 
+import aov_support as ta
+import cost_view_support as tc
 import deep_trees as dt
 import mis_reference as mr
 import motion_reference as mref
 import nee_reference as nr
 import radiance_reference as rr
-import test_gpu_aov as ta
-import test_gpu_cost_view as tc
-import test_gpu_fuzz as tf
-import test_gpu_mis as tm
-import test_gpu_query as tq
-from test_deep_trees import CATCHER_POINT, CATCHER_Z, CONE_SCALE, cone_camera, cone_mesh
-from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
+import query_support as tq
+from cost_view_support import orc_log  # noqa: F401  (fixture)
+from deep_trees import CATCHER_POINT, CATCHER_Z, CONE_SCALE, cone_camera, cone_mesh, launches
+from gpu_support import KEYS, DevBuf, bits
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -56,7 +55,7 @@ _SCENES, _ORACLE, _REF = {}, {}, {}
 # ---------------------------------------------------------------- scenes
 def crowd(pkg, n, seed=3):
     """n small models between the camera and the comb and beside it: cubes, rounded cubes and quads, every fourth glass, every ninth
-    emitting (tests/test_gpu_fuzz.py::crowded_scene's mix, placed for deep_trees.camera)"""
+    emitting (tests/fuzz_scenes.py::crowded_overflow_scene's mix, placed for deep_trees.camera)"""
     rng = np.random.default_rng(seed)
     M, T = pkg.RayTracingMaterial, pkg.Transform
     meshes = [pkg.meshes.cube(), pkg.meshes.rounded_cube(3), pkg.meshes.quad()]
@@ -142,7 +141,7 @@ def render(lib, tr, desc, stats=False, seed=9):
     mgr.RenderFrame()
     c = tr.counters()
     prof = tr.phase_profile() if stats else None
-    out = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in tf.KEYS],
+    out = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in KEYS],
                viol=prof["filter_violations"][0] if stats else 0, hot=prof["inner_from_lds_cache"][0] if stats else None)
     tr.close()
     return out
@@ -170,19 +169,11 @@ def assert_render(got, want, what, stats):
     assert same(got["acc"], want["acc"]), f"{what}: accumulated image differs in {int((got['acc'] != want['acc']).any(axis=-1).sum())} pixels"
     assert same(got["frame"], want["frame"]), f"{what}: last frame differs in {int((got['frame'] != want['frame']).any(axis=-1).sum())} pixels"
     if stats:
-        assert got["counters"] == want["counters"], (what, dict(zip(tf.KEYS, got["counters"])), dict(zip(tf.KEYS, want["counters"])))
+        assert got["counters"] == want["counters"], (what, dict(zip(KEYS, got["counters"])), dict(zip(KEYS, want["counters"])))
         assert got["viol"] == 0, what
     else:  # the shipped instantiation counts segments and pixel frames only
         for k in ("segments", "pixelFrames"):
-            assert got["counters"][tf.KEYS.index(k)] == want["counters"][tf.KEYS.index(k)], (what, k)
-
-
-LAUNCH = re.compile(r"kernel variant (\d+): (\d+) stack entries, (\d+) B of LDS per workgroup of (\d+) threads \((\d+) B of it the top-of-tree cache: (\d+) records\)")
-
-
-def launches(capfd):
-    """(variant, stack entries, LDS bytes, threads, cache records) of every launch shape reported since the last call"""
-    return [tuple(int(g) for g in (m.group(1), m.group(2), m.group(3), m.group(4), m.group(6))) for m in LAUNCH.finditer(capfd.readouterr().err)]
+            assert got["counters"][KEYS.index(k)] == want["counters"][KEYS.index(k)], (what, k)
 
 
 # ---------------------------------------------------------------- a. the trace kernels
@@ -196,7 +187,7 @@ TRACE_SCENES = ([f"comb{h}{form}" + ("-diffuse" if form == "B" else "") for h in
 def test_trace_kernels_fill_the_last_stack_row(pkg, api, orc, name, monkeypatch, capfd):
     desc, height = scene(pkg, name), height_of(name)
     want = oracle_render(pkg, orc, name)
-    assert want["counters"][tf.KEYS.index("innerSteps")] > 0 and np.isfinite(want["acc"]).all() and want["acc"][..., :3].any()
+    assert want["counters"][KEYS.index("innerSteps")] > 0 and np.isfinite(want["acc"]).all() and want["acc"][..., :3].any()
     t0 = time.perf_counter()
     monkeypatch.setenv("RT_DEBUG_LAUNCH", "1")
     monkeypatch.delenv("RT_LAYOUT", raising=False)
@@ -219,7 +210,7 @@ def test_trace_kernels_fill_the_last_stack_row(pkg, api, orc, name, monkeypatch,
         if shape == "single":
             assert seen[shape] == [(64, 0)], (name, seen)
         if shape == "cache16" and height == 30:  # 16 records of 30 pairs: a walk alternates between the LDS copy and global memory
-            assert seen[shape][0][1] == 16 and 0 < got["hot"] < want["counters"][tf.KEYS.index("innerSteps")], (name, seen, got["hot"])
+            assert seen[shape][0][1] == 16 and 0 < got["hot"] < want["counters"][KEYS.index("innerSteps")], (name, seen, got["hot"])
         if shape == "default" and height <= 30:
             assert seen[shape][0][0] > 64 and got["hot"] > 0, (name, seen, got["hot"])
     line = f"{name}: height {height}, stack entries reported {height}; (threads, cache records) per shape {seen}"
@@ -236,7 +227,7 @@ def test_trace_kernels_fill_the_last_stack_row(pkg, api, orc, name, monkeypatch,
             assert height <= 30
             assert same(got["acc"], want["acc"]) and same(got["frame"], want["frame"]), f"{name}: the reference's text differs from the oracle"
             for k in ("segments", "innerSteps", "triTests"):  # its own two statistics (RC:254, RC:271) and the segments
-                assert got["counters"][tf.KEYS.index(k)] == want["counters"][tf.KEYS.index(k)], (name, k)
+                assert got["counters"][KEYS.index(k)] == want["counters"][KEYS.index(k)], (name, k)
             line += "; reference text: same bits"
     else:
         line += "; reference text: not compared" + (" (never at 32)" if height == 32 else " (not here)")
@@ -254,7 +245,7 @@ def test_comb_32_beside_other_models_in_both_orders(pkg, api, orc, kind, monkeyp
         desc = scene(pkg, name)
         n_models = len(desc.models)
         want = oracle_render(pkg, orc, name)
-        assert want["counters"][tf.KEYS.index("modelVisits")] == want["counters"][tf.KEYS.index("segments")] * n_models
+        assert want["counters"][KEYS.index("modelVisits")] == want["counters"][KEYS.index("segments")] * n_models
         for shape, env in (("default", {}), ("cache", {"RT_LAYOUT": "pre,arena,cache"}), ("single", {"RT_HOT_KB": "0"})):
             for k in ("RT_HOT_KB", "RT_LAYOUT"):
                 monkeypatch.delenv(k, raising=False)
@@ -264,7 +255,7 @@ def test_comb_32_beside_other_models_in_both_orders(pkg, api, orc, kind, monkeyp
             for stats in (False, True):
                 got = render(api, api.create_tracer(0), desc, stats)
                 assert_render(got, want, f"{name}, {shape}, {'stats' if stats else 'shipped'} build", stats)
-            assert got["counters"][tf.KEYS.index("modelVisits")] == got["counters"][tf.KEYS.index("segments")] * n_models
+            assert got["counters"][KEYS.index("modelVisits")] == got["counters"][KEYS.index("segments")] * n_models
             reported = launches(capfd)
             assert reported and {r[1] for r in reported} == {32}, (name, shape, reported)
             ext = 0 if n_models <= 64 else (n_models - 63 + 31) // 32
@@ -371,14 +362,14 @@ def test_ray_queries_and_radiance_with_a_wave_of_witness_rays(pkg, api, orc, nam
             tq.assert_same_records(got, tq.records_from_oracle(pkg, None, want10[order], got["object"], got["triangle"]), f"{name}, {what}")
             assert not got["reserved"].any()
             assert (got["object"][hit[order]] >= 0).all() and (got["triangle"][hit[order]] >= 0).all()
-            assert tq.bits(dbg[order, 2]).tolist() == tq.bits(got["dst"]).tolist()
-            assert tq.bits(dbg[order, 3:6]).tolist() == tq.bits(got["normal"]).tolist() and tq.bits(dbg[order, 6:9]).tolist() == tq.bits(got["pos"]).tolist()
+            assert bits(dbg[order, 2]).tolist() == bits(got["dst"]).tolist()
+            assert bits(dbg[order, 3:6]).tolist() == bits(got["normal"]).tolist() and bits(dbg[order, 6:9]).tolist() == bits(got["pos"]).tolist()
             assert np.array_equal(dbg[order, 0] != 0, (got["hit"] & 3) != 0) and np.array_equal(dbg[order, 1] != 0, (got["hit"] & 0x100) != 0)
             # the 64 witness slots hold one and the same record
             w64 = got[33:97] if what == "in order" else got[n - 97:n - 33]
             assert len({r.tobytes() for r in w64}) == 1
             # ---- the buffer form, with guard words behind the last record
-            d_rays, d_hits = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 48 + guard, fill=0xa5)
+            d_rays, d_hits = DevBuf(n * 32).upload(rays), DevBuf(n * 48 + guard, fill=0xa5)
             tr.query_closest_buffers(d_rays.ptr, n, d_hits.ptr)
             tr.synchronize()
             raw = d_hits.download(np.uint8)
@@ -389,7 +380,7 @@ def test_ray_queries_and_radiance_with_a_wave_of_witness_rays(pkg, api, orc, nam
                 occ = tr.query_occluded(abi.make_rays(o[order], d[order], tmax=tmax))
                 wanted = (hit[order] & (want10[order, 2] < tmax)).astype(np.uint32)
                 assert np.array_equal(occ, wanted), (name, what, tname, np.argwhere(occ != wanted).ravel()[:5])
-                d_occ = tq.DevBuf(n * 4 + guard, fill=0xa5)
+                d_occ = DevBuf(n * 4 + guard, fill=0xa5)
                 d_rays.upload(abi.make_rays(o[order], d[order], tmax=tmax))
                 tr.query_occluded_buffers(d_rays.ptr, n, d_occ.ptr)
                 tr.synchronize()
@@ -486,13 +477,13 @@ def test_gpu_builder_takes_the_cone_to_depth_32_and_the_scene_renders_the_same_b
             mgr.divergeStrength = 0.7
             mgr.RenderFrame()
             c = tr.counters()
-            got = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in tf.KEYS],
+            got = dict(acc=tr.read_accumulated(), frame=tr.read_frame(), counters=[c[k] for k in KEYS],
                        viol=tr.phase_profile()["filter_violations"][0] if stats_on else 0)
             tr.close()
             assert_render(got, want, f"cone from {where}, {'stats' if stats_on else 'shipped'} build", stats_on)
         reported = launches(capfd)
         assert reported and {r[1] for r in reported} == {32}, reported
-        lines.append(f"cone from {where}: stack entries reported 32, {want['counters'][tf.KEYS.index('innerSteps')]} inner steps")
+        lines.append(f"cone from {where}: stack entries reported 32, {want['counters'][KEYS.index('innerSteps')]} inner steps")
     print("\n".join(lines))
 
 
@@ -532,7 +523,7 @@ def states_whose_first_sample_picks(orc, table, triangles, count, first=1 << 16)
 
 
 def nee_arrays(pkg, api, name):
-    """((meshInfo, triangles, nodes, spheres), RtParams) of a scene by name, as tests/test_gpu_radiance.py::params_of makes them"""
+    """((meshInfo, triangles, nodes, spheres), RtParams) of a scene by name, as tests/radiance_reference.py::params_of makes them"""
     mgr = scene(pkg, name).make_manager(None, api, W, H)
     mgr.renderSeed = 5
     data = mgr.CreateAllMeshData(mgr.models)
@@ -652,7 +643,7 @@ def assert_batch_in_every_order(name, tr, rays, want, host, buffers):
     got = host(rays)
     rev = host(rays[::-1])[::-1]
     prefixes = {k: host(rays[:k]) for k in (1, 33, 96, 97, 130)}
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16 + guard, fill=0xa5)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16 + guard, fill=0xa5)
     try:
         buffers(d_rays.ptr, n, d_out.ptr)
         tr.synchronize()
@@ -707,8 +698,8 @@ def test_nee_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
             assert stripped.tobytes() == plain.tobytes() and (stripped["rng"] != rays["rng"]).any() and stripped.tobytes() != got.tobytes()
     finally:
         tr.close()
-    assert tq.bits(dbg[:, 2]).tolist() == tq.bits(hits["dst"]).tolist()
-    assert tq.bits(dbg[:, 3:6]).tolist() == tq.bits(hits["normal"]).tolist() and tq.bits(dbg[:, 6:9]).tolist() == tq.bits(hits["pos"]).tolist()
+    assert bits(dbg[:, 2]).tolist() == bits(hits["dst"]).tolist()
+    assert bits(dbg[:, 3:6]).tolist() == bits(hits["normal"]).tolist() and bits(dbg[:, 6:9]).tolist() == bits(hits["pos"]).tolist()
     assert np.array_equal(dbg[:, 0] != 0, (hits["hit"] & 3) != 0) and np.array_equal(dbg[:, 1] != 0, (hits["hit"] & 0x100) != 0)
     print(f"{name}: {len(full_shadows)} shadow rays and {len(full_segments)} path segments with {height} stack entries; lanes of vertex 0 with a shadow ray per block {mixed}; "
           f"{len(so)} distinct shadow rays against rt_debug_intersect; reference {t_ref:.1f} s, all {time.perf_counter() - t0:.1f} s")
@@ -756,7 +747,7 @@ def test_mis_fills_the_last_stack_row_in_both_of_its_walks(pkg, api, orc, name):
     sampled = {v for (_, v, *_r) in est.sample_log}
     assert sampled == {0, 1}, f"vertices 0 and 1 sample, no other: {sampled}"
     assert est.skipped_log and all(v == 2 for (_, v) in est.skipped_log), "the last vertex takes no sample"
-    tm.rules_allowed(est, name)
+    mr.rules_allowed(est, name)
     models, triangles, spheres = arrays[0], arrays[1], arrays[3]
     objects, words, table = mr.map_arrays(abi, models, triangles, spheres)
     assert table["n_triangle_entries"] >= height + 1 and table["n_sphere_entries"] == 0

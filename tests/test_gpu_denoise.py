@@ -21,52 +21,13 @@ import pytest
 
 from flush_table import held_at
 
+import aov_support as ga
 import denoise_reference as ref
-import test_gpu_aov as ga
+from gpu_support import DevBuf, assert_same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-class DevBuf:
-    """Device memory through the HIP runtime the library already loaded (torch runs in a child process: it brings its own runtime)."""
-
-    def __init__(self, nbytes, fill=0):
-        self.hip = C.CDLL("libamdhip64.so")
-        self.nbytes = nbytes
-        self.p = C.c_void_p()
-        assert self.hip.hipMalloc(C.byref(self.p), C.c_size_t(max(nbytes, 16))) == 0
-        assert self.hip.hipMemset(self.p, fill, C.c_size_t(max(nbytes, 16))) == 0 and self.hip.hipDeviceSynchronize() == 0
-
-    @classmethod
-    def of(cls, array):
-        array = np.ascontiguousarray(array)
-        d = cls(array.nbytes)
-        assert d.hip.hipMemcpy(d.p, C.c_void_p(array.ctypes.data), C.c_size_t(array.nbytes), C.c_int(1)) == 0
-        return d
-
-    @property
-    def ptr(self):
-        return self.p.value
-
-    def image(self, h, w):
-        out = np.zeros((h, w, 4), dtype=F)
-        assert out.nbytes == self.nbytes
-        assert self.hip.hipMemcpy(C.c_void_p(out.ctypes.data), self.p, C.c_size_t(self.nbytes), C.c_int(2)) == 0
-        return out
-
-    def free(self):
-        self.hip.hipFree(self.p)
-
-
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    if len(bad):
-        y, x, k = bad[0]
-        raise AssertionError(f"{what}: {len(set(map(tuple, bad[:, :2])))} pixels differ; first at row {y}, column {x}, channel {k}: "
-                             f"got {got[y, x]}, want {want[y, x]}")
 
 
 def filter_on_device(api, tr, rgba, aov, **fields):
@@ -142,7 +103,7 @@ root = sys.argv[1]
 sys.path.insert(0, root)
 sys.path.insert(0, os.path.join(root, "tests"))
 import __graft_entry__ as graft
-import test_gpu_aov as ga
+import aov_support as ga
 pkg = graft.load_package()
 api = pkg.load_library()
 for layout in (None, "dense", "pre,arena,cache"):

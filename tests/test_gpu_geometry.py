@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 
 from conftest import render
-from test_gpu_parity import KEYS, bits_equal
+from gpu_support import KEYS, bits_equal
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

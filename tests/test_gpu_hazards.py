@@ -27,16 +27,17 @@ import time
 import numpy as np
 import pytest
 
+import aov_support as ta
 import hazard_scenes as hz
 import mis_reference as mr
 import nee_reference as nr
 import radiance_reference as rr
-import test_gpu_mis as tm
-from test_gpu_tile_tri import KEYS, environment
+from gpu_support import KEYS, environment
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 F3 = C.c_float * 3
+ENV = ("RT_TILE_TRI", "RT_TILE_CAND", "RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")   # the variables tests/test_gpu_tile_tri.py clears
 POOLED, SINGLE = {"RT_POOL_MIN_ITEMS": "0"}, {"RT_POOL": "0"}
 ALL = [None] + hz.CASES
 IDS = ["unplanted"] + [c.name for c in hz.CASES]
@@ -48,7 +49,7 @@ def contexts(api):
     made = []
     for name, env in (("default", {}), ("pooled", POOLED), ("single waves", SINGLE)):
         for stats in (False, True):
-            with environment(env) if env else _nothing():
+            with environment(env, ENV) if env else _nothing():
                 tr = api.create_tracer(0)
             tr.enable_stats(stats)
             made.append((name, env, tr, stats))
@@ -86,7 +87,7 @@ def _drive_watched(rig, tr):
 def _check(pkg, api, orc, case, base, name, env, tr, stats):
     what = f"{case.name if case else 'unplanted'} on {base} ({name}, {'STATS' if stats else 'shipped'})"
     want = hz.expected(pkg, orc, base, case)
-    with environment(env) if env else _nothing():
+    with environment(env, ENV) if env else _nothing():
         tr.reset_counters()
         single, fused, c, debug = _drive_watched(hz.Rig(pkg, api, base, case), tr)
         viol = tr.phase_profile()["filter_violations"][0] if stats else 0
@@ -195,7 +196,6 @@ def test_aov_records_of_a_hazard_scene(pkg, api, orc, contexts, case):
     tests/test_gpu_aov.py; albedo from oracle_material_colour (a hit; the material is the one of the record's own object, whose flag
     must be the oracle's hit's) or oracle_environment_light (a miss); emission = emissionCol * emissionStrength; object and
     triangle: -1 exactly on a miss, a sphere's triangle -1, a model's inside the model's range."""
-    import test_gpu_aov as ta
     abi = pkg.abi
     for base in hz.SIDE_BASES:
         if not case.applies(base):
@@ -373,7 +373,7 @@ def _not_vacuous(what, est, expect, t0):
           f"{time.perf_counter() - t0:.2f} s for this base, the reference included")
     assert 4 * live >= len(rgb), f"{what}: only {live} of {len(rgb)} compared records are finite and not zero"
     assert est.samples > 0, what
-    tm.rules_allowed(est, what)
+    mr.rules_allowed(est, what)
 
 
 def _assert_map(pkg, api, what, rig):
@@ -560,7 +560,7 @@ def test_triangle_values_under_the_layout_that_moves_the_records(pkg, api, orc, 
     rig = hz.Rig(pkg, api, base, case)
     used = api.layout_arrays(rig.models, rig.triangles, rig.nodes, layout)["used"]
     assert "pre" in used.split(",") and "arena" in used.split(","), f"asked for {layout}, the scene is laid out as {used}"
-    with environment({"RT_LAYOUT": layout}):
+    with environment({"RT_LAYOUT": layout}, ENV):
         for stats in (False, True):
             tr = api.create_tracer(0)
             try:

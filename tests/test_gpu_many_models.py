@@ -26,20 +26,19 @@ import time
 import numpy as np
 import pytest
 
+import aov_support as ta
+import cost_view_support as tc
 import hazard_scenes as hz
 import many_models as mm
 import mis_reference as mr
 import motion_reference as mref
 import nee_reference as nr
 import radiance_reference as rr
-import test_gpu_aov as ta
-import test_gpu_cost_view as tc
-import test_gpu_mis as tm
-import test_gpu_query as tq
-from test_gpu_cost_view import orc_log  # noqa: F401  (fixture)
-from test_gpu_deep_trees import launches
-from test_gpu_fuzz import KEYS
-from test_launch_plan import one, plan  # noqa: F401  (plan: the fixture that builds tests/launch_plan_driver.cpp)
+import query_support as tq
+from cost_view_support import orc_log  # noqa: F401  (fixture)
+from deep_trees import launches
+from gpu_support import KEYS
+from launch_plan_support import one, plan  # noqa: F401  (plan: the fixture that builds tests/launch_plan_driver.cpp)
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -200,7 +199,7 @@ def _side_contexts(pkg, api, orc, sc, models=None):
 
 
 def cost_of_log(log):
-    """tests/test_gpu_cost_view.py::cost_of_log without the per-token loop, for logs of a million tokens.  The log's payload bytes (an
+    """tests/cost_view_support.py::cost_of_log without the per-token loop, for logs of a million tokens.  The log's payload bytes (an
     inner step's depth, a leaf's depth and count) may equal a tag in general; where every one of them is below 'A' (65) — checked: the
     bytes below 65 must be exactly the one behind each 'B' and the two behind each 'C' — the tags are the bytes from 65 up and the fields
     are sums over masks.  Otherwise the loop does it."""
@@ -513,7 +512,7 @@ def test_mis_with_emitters_on_either_side_of_the_boundaries(pkg, api, orc, name,
         tr.close()
     ok = (rr.bits(out["rgb"]) == rr.bits(expect["rgb"])).all(axis=1) & (out["rng"] == expect["rng"])
     assert len(est.emission_hits) == len(est.emission_log)
-    tm.rules_allowed(est, f"{name} bounce={bounce}")
+    mr.rules_allowed(est, f"{name} bounce={bounce}")
     weighted_on = sorted({obj for (obj, _), e in zip(est.emission_hits, est.emission_log) if e[3] == mr.WEIGHTED})
     rules = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
     sampled, skipped = sorted({v for (_, v, *_r) in est.sample_log}), sorted({v for (_, v) in est.skipped_log})

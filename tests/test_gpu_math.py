@@ -4,7 +4,7 @@ divide / sqrt, denormals and special values."""
 import numpy as np
 import pytest
 
-from test_math import OPS, ev
+from math_support import OPS, ev
 
 pytestmark = pytest.mark.gpu
 

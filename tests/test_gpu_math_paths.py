@@ -10,7 +10,7 @@ exhaustive form of this (all 2^32 arguments, device against device); this is the
 import numpy as np
 import pytest
 
-from test_math import OPS, ev
+from math_support import OPS, ev
 
 pytestmark = pytest.mark.gpu
 

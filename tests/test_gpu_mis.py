@@ -29,13 +29,15 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mis_reference as mr  # noqa: E402
 import nee_reference as nr  # noqa: E402
+import nee_support as gn  # noqa: E402  (scenes, batches, helpers: shared, never written)
+import query_support as tq  # noqa: E402
+import radiance_reference as rr  # noqa: E402
 from flush_table import held_at  # noqa: E402
-import test_gpu_nee as gn  # noqa: E402  (scenes, batches, helpers: shared, never written)
-import test_gpu_query as tq  # noqa: E402
-import test_gpu_radiance as rg  # noqa: E402
+from gpu_support import DevBuf  # noqa: E402
+from mis_reference import RULE_TABLE, rules_allowed  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = gn.ROOT
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 W, H = gn.W, gn.H  # the 200 camera rays of tests/test_gpu_nee.py's bit test
 BIT_SCENES = ["nee_flat", "config3_bvh", "crowded70_emissive", "nee_mirrored", "nee_glass", "nee_inside", "nee_instances"]
@@ -210,33 +212,6 @@ def test_a_reused_lane_starts_without_the_dead_paths_cosine(pkg, api, orc, monke
 
 
 # ---------------------------------------------------------------- the rules of emission_weight
-# One row per rule constant of tests/mis_reference.py: the case (scene, maxBounceCount as in case()) whose emission_log must hold the rule,
-# or None and why no table the library builds reaches it.  A rule marked unreachable must not be logged by ANY case: rules_allowed() is
-# called by every MIS test that runs the reference (here and in test_gpu_deep_trees.py, test_gpu_many_models.py and
-# test_gpu_hazards.py: four modules), so a change that makes one reachable is noticed where it happens.
-RULE_TABLE = [
-    (mr.WEIGHTED, "sphere", ("nee_flat", None), ""),
-    (mr.WEIGHTED, "triangle", ("nee_flat", None), ""),
-    (mr.NO_ENTRY_RULE, None, ("config3_bvh", None), ""),
-    (mr.INSIDE, "sphere", ("nee_inside", None), ""),
-    (mr.BACK, "triangle", "mis_back_light", "reached only through a model record whose worldToLocal contradicts its localToWorld (back_light_case): an opaque model is always "
-                                             "culled from behind, so no consistent scene hits a table triangle with cl <= 0"),
-    (mr.NOT_CONE, None, None, "needs a FRONT-face hit of a sphere from a segment origin inside it (d2 <= r2): a ray that starts inside a sphere leaves it through a back face"),
-    (mr.NOT_LOBE, None, None, "needs dot(n, normalize(n + RandomDirection)) <= 0 at a vertex that sampled: RandomDirection is a unit vector, so n + it lies in n's closed half space, "
-                              "and the sum is 0 (a NaN direction, which hits nothing) only for the one draw -n"),
-    (mr.NAN, None, None, "needs prob * d2 and cl * S both 0 or both inf, or pb + pl' not finite: the table's area rule keeps S finite and > 0 and prob in (0, 1], cl is in (0, 1], and the "
-                         "surface offset keeps d2 > 0"),
-]
-UNREACHABLE = {rule for (rule, _, where, _) in RULE_TABLE if where is None}
-
-
-def rules_allowed(est, what):
-    """no emission of this reference run was given its weight by a rule RULE_TABLE marks unreachable -> {rule: count}"""
-    seen = {r: sum(1 for e in est.emission_log if e[3] == r) for r in sorted({e[3] for e in est.emission_log})}
-    assert not set(seen) & UNREACHABLE, f"{what}: the reference logged {seen}; RULE_TABLE marks {sorted(set(seen) & UNREACHABLE)} unreachable"
-    return seen
-
-
 _BACK = {}
 
 
@@ -258,7 +233,7 @@ def back_light_case(pkg, api, orc):
         sc = gn.SceneArrays(api, pkg.scenes.SceneDescription("mis_back_light", 64, 36, 1, settings, cam, [ceiling, light], []))
         sc.models = sc.models.copy()
         sc.models[1]["worldToLocal"] = pkg.manager.matrix_to_abi(up.worldToLocalMatrix)
-        p = rg.params_of(sc, api, 64, 36, {})
+        p = rr.params_of(sc, api, 64, 36, {})
         k = np.arange(96)
         rays = pkg.abi.make_path_rays(np.stack([-0.4 + 0.8 * (k % 12) / 11, np.full(96, 2.0), -0.4 + 0.8 * (k // 12) / 7], axis=1), np.tile([0.0, 1.0, 0.0], (96, 1)), 300 + 17 * k)
         tr = gn.hip_tracer(api, sc, p)
@@ -357,7 +332,7 @@ def test_floor_under_a_spherical_emitter_closed_form(pkg, api, orc, offset):
     cam = pkg.Camera(pkg.Transform((0, 1, -6)), fieldOfView=60.0)
     settings = dict(maxBounceCount=1, numRaysPerPixel=1, useSky=False, accumulate=True, bvhQuality=1)
     sc = gn.SceneArrays(api, pkg.scenes.SceneDescription("mis_physics", 64, 36, 1, settings, cam, [floor], [light]))
-    p = rg.params_of(sc, api, 64, 36, {})
+    p = rr.params_of(sc, api, 64, 36, {})
     assert p.maxBounceCount == 1 and not p.useSky
     ray = pkg.abi.make_path_rays([[offset, 1.0, 0.0]], [[0, -1, 0]], 1)
     tr = gn.hip_tracer(api, sc, p)
@@ -412,7 +387,7 @@ def near_light_scene(pkg, api):
         cam = pkg.Camera(T((3, 1, 0), (0, -90, 0)), fieldOfView=60.0)
         settings = dict(maxBounceCount=1, numRaysPerPixel=1, useSky=False, accumulate=True, bvhQuality=1)
         sc = gn.SceneArrays(api, pkg.scenes.SceneDescription("mis_near_light", 64, 36, 1, settings, cam, [ceiling, light], []))
-        p = rg.params_of(sc, api, 64, 36, {})
+        p = rr.params_of(sc, api, 64, 36, {})
         assert p.maxBounceCount == 1 and not p.useSky
         ray = pkg.abi.make_path_rays([[0.04, 2.0, 0.0]], [[0, 1, 0]], 1)
         tr = gn.hip_tracer(api, sc, p)
@@ -515,7 +490,7 @@ def test_device_form_launches_held_back_frames_first_like_a_flushes_row(pkg, api
             rays = np.repeat(abi.make_path_rays([[0.0, 0.05, 0.0]], [[0, -1, 0]], 9), n)
             rays["origin"][:, 0] += np.arange(n) * F(0.002)
             rays["rng"] = np.arange(n) + 100
-            d_rays, d_out = tq.DevBuf(rays.nbytes).upload(rays), tq.DevBuf(n * 16)
+            d_rays, d_out = DevBuf(rays.nbytes).upload(rays), DevBuf(n * 16)
             mgr.RenderFrames(2)
             before = tr.radiance_trace_mis(rays)
             for _ in range(3):
@@ -544,7 +519,7 @@ def test_device_form_sees_updates_and_the_rebuilt_map(pkg, api, orc):
     names = [m.name for m in sc.desc.models]
     light, cube = names.index("Light"), names.index("OpaqueRoundedCube")
     n = len(rays)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
 
     def device(tr):
         tr.radiance_trace_mis_buffers(d_rays.ptr, n, d_out.ptr)
@@ -586,7 +561,7 @@ def test_device_form_sees_updates_and_the_rebuilt_map(pkg, api, orc):
         rays2 = np.repeat(abi.make_path_rays([[0.0, 0.05, 0.0]], [[0, -1, 0]], 9), m)
         rays2["origin"][:, 0] += np.arange(m) * F(0.002)
         rays2["rng"] = np.arange(m) + 100
-        d_rays, d_out = tq.DevBuf(rays2.nbytes).upload(rays2), tq.DevBuf(m * 16)
+        d_rays, d_out = DevBuf(rays2.nbytes).upload(rays2), DevBuf(m * 16)
         before = tr.radiance_trace_mis(rays2)
         changed = spheres.copy()
         changed["material"]["emissionStrength"][:] = 0
@@ -617,7 +592,7 @@ def test_mixed_calls_of_the_three_estimators_and_frames_leave_no_trace(pkg, api,
     pass wrote its own estimator's records, and the closing rt_synchronize — which reports every pass's watchdog word — is RT_OK."""
     sc, p, rays, want, est = case(pkg, api, orc, "config3_bvh", None)
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16), tq.DevBuf(n * 16), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16), DevBuf(n * 16), DevBuf(n * 16))
     tr = api.create_tracer(0)
     try:
         tr.enable_stats(True)
@@ -656,7 +631,7 @@ def test_errors(pkg, api, orc):
     n = 100
     rays = rays200[:n].copy()
     out = np.zeros(n, dtype=abi.RADIANCE_DTYPE)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     bad, state, ok = abi.RT_ERR_INVALID_ARG, abi.RT_ERR_STATE, abi.RT_OK
     tr = api.create_tracer(0)
 
@@ -728,7 +703,7 @@ def test_more_entries_than_the_cap_is_a_scene_error_of_this_call_only(pkg, api, 
     p, rays = gn.camera_batch(pkg, api, orc, sc, 16, 8, None)
     n = len(rays)
     out = np.zeros(n, dtype=abi.RADIANCE_DTYPE)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     tr = gn.hip_tracer(api, sc, p)
     try:
         for _ in range(2):
@@ -751,7 +726,7 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
     abi = pkg.abi
     sc, p, rays, want, est = case(pkg, api, orc, "config3_bvh", None)
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16))
     tr = api.create_tracer(0)
     try:
         mgr = pkg.scenes.get(3).make_manager(tr, api, 24, 16)

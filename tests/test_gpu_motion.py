@@ -17,9 +17,9 @@ import pytest
 
 import motion_reference as mref
 import reproject_reference as ref
-import test_gpu_aov as ga
-from test_gpu_denoise import DevBuf, assert_same_bits
-from test_gpu_reproject import NEARBY, move_camera, records_of
+import aov_support as ga
+from gpu_support import DevBuf, assert_same_bits
+from reproject_support import NEARBY, move_camera, records_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -35,77 +35,20 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import deep_trees as dt  # noqa: E402
 import nee_reference as nr  # noqa: E402
 import radiance_reference as rr  # noqa: E402
+import query_support as tq  # noqa: E402  (snapshot)
 from flush_table import held_at  # noqa: E402
-import test_gpu_query as tq  # noqa: E402  (scenes, DevBuf, snapshot: shared, never written)
-import test_gpu_radiance as rg  # noqa: E402  (params_of, assert_rgb)
+from gpu_support import DevBuf  # noqa: E402
+from nee_support import (H, LAYOUTS, W, SceneArrays, assert_records, camera_batch, chained, grid_mesh, hip_tracer, scene,  # noqa: E402
+                         without_cache)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-FRAME = 3
-W, H = 20, 10  # 200 camera rays: three blocks and a partial one
 BIT_SCENES = ["nee_flat", "config3_bvh", "crowded70_emissive", "nee_mirrored", "nee_glass", "nee_inside", "nee_instances"]
 BOUNCES = [-1, 0, 1, None]
-LAYOUTS = ["dense", "pre", "pre,align", "pre,arena", "pre,arena,cache", "pre,hot=2,arena,palign"]
 LAYOUT_SCENES = ["config3_bvh", "crowded70_emissive", "nee_instances"]
 
-_SCENES = {}
 _CASES = {}
-
-
-class SceneArrays:
-    """A scene description's arrays as rt_upload_scene takes them (tests/test_gpu_query.py's Scene for descriptions it does not know)."""
-
-    def __init__(self, api, desc):
-        self.desc = desc
-        mgr = desc.make_manager(None, api, 64, 36)
-        data = mgr.CreateAllMeshData(mgr.models)
-        self.models, self.triangles, self.nodes = data["meshInfo"], data["triangles"], data["nodes"]
-        self.spheres = mgr._pack_spheres()
-
-    def upload(self, tracer, models=None, spheres=None):
-        tracer.upload_scene(self.models if models is None else models, self.triangles, self.nodes, self.spheres if spheres is None else spheres)
-        return tracer
-
-    def stripped(self):
-        """The arrays with every emitter put out: emissionStrength 0 (a checkered material's second colour stays)."""
-        models, spheres = self.models.copy(), self.spheres.copy()
-        models["material"]["emissionStrength"] = 0
-        spheres["material"]["emissionStrength"] = 0
-        return models, spheres
-
-
-def describe(pkg, name):
-    if name == "crowded70_emissive":  # the MANY variant: model 0 (the cube at the origin, a ball poking through its faces) and sphere 1 made emissive
-        d = tq.crowded_scene(pkg)
-        M = pkg.RayTracingMaterial
-        d.models[0].material = M(diffuseCol=(0, 0, 0, 1), emissionCol=(1, 0.8, 0.5, 1), emissionStrength=12.0)
-        d.spheres[1].material = M(diffuseCol=(0.2, 0.2, 0.2, 1), emissionCol=(0.4, 0.6, 1, 1), emissionStrength=5.0)
-        return d
-    if name.startswith("nee_"):
-        return nr.build_scene(pkg, name)
-    return tq.scene_of(pkg, name)
-
-
-def scene(pkg, api, name):
-    if name not in _SCENES:
-        _SCENES[name] = SceneArrays(api, describe(pkg, name))
-    return _SCENES[name]
-
-
-def hip_tracer(api, sc, p, **arrays):
-    tr = sc.upload(api.create_tracer(0), **arrays)
-    tr.set_params(p)
-    return tr
-
-
-def camera_batch(pkg, api, orc, sc, w, h, bounce):
-    tweak = dict(rg.NO_DOF, numRaysPerPixel=1)
-    if bounce is not None:
-        tweak["maxBounceCount"] = bounce
-    p = rg.params_of(sc, api, w, h, tweak)
-    origins, dirs, states = rr.camera_rays(orc, p, w, h, FRAME)
-    return p, pkg.abi.make_path_rays(origins.reshape(-1, 3), dirs.reshape(-1, 3), states.reshape(-1))
 
 
 def case(pkg, api, orc, name, bounce):
@@ -124,13 +67,6 @@ def case(pkg, api, orc, name, bounce):
             a.setflags(write=False)
         _CASES[key] = (sc, p, rays, want, est)
     return _CASES[key]
-
-
-def assert_records(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, what
-    rg.assert_rgb(got["rgb"], want["rgb"], what)
-    bad = np.argwhere(got["rng"] != want["rng"]).ravel()
-    assert not len(bad), f"{what}: rng of {len(bad)} rays differs; first is ray {bad[0]}"
 
 
 # ---------------------------------------------------------------- 1. bit for bit
@@ -254,18 +190,6 @@ def test_an_all_mirror_scene_gives_rt_radiance_traces_records(pkg, api, orc):
 
 
 # ---------------------------------------------------------------- 3. physics, closed form
-def chained(call, ray, chains, rounds):
-    """chains x rounds samples of one ray: `chains` generator sequences, each chained through `rounds` calls."""
-    rays = np.repeat(ray, chains)
-    rays["rng"] = (np.arange(chains, dtype=np.uint64) * 2654435761 + 12345) % (1 << 32)
-    out = np.zeros((rounds, chains, 3), dtype=F)
-    for k in range(rounds):
-        rec = call(rays)
-        out[k] = rec["rgb"]
-        rays["rng"] = rec["rng"]
-    return out.reshape(-1, 3)
-
-
 @pytest.mark.parametrize("offset", [0.7, 2.0])
 def test_floor_under_a_spherical_emitter_closed_form(pkg, api, orc, offset):
     """A diffuse floor (rho = 0.8) under an emissive sphere (r = 0.5, centre 3 above the floor, Le = 10, diffuseCol 0), no sky,
@@ -281,7 +205,7 @@ def test_floor_under_a_spherical_emitter_closed_form(pkg, api, orc, offset):
     cam = pkg.Camera(pkg.Transform((0, 1, -6)), fieldOfView=60.0)
     settings = dict(maxBounceCount=1, numRaysPerPixel=1, useSky=False, accumulate=True, bvhQuality=1)
     sc = SceneArrays(api, pkg.scenes.SceneDescription("nee_physics", 64, 36, 1, settings, cam, [floor], [light]))
-    p = rg.params_of(sc, api, 64, 36, {})
+    p = rr.params_of(sc, api, 64, 36, {})
     assert p.maxBounceCount == 1 and not p.useSky
     ray = pkg.abi.make_path_rays([[offset, 1.0, 0.0]], [[0, -1, 0]], 1)
     tr = hip_tracer(api, sc, p)
@@ -366,7 +290,7 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
             rays = np.repeat(abi.make_path_rays([[0.0, 0.05, 0.0]], [[0, -1, 0]], 9), n)  # between the spheres, straight down at the ground
             rays["origin"][:, 0] += np.arange(n) * F(0.002)
             rays["rng"] = np.arange(n) + 100
-            d_rays, d_out = tq.DevBuf(rays.nbytes).upload(rays), tq.DevBuf(n * 16)
+            d_rays, d_out = DevBuf(rays.nbytes).upload(rays), DevBuf(n * 16)
             if with_passes:
                 before = tr.radiance_trace_nee(rays)
                 lights = tr.nee_light_count()
@@ -519,7 +443,7 @@ def mixed_calls(tr, rays, bufs):
 def test_nee_calls_leave_no_trace(pkg, api, orc):
     sc, p, rays, want, est = case(pkg, api, orc, "config3_bvh", None)
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16))
     try:
         # a rendering context, whole and as part 1 of 2 of a strip partition: everything a caller can read is the same before and after,
         # and so are the records of the other passes (whose watchdog words a synchronise would report)
@@ -557,7 +481,7 @@ def test_errors(pkg, api, orc):
     n = 100
     rays = rays200[:n].copy()
     out = np.zeros(n, dtype=abi.RADIANCE_DTYPE)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     bad, state, ok = abi.RT_ERR_INVALID_ARG, abi.RT_ERR_STATE, abi.RT_OK
     host, dev = api.nee_trace, api.nee_trace_buffers
     a, b = C.c_int(-7), C.c_int(-7)
@@ -610,7 +534,7 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
     abi = pkg.abi
     sc, p, rays, want, est = case(pkg, api, orc, "config3_bvh", None)
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16))
     tr = api.create_tracer(0)
     try:
         mgr = pkg.scenes.get(3).make_manager(tr, api, 24, 16)
@@ -663,16 +587,6 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
 
 
 # ---------------------------------------------------------------- 6. the entry cap, through a context
-def grid_mesh(pkg, nx=256, ny=128):
-    """nx x ny quads in the plane z = 0, two triangles each (2^16 at the default), front side -z like the Quad."""
-    xs, ys = np.meshgrid(np.linspace(-0.5, 0.5, nx + 1), np.linspace(-0.5, 0.5, ny + 1), indexing="xy")
-    verts = np.stack([xs.ravel(), ys.ravel(), np.zeros(xs.size)], axis=1).astype(F)
-    i = (np.arange(ny)[:, None] * (nx + 1) + np.arange(nx)[None, :]).ravel()
-    a, b, c, d = i, i + 1, i + nx + 1, i + nx + 2  # the Quad's corners 0, 1, 2, 3 and its triangles (0, 3, 1), (3, 0, 2)
-    idx = np.stack([a, d, b, d, a, c], axis=1).ravel().astype(np.int32)
-    return pkg.meshes.Mesh(verts, np.tile(np.array([[0, 0, -1]], dtype=F), (len(verts), 1)), idx, "Grid")
-
-
 def test_more_entries_than_the_cap_is_a_scene_error_of_these_calls_only(pkg, api, orc):
     """One mesh of 2^16 triangles under 65 emissive models: 65 x 2^16 entries, 2^16 past RT_NEE_MAX_LIGHTS, from 2^16 uploaded
     triangles.  The three calls of the header refuse with RT_ERR_SCENE and say why, every time (the table stays stale); the scene stays
@@ -692,7 +606,7 @@ def test_more_entries_than_the_cap_is_a_scene_error_of_these_calls_only(pkg, api
     p, rays = camera_batch(pkg, api, orc, sc, 16, 8, None)
     n = len(rays)
     out = np.zeros(n, dtype=abi.RADIANCE_DTYPE)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     a, b = C.c_int(-7), C.c_int(-7)
     tr = hip_tracer(api, sc, p)
     try:
@@ -726,11 +640,6 @@ def test_more_entries_than_the_cap_is_a_scene_error_of_these_calls_only(pkg, api
 
 
 # ---------------------------------------------------------------- 7. every device layout
-def without_cache(layout):
-    """tests/test_layout.py's: `used` reports the records the cache really holds, so the cache word is compared apart"""
-    return ",".join(w for w in layout.split(",") if not w.startswith("cache")) or "dense"
-
-
 @pytest.mark.parametrize("layout", LAYOUTS)
 @pytest.mark.parametrize("name", LAYOUT_SCENES)
 def test_every_device_layout_gives_the_references_records(pkg, api, orc, monkeypatch, capfd, name, layout):
@@ -800,7 +709,7 @@ def test_one_context_through_updates_that_move_emitters(pkg, api, orc):
     spheres["centre"][1], spheres["radius"][1] = (-1.5, 2.8, -0.3), 2 * first.spheres["radius"][1]
     deep = dt.one_model(pkg, *dt.comb(abi, 33))  # 33 levels: refused
 
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     tr = api.create_tracer(0)
     records, lines = {}, []
 

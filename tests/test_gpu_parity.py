@@ -13,15 +13,11 @@ import numpy as np
 import pytest
 
 from flush_table import held_at
+from gpu_support import KEYS, bits_equal
 
 from conftest import render
 
 pytestmark = pytest.mark.gpu
-KEYS = ["segments", "innerSteps", "leafSteps", "triTests", "sphereTests", "modelVisits", "pixelFrames"]
-
-
-def bits_equal(a, b):
-    return a.shape == b.shape and bool(np.all(a.view(np.uint32) == b.view(np.uint32)))
 
 
 def rel_err(a, b):

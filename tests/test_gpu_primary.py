@@ -10,37 +10,16 @@ the audits of the conservative pre-tests (filter_violations) with 0.  The oracle
 The cases are the ones in which a stale, misplaced or wrongly enabled table would show: fused launches, a camera move, sphere and model
 updates between frames, defocus (table off), sphere counts 1 / 3 (the pair's tail) / 33 (over the cap: off), more models or triangles
 than the caps (off), a 12-triangle leaf next to a quad (within the caps), maxBounceCount = 0 (every intersection is a camera ray's)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from gpu_support import KEYS, bits, environment
+
 pytestmark = pytest.mark.gpu
-KEYS = ["segments", "innerSteps", "leafSteps", "triTests", "sphereTests", "modelVisits", "pixelFrames"]
+# RT_PRIMARY and RT_POOL_MIN_ITEMS are read when a context is made, RT_POOL when a scene is uploaded
+ENV = ("RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")
 WAYS = [("table, pooled", {"RT_PRIMARY": "1", "RT_POOL_MIN_ITEMS": "0"}), ("no table, pooled", {"RT_PRIMARY": "0", "RT_POOL_MIN_ITEMS": "0"}),
         ("table, single waves", {"RT_PRIMARY": "1", "RT_POOL": "0"}), ("no table, single waves", {"RT_PRIMARY": "0", "RT_POOL": "0"})]
-
-
-@contextlib.contextmanager
-def environment(env):
-    """RT_PRIMARY and RT_POOL_MIN_ITEMS are read when a context is made, RT_POOL when a scene is uploaded"""
-    names = ("RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")
-    old = {k: os.environ.get(k) for k in names}
-    for k in names:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def check(pkg, api, orc, drive, table=True):
@@ -53,7 +32,7 @@ def check(pkg, api, orc, drive, table=True):
     c.close()
     images = {}
     for name, env in WAYS:
-        with environment(env):
+        with environment(env, ENV):
             for stats in (False, True):
                 g = api.create_tracer(0)
                 g.enable_stats(stats)

@@ -6,7 +6,7 @@ is == on the bit patterns (uint32 views: NaN and -0 count), every ray.
      block), on config 2 (FLAT), config 3 (BVH), glass_balls and the 70-model scene of tests/test_gpu_query.py (MANY), with defocus and
      diverge both zero and both non-zero, maxBounceCount at the scene's default and at 1; the oracle's values are asserted finite first;
   2. the returned state: numRaysPerPixel = 2; ray 1 made from ray 0's returned rng; ((0 + L0) + L1) / 2 == oracle_trace_pixel;
-  3. arbitrary rays (the mix of tests/test_gpu_query.py's make_rays), maxBounceCount = 0: a miss gives oracle_environment_light(dir)
+  3. arbitrary rays (the mix of tests/query_support.py's make_rays), maxBounceCount = 0: a miss gives oracle_environment_light(dir)
      with useSky and 0 without, an opaque hit its emission, a glass hit 0; hit or miss from oracle_ray_collision;
   4. independence: 333 rays in order, reversed and as prefixes n = 1, 63, 64, 65, 130, with a sentinel behind the last record;
   5. RT_GRID=2: the blocks come from the counter, the bits are the same;
@@ -21,39 +21,27 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import query_support as tq  # noqa: E402  (scenes, the ray mix and the cached oracle records: shared, never written)
 import radiance_reference as rr  # noqa: E402
 from flush_table import held_at  # noqa: E402
-import test_gpu_query as tq  # noqa: E402  (scenes, the ray mix, DevBuf and the cached oracle records: shared, never written)
+from gpu_support import DevBuf  # noqa: E402
+from radiance_reference import FRAME, NO_DOF, assert_rgb, params_of  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
 F3 = C.c_float * 3
-FRAME = 3
 DOF = dict(defocusStrength=40.0, divergeStrength=1.5, focusDistance=4.0)
-NO_DOF = dict(defocusStrength=0.0, divergeStrength=0.0)
 
 _SCENES = {}
 _CASES = {}
 
 
 def scene(pkg, api, name):
-    """tests/test_gpu_query.py's Scene (description and the arrays rt_upload_scene takes), built once per name."""
+    """tests/query_support.py's Scene (description and the arrays rt_upload_scene takes), built once per name."""
     if name not in _SCENES:
         _SCENES[name] = tq.Scene(pkg, api, name)
     return _SCENES[name]
-
-
-def params_of(sc, api, w, h, tweak):
-    """The RtParams the scene's manager would set at w x h with `tweak` applied (no tracer involved)."""
-    mgr = sc.desc.make_manager(None, api, w, h)
-    for k, v in tweak.items():
-        assert hasattr(mgr, k), k
-        setattr(mgr, k, v)
-    mgr.renderSeed = 5
-    p = mgr.params()
-    p.frame = FRAME
-    return p
 
 
 def hip_tracer(api, sc, p):
@@ -88,12 +76,6 @@ def camera_case(pkg, api, orc, name, w, h, dof, bounce, spp=1, sky=None):
             a.setflags(write=False)
         _CASES[key] = (sc, p, origins, dirs, states, want)
     return _CASES[key]
-
-
-def assert_rgb(got, want, what):
-    a, b = rr.bits(got).reshape(-1, 3), rr.bits(want).reshape(-1, 3)
-    bad = np.argwhere((a != b).any(axis=1)).ravel()
-    assert not len(bad), f"{what}: {len(bad)} of {len(a)} rays differ; first is ray {bad[0]}: got {got.reshape(-1, 3)[bad[0]]}, want {want.reshape(-1, 3)[bad[0]]}"
 
 
 # ---------------------------------------------------------------- 1. camera equivalence
@@ -197,10 +179,10 @@ def test_a_record_depends_on_its_own_ray_only(pkg, api, orc, name):
         full = tr.radiance_trace(rays)
         assert_rgb(full["rgb"], want.reshape(-1, 3)[:n], name)
         assert tr.radiance_trace(rays[::-1])[::-1].tobytes() == full.tobytes(), "reversed"
-        d_rays = tq.DevBuf(n * 32).upload(rays)
+        d_rays = DevBuf(n * 32).upload(rays)
         for k in (1, 63, 64, 65, 130):
             assert tr.radiance_trace(rays[:k]).tobytes() == full[:k].tobytes(), k
-            d_out = tq.DevBuf(k * 16 + 16, fill=0xa5)
+            d_out = DevBuf(k * 16 + 16, fill=0xa5)
             tr.radiance_trace_buffers(d_rays.ptr, k, d_out.ptr)
             tr.synchronize()
             raw = d_out.download(np.uint8)
@@ -246,7 +228,7 @@ def test_buffer_form_sees_updates_and_runs_behind_held_back_frames(pkg, api, orc
             # rays that graze past sphere 0 where it stands and meet it head on once it has moved
             rays = np.repeat(abi.make_path_rays([moved + [0, 0, -50 * r]], [[0, 0, 1]], 9), 70)
             rays["rng"] = np.arange(70) + 100
-            d_rays, d_out = tq.DevBuf(rays.nbytes).upload(rays), tq.DevBuf(70 * 16)
+            d_rays, d_out = DevBuf(rays.nbytes).upload(rays), DevBuf(70 * 16)
             if with_passes:
                 before = tr.radiance_trace(rays)
             mgr.RenderFrames(5)
@@ -358,7 +340,7 @@ def test_radiance_calls_leave_no_trace(pkg, api, orc):
     sc, p, origins, dirs, states, want = camera_case(pkg, api, orc, "config3_bvh", w, h, True, None)
     rays = pkg.abi.make_path_rays(origins.reshape(-1, 3), dirs.reshape(-1, 3), states.reshape(-1))
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16))
     try:
         # a rendering context, whole and as part 1 of 2 of a strip partition: everything a caller can read is the same before and after
         for part in (None, 1):
@@ -394,7 +376,7 @@ def test_errors(pkg, api, orc):
     n = 100
     rays = abi.make_path_rays(origins.reshape(-1, 3), dirs.reshape(-1, 3), states.reshape(-1))[:n].copy()
     out = np.zeros(n, dtype=abi.RADIANCE_DTYPE)
-    d_rays, d_out = tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16)
+    d_rays, d_out = DevBuf(n * 32).upload(rays), DevBuf(n * 16)
     bad, state, ok = abi.RT_ERR_INVALID_ARG, abi.RT_ERR_STATE, abi.RT_OK
     host, dev = api.radiance_trace, api.radiance_trace_buffers
     tr = api.create_tracer(0)
@@ -447,7 +429,7 @@ def test_watchdog_fails_the_pass_not_the_context(pkg, api, orc, monkeypatch):
     sc, p, origins, dirs, states, want = camera_case(pkg, api, orc, "config3_bvh", w, h, False, None)
     rays = abi.make_path_rays(origins.reshape(-1, 3), dirs.reshape(-1, 3), states.reshape(-1))[:256]
     n = len(rays)
-    bufs = (tq.DevBuf(n * 32).upload(rays), tq.DevBuf(n * 16))
+    bufs = (DevBuf(n * 32).upload(rays), DevBuf(n * 16))
     images = []
     for lib, tr in ((api, api.create_tracer(0)), (orc, orc.create_tracer(1))):
         try:

@@ -15,6 +15,9 @@ import os
 import numpy as np
 import pytest
 
+from bvh_support import mesh_cases
+from fuzz_scenes import random_scene
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _spec = importlib.util.spec_from_file_location("rt_ref_lib", os.path.join(ROOT, "oracle", "ref_lib.py"))
@@ -85,8 +88,8 @@ SPHERE_CASES = [  # BASELINE config 1 exactly; config 2 = the headline image; sp
     ("config1_exact", lambda pkg: pkg.scenes.get(1), 256, 256, 1),
     ("config2_headline", lambda pkg: pkg.scenes.get(2), 480, 270, 2),
     ("config2_ragged", lambda pkg: pkg.scenes.get(2), 61, 35, 3),
-    ("fuzz3_spheres_and_meshes", lambda pkg: __import__("test_gpu_fuzz").random_scene(pkg, 3)[0], None, None, None),
-    ("fuzz5_spheres_and_meshes", lambda pkg: __import__("test_gpu_fuzz").random_scene(pkg, 5)[0], None, None, None),
+    ("fuzz3_spheres_and_meshes", lambda pkg: random_scene(pkg, 3)[0], None, None, None),
+    ("fuzz5_spheres_and_meshes", lambda pkg: random_scene(pkg, 5)[0], None, None, None),
 ]
 
 
@@ -129,8 +132,7 @@ def test_gpu_bvh_builder_equals_the_compiled_reference_bvh_text(pkg, api):
         pytest.fail("stale reference library: " + why)
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import test_bvh
-    meshes = test_bvh.mesh_cases(pkg) + [pkg.meshes.icosphere(5, 1.0, 2), pkg.meshes.icosphere(6, 1.0, 4)]
+    meshes = mesh_cases(pkg) + [pkg.meshes.icosphere(5, 1.0, 2), pkg.meshes.icosphere(6, 1.0, 4)]
 
     def same(a, b):
         sa, sb = dict(a[2]), dict(b[2])

@@ -19,18 +19,13 @@ import pytest
 
 import denoise_reference as dref
 import reproject_reference as ref
-import test_gpu_aov as ga
-from test_gpu_denoise import DevBuf, assert_same_bits
+import aov_support as ga
+from gpu_support import DevBuf, assert_same_bits
+from reproject_support import NEARBY, move_camera, records_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F = np.float32
-
-
-def records_of(pkg, dev, h, w):
-    out = np.zeros((h, w), dtype=pkg.abi.AOV_DTYPE)
-    assert dev.hip.hipMemcpy(C.c_void_p(out.ctypes.data), dev.p, C.c_size_t(out.nbytes), C.c_int(2)) == 0
-    return out
 
 
 def reproject_on_device(pkg, tr, rgba, prev, cur, p):
@@ -44,19 +39,6 @@ def reproject_on_device(pkg, tr, rgba, prev, cur, p):
     finally:
         for d in bufs:
             d.free()
-
-
-def move_camera(pkg, mgr, offset=(0.25, 0.1, 0.15), turn=(0.0, 2.0, 0.0)):
-    """The manager's camera, `offset` further and `turn` degrees on; the new parameters are set (rt_set_params)."""
-    t = mgr.camera.transform
-    if hasattr(t, "position"):
-        mgr.camera.transform = pkg.Transform(tuple(np.array(t.position) + np.array(offset)), tuple(np.array(t.euler) + np.array(turn)))
-    else:  # a camera given by its matrix (scene files): the offset alone
-        assert not any(turn)
-        m = np.array(t.localToWorldMatrix, dtype=np.float64)
-        m[:3, 3] += offset
-        mgr.camera.transform = type(t)(m)
-    mgr.SetShaderParams()
 
 
 # ---------------------------------------------------------------- 6. the passes alone, bits
@@ -185,7 +167,7 @@ root = sys.argv[1]
 sys.path.insert(0, root)
 sys.path.insert(0, os.path.join(root, "tests"))
 import __graft_entry__ as graft
-import test_gpu_aov as ga
+import aov_support as ga
 import denoise_reference as dref
 import reproject_reference as ref
 pkg = graft.load_package()
@@ -633,9 +615,6 @@ def test_watchdog_of_the_internal_aov_pass_leaves_the_accumulator_untouched(pkg,
 
 
 # ---------------------------------------------------------------- 12. it reprojects
-NEARBY = dict(offset=(0.05, 0.02, 0.03), turn=(0.0, 0.4, 0.0))
-
-
 def test_it_reprojects(pkg, api):
     """Config 3 at 320 x 180.  32 frames at view A, a move to the nearby view B, rt_reproject_accumulated with the default parameters, 4 more
     frames, rt_resolve: C.  R: reset at B, then 4 frames.  G: the mean of 1,024 frames at B.  Over the pixels with carried history,

@@ -14,16 +14,17 @@ STATS build a launch with the bit evaluates both forms and counts a difference a
   a radiance batch with an unnormalised direction on a context whose frame launches carry the bit: the side passes keep the whole function.
 
 At most 64 x 36 pixels, two rays per pixel, three frames."""
-import contextlib
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
+from gpu_support import environment
+
 pytestmark = pytest.mark.gpu
 F = np.float32
 F3 = C.c_float * 3
+# all of them are read when a context is made or a scene is uploaded
 ENV = ("RT_SKY_SUN", "RT_POOL", "RT_POOL_MIN_ITEMS", "RT_HOLD_BACK", "RT_COALESCE")
 FLAT_WAYS = [("pooled", {"RT_POOL_MIN_ITEMS": "0"}), ("single waves", {"RT_POOL": "0"})]
 BVH_WAYS = [("bvh", {})]
@@ -58,22 +59,6 @@ REFUSED = {
     "intensity NaN": dict(sunIntensity=float("nan")),
     "colour 1e30": dict(sunColor=(1.0, 1e30, 1.0)),
 }
-
-
-@contextlib.contextmanager
-def environment(env):
-    """all of them are read when a context is made or a scene is uploaded"""
-    old = {k: os.environ.get(k) for k in ENV}
-    for k in ENV:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
 
 
 def same(got, want):
@@ -118,7 +103,7 @@ def check(api, orc, drive, ways):
     c.close()
     for name, env in ways:
         for sky_sun in ("1", "0"):
-            with environment(dict(env, RT_SKY_SUN=sky_sun)):
+            with environment(dict(env, RT_SKY_SUN=sky_sun), ENV):
                 for stats in (False, True):
                     g = api.create_tracer(0)
                     g.enable_stats(stats)
@@ -185,7 +170,7 @@ def test_the_bit_follows_the_launch_not_the_context(pkg, api, orc, make_scene):
         return out
 
     def run(lib, env, read_between, stats=False):
-        with environment(env):
+        with environment(env, ENV):
             tr = lib.create_tracer(0) if lib is api else lib.create_tracer(8)
             if lib is api:
                 tr.enable_stats(stats)
@@ -215,7 +200,7 @@ def test_a_side_pass_keeps_the_whole_function(pkg, api, orc):
     pow(1e30, 2) = inf and inf * 0 = NaN in GetEnvironmentLight, 0.35 / 0.3 / 0.35 without the sun's addend.  The context's frame
     launches carry the bit; the batch must not."""
     sc, (w, h) = flat_scene(pkg)
-    with environment({}):
+    with environment({}, ENV):
         tr = api.create_tracer(0)
         try:
             mgr = sc.make_manager(tr, api, w, h)

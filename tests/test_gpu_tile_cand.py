@@ -11,37 +11,16 @@ rt_debug_tile_cand with what the caps say: a table that silently stayed off woul
 
 The sequences are the ones in which a stale table would show: a sphere moved across the image between frames, a camera move, single
 frames (two parts, one per stream) alternating with fused launches (which alternate between the streams themselves)."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from gpu_support import KEYS, bits, environment
+
 pytestmark = pytest.mark.gpu
-KEYS = ["segments", "innerSteps", "leafSteps", "triTests", "sphereTests", "modelVisits", "pixelFrames"]
+# RT_TILE_CAND and RT_POOL_MIN_ITEMS are read when a context is made, RT_POOL when a scene is uploaded
+ENV = ("RT_TILE_CAND", "RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")
 WAYS = [("table, pooled", {"RT_TILE_CAND": "1", "RT_POOL_MIN_ITEMS": "0"}), ("no table, pooled", {"RT_TILE_CAND": "0", "RT_POOL_MIN_ITEMS": "0"}),
         ("table, single waves", {"RT_TILE_CAND": "1", "RT_POOL": "0"}), ("no table, single waves", {"RT_TILE_CAND": "0", "RT_POOL": "0"})]
-
-
-@contextlib.contextmanager
-def environment(env):
-    """RT_TILE_CAND and RT_POOL_MIN_ITEMS are read when a context is made, RT_POOL when a scene is uploaded"""
-    names = ("RT_TILE_CAND", "RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")
-    old = {k: os.environ.get(k) for k in names}
-    for k in names:
-        os.environ.pop(k, None)
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def check(pkg, api, orc, drive, table=True, part=None):
@@ -54,7 +33,7 @@ def check(pkg, api, orc, drive, table=True, part=None):
     c.close()
     first = None
     for name, env in WAYS:
-        with environment(env):
+        with environment(env, ENV):
             for stats in (False, True):
                 g = api.create_tracer(0)
                 if part:

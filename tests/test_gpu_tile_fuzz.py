@@ -15,9 +15,11 @@ import numpy as np
 import pytest
 
 import capfuzz_scenes as cs
-from test_gpu_tile_tri import KEYS, bits, environment
+from capfuzz_scenes import WALK_SEEDS, _walk
+from gpu_support import KEYS, bits, environment
 
 pytestmark = pytest.mark.gpu
+ENV = ("RT_TILE_TRI", "RT_TILE_CAND", "RT_PRIMARY", "RT_POOL", "RT_POOL_MIN_ITEMS")   # the variables tests/test_gpu_tile_tri.py clears
 POOLED, SINGLE = {"RT_POOL_MIN_ITEMS": "0"}, {"RT_POOL": "0"}   # pooled workgroups also at these small sizes / single waves
 
 
@@ -42,7 +44,7 @@ def _check_scene(pkg, api, orc, make, part, table):
     assert wantCounters["segments"] > 0
     first = None
     for name, env in (("pooled", POOLED), ("single waves", SINGLE)):
-        with environment(env):
+        with environment(env, ENV):
             for stats in (False, True):
                 g = api.create_tracer(0)
                 if part:
@@ -88,7 +90,7 @@ def test_masks_cut_work_over_the_family(pkg, api):
     total = {}
     for switch in ("1", "0"):
         total[switch] = 0
-        with environment({"RT_TILE_TRI": switch, **POOLED}):
+        with environment({"RT_TILE_TRI": switch, **POOLED}, ENV):
             for seed in cs.EMPTY_TRI_MASK_SEEDS:
                 g = api.create_tracer(0)
                 if cs.partition_of(seed):
@@ -104,39 +106,6 @@ def test_masks_cut_work_over_the_family(pkg, api):
 
 
 # ---- one context through the calls whose arguments are part of the TileCandKey ----------------------------------------------------------
-
-WALK_SEEDS = (2, 4, 6, 12, 13, 18, 22)        # scenes with spheres and models
-OTHER_IN_CAP = (19, 11, 3, 23, 20, 6, 12)     # what upload_scene replaces them with
-STEPS = 10
-
-
-def _walk(pkg, seed):
-    """the walk of a seed as plain data, so that the library's manager and the oracle's take the very same steps.  Four of the six plain
-    kinds (which two are left out rotates with the seed) and the six that come once per walk, shuffled; the second in-cap upload comes
-    two steps after the over-the-cap one and defocus goes on early enough to go off again two steps later."""
-    d = cs._Draw(pkg, 7919 * seed + 1)
-    plain = ["sphere", "model", "camera", "fov", "diverge", "reset"]
-    idx = WALK_SEEDS.index(seed)
-    for k in sorted({idx % 6, (idx + 3) % 6}, reverse=True):
-        del plain[k]
-    kinds = plain + ["defocus", "resize_same_tiles", "resize", "upload_in_cap", "upload_over_a_cap", "upload_in_cap_again"]
-    assert len(kinds) == STEPS
-    for i in range(len(kinds) - 1, 0, -1):
-        j = int(d.rnd() * (i + 1))
-        kinds[i], kinds[j] = kinds[j], kinds[i]
-    if kinds.index("defocus") > STEPS - 3:
-        kinds.remove("defocus")
-        kinds.insert(int(d.rnd() * (STEPS - 2)), "defocus")
-    kinds.remove("upload_in_cap_again")   # over a cap for two steps, not for most of the walk: the steps are there to change a table's key
-    kinds.insert(min(kinds.index("upload_over_a_cap") + 2, len(kinds)), "upload_in_cap_again")
-    if kinds.index("defocus") > STEPS - 3:   # (pushed back by the insertion)
-        kinds.remove("defocus")
-        kinds.insert(0, "defocus")
-    steps = []
-    for i, kind in enumerate(kinds):
-        steps.append(dict(kind=kind, u=[d.rnd() for _ in range(12)], k=2 + int(d.rnd() * 4), over=idx % 3, other=OTHER_IN_CAP[idx] if kind == "upload_in_cap" else seed))
-    return steps
-
 
 class _Walker:
     """one manager on one tracer; step() applies a step of the walk and renders: on an idle device one RenderFrame (two parts, one per
@@ -243,7 +212,7 @@ def test_one_context_through_key_changing_calls(pkg, api, orc, seed, stats):
     """a stale table shows as a wrong pixel: after every step the accumulated image and `segments` equal the oracle's, which took the
     same steps, and the two debug calls say what the step's state says (off over a cap and under defocus, on again afterwards)"""
     want = _oracle_walk(pkg, orc, seed)
-    with environment(POOLED):
+    with environment(POOLED, ENV):
         g = api.create_tracer(0)
         g.enable_stats(stats)
         w = _Walker(pkg, api, g, seed)

@@ -23,10 +23,10 @@ from flush_table import held_at
 
 import motion_reference as mref
 import reproject_reference as rp
-import test_gpu_aov as ga
+import aov_support as ga
 import variance_reference as ref
-from test_gpu_denoise import DevBuf, assert_same_bits
-from test_gpu_reproject import NEARBY, move_camera, records_of
+from gpu_support import DevBuf, assert_same_bits
+from reproject_support import NEARBY, move_camera, records_of
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -136,7 +136,7 @@ root = sys.argv[1]
 sys.path.insert(0, root)
 sys.path.insert(0, os.path.join(root, "tests"))
 import __graft_entry__ as graft
-import test_gpu_aov as ga
+import aov_support as ga
 pkg = graft.load_package()
 api = pkg.load_library()
 for layout in (None, "dense", "pre,arena,cache"):

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import hazard_scenes as hz
+import host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -325,15 +326,9 @@ def test_tables_column_of_the_triangle_cases_is_reasoned(pkg, orc, case):
 def tile_tri_driver(tmp_path_factory):
     """tests/tile_tri_driver.cpp as tests/test_tile_fuzz.py builds it: a stand-alone program under the address and undefined-behaviour
     sanitizers"""
-    import shutil
-    import subprocess
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
     d = tmp_path_factory.mktemp("hazard_tiles")
-    exe = str(d / "tile_tri_san")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", "tile_tri_driver.cpp"), "-o", exe])
+    exe = host_driver.build(d, "tile_tri", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                            "-static-libasan", "-static-libubsan"], exe="tile_tri_san")
     return d, exe
 
 

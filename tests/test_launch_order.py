@@ -6,22 +6,16 @@ and the buffers each step touches; a small context mirrors launch_frames around 
 (a) every pair of conflicting accesses is ordered in issue order; (b) the halves of a two-part frame, and in steady state the trace
 kernels of consecutive fused launches on different streams, are NOT ordered against each other; (c) the exact record / wait lists
 of three steady-state sequences; (d) the checker itself: dropping the waits of an event kind that matters produces a violation."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import host_driver
 
 
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("launch_order") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "launch_order_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path_factory.mktemp("launch_order"), "launch_order", ["-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror"])
 
     def run(*args):
         return subprocess.check_output([exe, *args], text=True, timeout=600).splitlines()

@@ -5,43 +5,16 @@ the tile counter's conservation against a simulation of the kernel's consumption
 ("Which workgroup shape a launch gets") states it, the variant slots and LDS bytes, the staging slabs and the frames per fused launch,
 and the suspension tuner's rule."""
 import math
-import os
 import random
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from launch_plan_support import one, plan  # noqa: F401  (plan: the fixture that builds tests/launch_plan_driver.cpp)
+
 CUS = 256
 MIB = 1 << 20
 SLAB_BUDGET = 1536 * MIB  # RT_FUSE_SLAB_BYTES
-
-
-@pytest.fixture(scope="module")
-def plan(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("launch_plan") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", os.path.join(ROOT, "tests", "launch_plan_driver.cpp"), "-o", exe])
-
-    def ask(*requests):
-        """requests: (command, {key: value}); one dict of the answer's fields per request"""
-        text = "".join(cmd + "".join(f" {k}={int(v) if isinstance(v, bool) else v}" for k, v in kw.items()) + "\n" for cmd, kw in requests)
-        lines = subprocess.run([exe], input=text, capture_output=True, text=True, timeout=600, check=True).stdout.splitlines()
-        assert len(lines) == len(requests), lines[:3]
-        out = []
-        for line in lines:
-            assert "=" in line and not line.startswith(("ERROR", "BROKEN")), line
-            out.append({k: float(v) if "." in v else int(v) for k, v in (t.split("=") for t in line.split())})
-        return out
-    ask.exe = exe
-    return ask
-
-
-def one(plan, cmd, **kw):
-    return plan((cmd, kw))[0]
 
 
 @pytest.mark.parametrize("seed", [1, 2, 3])

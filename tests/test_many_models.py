@@ -12,28 +12,22 @@
   7. the order in which a lane visits its candidates and the unfiltered tail, replayed on the host around the helper the kernel uses
      (tests/many_tail_driver.cpp), plainly and under the address and undefined-behaviour sanitizers, as a stand-alone program."""
 import os
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import host_driver
 import many_models as mm
-from test_launch_plan import one, plan  # noqa: F401  (plan: the fixture that builds tests/launch_plan_driver.cpp)
+import scene_prep_support as sp
+from launch_plan_support import one, plan  # noqa: F401  (plan: the fixture that builds tests/launch_plan_driver.cpp)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import __graft_entry__ as graft  # noqa: E402
 
 ref_lib = graft._ref_lib()
-
-
-def _cxx():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    return cxx
 
 
 # ---- 1. the catalogue ----------------------------------------------------------------------------------------------------------------
@@ -74,9 +68,7 @@ def test_edges_are_the_ends_of_the_mask():
 def test_planted_models_are_never_filtered(pkg, orc, tmp_path):
     """always1300 through rt_scene_prep.h (tests/scene_prep_driver.cpp): the filter records of the planted models say `always`, the
     unusable leaf root with count 0, and those of crowd1300 at the same indices do not"""
-    import test_scene_prep as sp
-    exe = str(tmp_path / "driver")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", os.path.join(ROOT, "tests", "scene_prep_driver.cpp"), "-o", exe, "-pthread"])
+    exe = host_driver.build(tmp_path, "scene_prep", ["-std=c++17", "-O2"], after=["-pthread"])
     always = {}
     for name in ("always1300", "crowd1300"):
         sc = mm.scene(pkg, orc, name)
@@ -212,11 +204,9 @@ def test_tail_rule_visits_every_model_once_in_order(tmp_path):
     """tests/many_tail_driver.cpp around rt_plan::next_unfiltered_model, the expression rt_kernels.h's vote and phase A share: n = 65,
     1087, 1088 and 1300 models; no candidate, all, only 1086, all but 1086, every word alone, the ends of every word, 200 random sets.
     Built plainly (warning-free) and with the sanitizers linked into the program; nothing sanitized is loaded into python."""
-    src = os.path.join(ROOT, "tests", "many_tail_driver.cpp")
-    plain, san = str(tmp_path / "tail"), str(tmp_path / "tail_san")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
-    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           src, "-o", san])
+    plain = host_driver.build(tmp_path, "many_tail", ["-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror"], exe="tail")
+    san = host_driver.build(tmp_path, "many_tail", ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"],
+                            exe="tail_san")
     for exe in (plain, san):
         p = subprocess.run([exe], capture_output=True, text=True, timeout=600)
         assert p.returncode == 0 and p.stdout.strip() == "MANY_TAIL_OK", (exe, p.returncode, p.stdout[-300:], p.stderr[-3000:])

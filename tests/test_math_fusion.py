@@ -4,23 +4,17 @@ tests/math_fusion_driver.cpp enumerates, for each fused step, every multiplier t
 product whether the binary32 product is exact, and compares std::fma with multiply-then-add bit for bit over addends the function meets.
 A fusion is sound where `inexact` and `differ` are 0.  The second Cody-Waite step of rt_reduce_pio2 is the counter-example the header keeps
 unfused: exact for |n| < 2^13, not for every n that |x| < 3e4 admits."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "math_fusion_driver.cpp")
+import host_driver
+
 FUSED = ["reduce_P1", "cos_half_z", "smoothstep_2t", "exp_k_ln2hi", "log_k_ln2hi"]
 
 
 def build_and_run(tmp, extra):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Werror", *extra, SRC, "-o", exe])
+    exe = host_driver.build(tmp, "math_fusion", ["-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Werror", *extra])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600, check=True).stdout
     rows = {}
     for line in out.splitlines():

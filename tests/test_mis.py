@@ -7,12 +7,13 @@ the address and undefined-behaviour sanitizers."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import host_driver
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mis_reference as mr  # noqa: E402
@@ -190,11 +191,7 @@ def test_mis_map_driver_is_clean_under_address_and_undefined_sanitizers(tmp_path
     """The table and the map of generated scenes (instances, mirrored, dark and glass models, zero-area triangles, excluded spheres),
     the packed device words and the lookup for every hit and for triangles outside a model's range.  A program of its own: nothing
     of it is loaded into this process."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path / "mis_map_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "mis_map_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path, "mis_map", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                            exe="mis_map_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and p.stdout.strip() == "MIS_MAP_OK", (p.returncode, p.stdout, p.stderr)

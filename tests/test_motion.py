@@ -6,16 +6,16 @@ bit, every pixel, every channel."""
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_driver
 import motion_reference as mref
 import reproject_reference as ref
-from test_reproject import assert_same_bits
+from gpu_support import assert_same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -140,12 +140,7 @@ def test_motion_from_scene_equals_its_restatement_and_is_rigid(pkg, api, seed):
 # ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("motion_math") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "motion_math_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path_factory.mktemp("motion_math"), "motion_math", ["-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
 
     def reproject(rgba, prev, cur, motion, view_params, cam, max_plane, min_dot, max_history, flags=0):
         h, w = rgba.shape[:2]

@@ -6,12 +6,13 @@ of the feature — passes its stand-alone driver (tests/light_table_driver.cpp) 
 sanitizers."""
 import os
 import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
+
+import host_driver
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import nee_reference as nr  # noqa: E402
@@ -121,11 +122,7 @@ def test_light_table_driver_is_clean_under_address_and_undefined_sanitizers(tmp_
     """Which objects become entries (glass, NaN, non-positive, zero-area, zero-radius, checkered), the mirrored transform's swap, one set
     of entries per instance, the cdf and the pick rule at 0, 1 and every cdf value, the entry cap, the dump, and rt_nee_launch.h's
     argument checks and sizes.  A program of its own: nothing of it is loaded into this process."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path / "light_table_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "light_table_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path, "light_table", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                            exe="light_table_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and p.stdout.strip() == "LIGHT_TABLE_OK", (p.returncode, p.stdout, p.stderr)

@@ -10,29 +10,21 @@ the real rt_scene_prep.h, every table entry equals BITWISE the per-ray formula o
 is off for defocus != 0, the run-time switch, a camera origin component of -0, a non-finite camera, more spheres / models / triangles than
 the caps, a non-FLAT scene and a table entry that is not finite."""
 import os
-import shutil
 import subprocess
 
 import pytest
 
+import host_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _cxx():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    return cxx
 
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     d = tmp_path_factory.mktemp("primary")
-    src = os.path.join(ROOT, "tests", "primary_driver.cpp")
-    plain, san = str(d / "driver"), str(d / "driver_san")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", src, "-o", plain, "-pthread"])
-    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", src, "-o", san, "-pthread"])
+    plain = host_driver.build(d, "primary", ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"], after=["-pthread"])
+    san = host_driver.build(d, "primary", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                         "-static-libasan", "-static-libubsan"], exe="driver_san", after=["-pthread"])
     return {"plain": plain, "san": san}
 
 

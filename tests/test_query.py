@@ -5,11 +5,12 @@ of the entry points — passes its stand-alone driver (tests/query_launch_driver
 sanitizers."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+import host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -87,11 +88,7 @@ def test_every_call_refuses_a_null_context(pkg, api):
 def test_launch_header_driver_is_clean_under_address_and_undefined_sanitizers(tmp_path):
     """Blocks and grid at n = 0, 1, 63, 64, 65, 2^26; the byte-size overflow guard; the overlap predicate on touching, nested and disjoint
     ranges; the shared argument checks.  A program of its own: nothing of it is loaded into this process."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path / "query_launch_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "query_launch_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path, "query_launch", ["-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                            exe="query_launch_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and p.stdout.strip() == "QUERY_LAUNCH_OK", (p.returncode, p.stdout, p.stderr)

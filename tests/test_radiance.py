@@ -5,11 +5,12 @@ context; and ray-tracing_amd/csrc/rt_radiance_launch.h — the HIP-free half of 
 (tests/radiance_launch_driver.cpp) built with the address and undefined-behaviour sanitizers."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
+
+import host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -95,11 +96,7 @@ def test_launch_header_driver_is_clean_under_address_and_undefined_sanitizers(tm
     """Blocks and grid at n = 0, 1, 63, 64, 65, 2^26; the hand-out of blocks (first block by wave, the rest by ticket) in three drawing
     orders; the byte-size overflow guard; the overlap predicate; the shared argument checks at this pass's record size.  A program of
     its own: nothing of it is loaded into this process."""
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path / "radiance_launch_driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           os.path.join(ROOT, "tests", "radiance_launch_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path, "radiance_launch", ["-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+                            exe="radiance_launch_driver")
     p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0 and p.stdout.strip() == "RADIANCE_LAUNCH_OK", (p.returncode, p.stdout, p.stderr)

@@ -25,6 +25,9 @@ import sys
 import numpy as np
 import pytest
 
+from bvh_support import mesh_cases
+from fuzz_scenes import random_scene
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -52,7 +55,7 @@ def ref(pkg):
     return lib
 
 
-def bits(a):
+def float32_bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
@@ -77,8 +80,8 @@ def render_pair(pkg, orc_lib, ref_lib_, scene_factory, w, h, frames, seed, tweak
 
 def assert_same(out, what):
     (acc_o, fr_o, c_o, f_o), (acc_r, fr_r, c_r, f_r) = out
-    assert np.array_equal(bits(fr_o), bits(fr_r)), f"{what}: FrameRender differs in {int(np.any(bits(fr_o) != bits(fr_r), axis=-1).sum())} pixels"
-    assert np.array_equal(bits(acc_o), bits(acc_r)), f"{what}: AccumulatedRender differs in {int(np.any(bits(acc_o) != bits(acc_r), axis=-1).sum())} pixels"
+    assert np.array_equal(float32_bits(fr_o), float32_bits(fr_r)), f"{what}: FrameRender differs in {int(np.any(float32_bits(fr_o) != float32_bits(fr_r), axis=-1).sum())} pixels"
+    assert np.array_equal(float32_bits(acc_o), float32_bits(acc_r)), f"{what}: AccumulatedRender differs in {int(np.any(float32_bits(acc_o) != float32_bits(acc_r), axis=-1).sum())} pixels"
     assert f_o == f_r
     # the shader's own counters: stats[0] = triangle tests (RC:254), stats[1] = box tests = 2 per inner node (RC:271)
     assert c_o["triTests"] == c_r["triTests"] and c_o["innerSteps"] == c_r["innerSteps"], (what, c_o, c_r)
@@ -113,7 +116,6 @@ def test_oracle_equals_the_compiled_reference_text(pkg, orc, ref, case):
 def test_random_model_scenes(pkg, orc, ref, seed):
     """the fuzz generator of the GPU suite (random meshes, transforms with non-uniform scale, all three material flags,
     random camera / bounces / spp / sky / depth of field / BVH quality), spheres removed"""
-    from test_gpu_fuzz import random_scene
     sc0, render_seed = random_scene(pkg, seed)
     if not sc0.models:
         pytest.skip("no models drawn for this seed")
@@ -171,13 +173,13 @@ def test_rng_functions(orc, ref):
     for s in [0, 1, 0xFFFFFFFF, 0x80000000] + [int(x) for x in rng.integers(0, 2**32, 2000)]:
         a, b = C.c_uint32(s), C.c_uint32(s)
         assert orc.next_random(C.byref(a)) == ref.next_random(C.byref(b)) and a.value == b.value
-        assert bits(orc.random_value(C.byref(a))) == bits(ref.random_value(C.byref(b))) and a.value == b.value
+        assert float32_bits(orc.random_value(C.byref(a))) == float32_bits(ref.random_value(C.byref(b))) and a.value == b.value
         da = _call(orc, "random_direction", 3, C.byref(a))
         db = _call(ref, "random_direction", 3, C.byref(b))
-        assert np.array_equal(bits(da), bits(db)) and a.value == b.value
+        assert np.array_equal(float32_bits(da), float32_bits(db)) and a.value == b.value
         pa = _call(orc, "random_point_in_circle", 2, C.byref(a))
         pb = _call(ref, "random_point_in_circle", 2, C.byref(b))
-        assert np.array_equal(bits(pa), bits(pb)) and a.value == b.value
+        assert np.array_equal(float32_bits(pa), float32_bits(pb)) and a.value == b.value
 
 
 def test_ray_triangle_box_sphere(pkg, orc, ref):
@@ -197,19 +199,19 @@ def test_ray_triangle_box_sphere(pkg, orc, ref):
         for cull in (0, 1):
             a = _call(orc, "ray_triangle", 6, _f3(pos), _f3(d), tri.ctypes.data, cull)
             b = _call(ref, "ray_triangle", 6, _f3(pos), _f3(d), tri.ctypes.data, cull)
-            assert np.array_equal(bits(a), bits(b)), (i, cull, a, b)
+            assert np.array_equal(float32_bits(a), float32_bits(b)), (i, cull, a, b)
         lo = rng.uniform(-2, 1, 3).astype(np.float32)
         hi = (lo + rng.uniform(0, 2, 3)).astype(np.float32)
         if i % 5 == 0:
             pos = ((lo + hi) / 2).astype(np.float32)  # origin inside the box: dst 0
         if i % 13 == 0:
             pos[0] = lo[0]  # on a slab plane with a parallel ray: 0 * inf
-        assert bits(orc.ray_box(_f3(pos), _f3(d), _f3(lo), _f3(hi))) == bits(ref.ray_box(_f3(pos), _f3(d), _f3(lo), _f3(hi)))
+        assert float32_bits(orc.ray_box(_f3(pos), _f3(d), _f3(lo), _f3(hi))) == float32_bits(ref.ray_box(_f3(pos), _f3(d), _f3(lo), _f3(hi)))
         centre = rng.uniform(-2, 2, 3).astype(np.float32)
         radius = float(rng.uniform(0.1, 2.5))
         a = _call(orc, "ray_sphere", 6, _f3(pos), _f3(d), _f3(centre), radius)
         b = _call(ref, "ray_sphere", 6, _f3(pos), _f3(d), _f3(centre), radius)
-        assert np.array_equal(bits(a), bits(b)), (i, a, b)
+        assert np.array_equal(float32_bits(a), float32_bits(b)), (i, a, b)
 
 
 def test_fresnel_refract_sky_material(pkg, orc, ref):
@@ -219,8 +221,8 @@ def test_fresnel_refract_sky_material(pkg, orc, ref):
         n = _unit(rng)
         d = _unit(rng)
         ia, ib = (1.0, float(rng.uniform(1.0, 2.4))) if i % 2 else (float(rng.uniform(1.0, 2.4)), 1.0)
-        assert bits(orc.reflectance(_f3(d), _f3(n), ia, ib)) == bits(ref.reflectance(_f3(d), _f3(n), ia, ib))
-        assert np.array_equal(bits(_call(orc, "refract", 3, _f3(d), _f3(n), ia, ib)), bits(_call(ref, "refract", 3, _f3(d), _f3(n), ia, ib)))
+        assert float32_bits(orc.reflectance(_f3(d), _f3(n), ia, ib)) == float32_bits(ref.reflectance(_f3(d), _f3(n), ia, ib))
+        assert np.array_equal(float32_bits(_call(orc, "refract", 3, _f3(d), _f3(n), ia, ib)), float32_bits(_call(ref, "refract", 3, _f3(d), _f3(n), ia, ib)))
         p = pkg.abi.RtParams()
         p.useSky = int(i % 9 != 0)
         p.sunFocus, p.sunIntensity = float(rng.uniform(50, 900)), float(rng.uniform(0, 20))
@@ -228,8 +230,8 @@ def test_fresnel_refract_sky_material(pkg, orc, ref):
         p.dirToSun[:] = [float(x) for x in _unit(rng)]
         if i % 6 == 0:
             d[1] = np.float32(rng.uniform(-0.012, 0.002))  # around the ground / horizon smoothstep (RC:176)
-        assert np.array_equal(bits(_call(orc, "environment_light", 3, C.byref(p), _f3(d))),
-                              bits(_call(ref, "environment_light", 3, C.byref(p), _f3(d))))
+        assert np.array_equal(float32_bits(_call(orc, "environment_light", 3, C.byref(p), _f3(d))),
+                              float32_bits(_call(ref, "environment_light", 3, C.byref(p), _f3(d))))
         mat[0]["flag"] = int(rng.integers(0, 3))
         for k in ("diffuseCol", "emissionCol", "specularCol"):
             mat[0][k] = rng.uniform(0, 1, 4)
@@ -237,7 +239,7 @@ def test_fresnel_refract_sky_material(pkg, orc, ref):
         for spec in (0, 1):
             a = _call(orc, "material_colour", 3, mat.ctypes.data, _f3(pos), _f3(n), spec)
             b = _call(ref, "material_colour", 3, mat.ctypes.data, _f3(pos), _f3(n), spec)
-            assert np.array_equal(bits(a), bits(b))
+            assert np.array_equal(float32_bits(a), float32_bits(b))
 
 
 def test_ray_collision_and_single_pixels(pkg, orc, ref):
@@ -255,14 +257,14 @@ def test_ray_collision_and_single_pixels(pkg, orc, ref):
         b = _call(ref, "ray_collision", 10, trs[1].h, _f3(pos), _f3(d))
         if a[0] == 0 and b[0] == 0:
             continue  # a miss leaves the other fields undefined in the reference (RC:337)
-        assert np.array_equal(bits(a), bits(b)), (i, a, b)
+        assert np.array_equal(float32_bits(a), float32_bits(b)), (i, a, b)
     for i in range(300):
         x, y, frame = int(rng.integers(0, 120)), int(rng.integers(0, 68)), int(rng.integers(1, 100))
         if i < 4:
             x, y = (119, 67) if i % 2 else (119, int(rng.integers(0, 68)))  # last column / row: quirk Q1
         a = _call(orc, "trace_pixel", 3, trs[0].h, x, y, frame)
         b = _call(ref, "trace_pixel", 3, trs[1].h, x, y, frame)
-        assert np.array_equal(bits(a), bits(b)), (x, y, frame, a, b)
+        assert np.array_equal(float32_bits(a), float32_bits(b)), (x, y, frame, a, b)
     for tr in trs:
         tr.close()
 
@@ -322,7 +324,6 @@ def test_oracle_equals_the_reference_text_with_the_sphere_hook(pkg, orc, ref_sph
 @pytest.mark.parametrize("seed", range(6))
 def test_random_scenes_with_spheres_and_models(pkg, orc, ref_spheres, seed):
     """the GPU suite's fuzz generator WITH its spheres: spheres inside / in front of / behind meshes, glass spheres, equal hits"""
-    from test_gpu_fuzz import random_scene
     sc0, render_seed = random_scene(pkg, seed)
     out = render_pair_with_spheres(pkg, orc, ref_spheres, lambda: random_scene(pkg, seed)[0], sc0.width, sc0.height, sc0.frames, render_seed)
     assert_same(out, f"fuzz {seed} with spheres")
@@ -361,12 +362,12 @@ def test_row_window_of_the_dispatcher(pkg, orc, ref_spheres):
             part.render_frame()
         rows = np.concatenate([np.arange(s_ * 8, min(H, s_ * 8 + 8)) for s_ in strips])
         a, b = whole.read_accumulated(), part.read_accumulated()
-        assert np.array_equal(bits(a[rows]), bits(b[rows]))
+        assert np.array_equal(float32_bits(a[rows]), float32_bits(b[rows]))
         other = np.setdiff1d(np.arange(H), rows)
         assert not b[other].any()
         imgs.append(b[rows])
         whole.close(), part.close()
-    assert np.array_equal(bits(imgs[0]), bits(imgs[1]))
+    assert np.array_equal(float32_bits(imgs[0]), float32_bits(imgs[1]))
 
 
 DEGENERATE = [(1, 1), (1, 13), (13, 1), (2, 2)]
@@ -464,8 +465,7 @@ def ref_bvh(pkg):
 
 def _bvh_meshes(pkg):
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import test_bvh
-    return test_bvh.mesh_cases(pkg) + [pkg.meshes.icosphere(4, 1.0, 7), pkg.meshes.icosphere(5, 1.0, 2), pkg.meshes.rounded_cube(12)]
+    return mesh_cases(pkg) + [pkg.meshes.icosphere(4, 1.0, 7), pkg.meshes.icosphere(5, 1.0, 2), pkg.meshes.rounded_cube(12)]
 
 
 def _same_build(a, b):

@@ -6,14 +6,15 @@ the kernels call, here run by the host driver tests/reproject_math_driver.cpp â€
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_driver
 import reproject_reference as ref
+from gpu_support import assert_same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -108,12 +109,7 @@ def test_default_params_are_as_the_header_states_them(pkg, api):
 # ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("reproject_math") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "reproject_math_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path_factory.mktemp("reproject_math"), "reproject_math", ["-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
 
     def run(blob, h, w, via_file=None):
         if via_file:
@@ -134,15 +130,6 @@ def driver(tmp_path_factory):
         return run(struct.pack("<4i", 1, w, h, 0) + rgba.tobytes(), h, w)
     reproject.resolve = resolve
     return reproject
-
-
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    if len(bad):
-        y, x, k = bad[0]
-        raise AssertionError(f"{what}: {len(set(map(tuple, bad[:, :2])))} pixels differ; first at row {y}, column {x}, channel {k}: "
-                             f"got {got[y, x]}, want {want[y, x]}")
 
 
 def test_the_synthetic_views_cover_what_they_are_there_for(pkg, orc):

@@ -8,78 +8,32 @@ here runs the sanitized build; the plain build only has to compile warning-free 
 What is checked: validation of corrupted scenes (same verdicts as the library, on the worker-thread path and on the sequential walk),
 the conservative root filter boxes, the packed filter pair records, the chunk partition, the sphere records."""
 import os
-import shutil
 import subprocess
 import time
 
 import numpy as np
 import pytest
 
+import host_driver
 from scene_corruptions import corrupted_scenes, scene_arrays
+from scene_prep_support import FILTER, ask, write_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "ray-tracing_amd", "csrc")
 
-FILTER = np.dtype([("bMin", "<f4", 3), ("bMax", "<f4", 3), ("always", "<u4"), ("innerRoot", "<u4")])
 CHUNK_MODELS = 16
 CHUNK = np.dtype([("bMin", "<f4", 3), ("bMax", "<f4", 3), ("always", "<u4"), ("count", "<u4"), ("innerRoots", "<u4"), ("pad", "<u4", 3),
                   ("members", "<u4", CHUNK_MODELS)])
 
 
-def _cxx():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     d = tmp_path_factory.mktemp("scene_prep")
-    src = os.path.join(ROOT, "tests", "scene_prep_driver.cpp")
-    plain, san = str(d / "driver"), str(d / "driver_san")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror", src, "-o", plain, "-pthread"])
+    plain = host_driver.build(d, "scene_prep", ["-std=c++17", "-O2", "-Wall", "-Wextra", "-Werror"], after=["-pthread"])
     # the runtimes are linked INTO the program: it needs nothing preloaded and does not care what else the loader brings
-    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
-                           src, "-o", san, "-pthread"])
+    san = host_driver.build(d, "scene_prep", ["-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"],
+                            exe="driver_san", after=["-pthread"])
     return {"plain": plain, "san": san, "dir": d}
-
-
-def _parse(buf):
-    """The driver's answers in order: a dict per `key=value` line (msg = the rest of the line), bytes per dump"""
-    out, pos = [], 0
-    while pos < len(buf):
-        nl = buf.index(b"\n", pos)
-        line, pos = buf[pos:nl].decode(), nl + 1
-        assert not line.startswith("ERROR"), line
-        if line.startswith("bytes="):
-            n = int(line[6:])
-            out.append(buf[pos:pos + n])
-            assert len(out[-1]) == n
-            pos += n
-            continue
-        head, _, msg = line.partition(" msg=")
-        d = {k: int(v) for k, v in (t.split("=") for t in head.split())}
-        if " msg=" in line:
-            d["msg"] = msg
-        out.append(d)
-    return out
-
-
-def ask(exe, requests, env=None, timeout=900):
-    """Runs the driver over the request lines; a sanitizer report (or any other failure) is a non-zero exit"""
-    e = {k: v for k, v in os.environ.items() if not k.startswith("RT_")}
-    e.update(env or {})
-    p = subprocess.run([exe], input=("\n".join(requests) + "\n").encode(), capture_output=True, env=e, timeout=timeout)
-    assert p.returncode == 0, (p.returncode, p.stderr.decode(errors="replace")[-4000:], p.stdout[-300:])
-    return _parse(p.stdout)
-
-
-def write_scene(path, models, tris, nodes, spheres):
-    with open(path, "wb") as f:
-        f.write(np.array([len(models), len(tris), len(nodes), len(spheres)], dtype="<i4").tobytes())
-        for a in (models, tris, nodes, spheres):
-            f.write(np.ascontiguousarray(a).tobytes())
 
 
 def patches(which, base, cur):
@@ -474,7 +428,7 @@ def test_sphere_records(pkg, drivers, n):
 def test_header_is_plain_cxx(tmp_path, header):
     src = tmp_path / "only.cpp"
     src.write_text(f'#include "{header}"\n')
-    subprocess.check_call([_cxx(), "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", CSRC, str(src)])
+    subprocess.check_call([host_driver.compiler(), "-std=c++17", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", CSRC, str(src)])
 
 
 def test_host_side_sources_name_no_device_api():

@@ -5,14 +5,12 @@ tests/sky_sun_driver.cpp finds the edge of the gate (smoothstep(-0.01, 0, y) >= 
 it, compares the two forms over every float within 20,000 ulps of the edge, a stride over the rest of the gate-1 range, a stride over
 |y| <= 2 and the special values — each crossed with (x, z) pairs that include +-0, +-inf and NaN — for a table of accepted parameter sets,
 and asks the predicate to refuse each hazard on its own."""
-import os
-import shutil
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "sky_sun_driver.cpp")
+import host_driver
+
 ACCEPTED = ["default", "near_the_bound", "y_half", "y_neg_zero", "y_pos_zero", "xz_neg_zero", "focus_low_end", "focus_high_end",
             "focus_high_end_dark", "scale_bounds", "negative_light"]
 REFUSED = ["tilted_sun", "sun_above", "long_sun", "nan_sun", "focus_zero", "focus_huge", "focus_negative", "focus_nan", "intensity_inf",
@@ -20,11 +18,7 @@ REFUSED = ["tilted_sun", "sun_above", "long_sun", "nan_sun", "focus_zero", "focu
 
 
 def build_and_run(tmp, extra):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Werror", *extra, SRC, "-o", exe])
+    exe = host_driver.build(tmp, "sky_sun", ["-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Wextra", "-Werror", *extra])
     out = subprocess.run([exe], capture_output=True, text=True, timeout=600, check=True).stdout
     rows = {}
     for line in out.splitlines():

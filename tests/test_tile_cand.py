@@ -17,31 +17,22 @@ of spheres the tile's sampled rays were really accepted by (a function of the sc
 holds) by at most 1.0 — and that bound lies far below the 16 bits of an all-ones mask, which the test checks too."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import host_driver
 from capfuzz_scenes import sphere_scene_file as scene_file   # (the driver's text form: shared with tests/test_tile_fuzz.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _cxx():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     d = tmp_path_factory.mktemp("tile_cand")
-    src = os.path.join(ROOT, "tests", "tile_cand_driver.cpp")
-    plain, san = str(d / "driver"), str(d / "driver_san")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
-    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", src, "-o", san])
+    plain = host_driver.build(d, "tile_cand", ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
+    san = host_driver.build(d, "tile_cand", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                         "-static-libasan", "-static-libubsan"], exe="driver_san")
     return {"plain": plain, "san": san, "dir": d}
 
 

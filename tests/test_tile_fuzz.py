@@ -16,14 +16,13 @@ asserted here, on the CPU, where the scenes are the same bits as there (the gene
   - every scene is within every cap, and every scene of scene_over_a_cap is over exactly the one it names."""
 import os
 import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
 import capfuzz_scenes as cs
-import test_gpu_tile_fuzz as gw   # (only its walks, which are plain data)
+import host_driver
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_SPHERES, MAX_MODELS, MAX_TRIS = 32, 4, 16   # RT_PRIMARY_MAX_* of ray-tracing_amd/csrc/rt_primary.h
@@ -31,15 +30,11 @@ MAX_SPHERES, MAX_MODELS, MAX_TRIS = 32, 4, 16   # RT_PRIMARY_MAX_* of ray-tracin
 
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
     d = tmp_path_factory.mktemp("tile_fuzz")
     out = {"dir": d}
     for name in ("tile_cand", "tile_tri"):
-        out[name] = str(d / (name + "_san"))
-        subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                               "-static-libasan", "-static-libubsan", os.path.join(ROOT, "tests", name + "_driver.cpp"), "-o", out[name]])
+        out[name] = host_driver.build(d, name, ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                                "-static-libasan", "-static-libubsan"], exe=name + "_san")
     return out
 
 
@@ -224,13 +219,13 @@ def test_every_listed_case_occurs(pkg):
 
 def test_the_walks_make_every_kind_of_step(pkg):
     """the walks of tests/test_gpu_tile_fuzz.py::test_one_context_through_key_changing_calls are plain data: checked here, without a device"""
-    kinds = [s["kind"] for seed in gw.WALK_SEEDS for s in gw._walk(pkg, seed)]
-    assert any(s["kind"] == "model" and s["u"][10] < 0.5 for seed in gw.WALK_SEEDS for s in gw._walk(pkg, seed)), "no mirrored transform"
+    kinds = [s["kind"] for seed in cs.WALK_SEEDS for s in cs._walk(pkg, seed)]
+    assert any(s["kind"] == "model" and s["u"][10] < 0.5 for seed in cs.WALK_SEEDS for s in cs._walk(pkg, seed)), "no mirrored transform"
     assert set(kinds) == {"sphere", "model", "camera", "fov", "diverge", "defocus", "resize_same_tiles", "resize", "upload_in_cap",
                           "upload_over_a_cap", "upload_in_cap_again", "reset"}
-    for seed in gw.WALK_SEEDS:
-        k = [s["kind"] for s in gw._walk(pkg, seed)]
-        assert len(k) == gw.STEPS and k.index("upload_over_a_cap") < k.index("upload_in_cap_again") and k.index("defocus") <= gw.STEPS - 3
+    for seed in cs.WALK_SEEDS:
+        k = [s["kind"] for s in cs._walk(pkg, seed)]
+        assert len(k) == cs.STEPS and k.index("upload_over_a_cap") < k.index("upload_in_cap_again") and k.index("defocus") <= cs.STEPS - 3
 
 
 def test_coverage_md_cites_test_functions_of_the_fuzz_files_that_exist():

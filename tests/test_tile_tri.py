@@ -21,31 +21,22 @@ holds) by at most 0.15 — the sphere masks sit 0.015 above theirs — and that 
 same run is the measurement the kernel path rests on: at least a quarter of the headline image's tiles must get an empty mask."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+import host_driver
 from capfuzz_scenes import triangle_scene_file as scene_file   # (the driver's text form: shared with tests/test_tile_fuzz.py)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _cxx():
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    return cxx
-
-
 @pytest.fixture(scope="module")
 def drivers(tmp_path_factory):
     d = tmp_path_factory.mktemp("tile_tri")
-    src = os.path.join(ROOT, "tests", "tile_tri_driver.cpp")
-    plain, san = str(d / "driver"), str(d / "driver_san")
-    subprocess.check_call([_cxx(), "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror", src, "-o", plain])
-    subprocess.check_call([_cxx(), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", src, "-o", san])
+    plain = host_driver.build(d, "tile_tri", ["-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
+    san = host_driver.build(d, "tile_tri", ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                                         "-static-libasan", "-static-libubsan"], exe="driver_san")
     return {"plain": plain, "san": san, "dir": d}
 
 

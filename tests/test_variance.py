@@ -6,15 +6,16 @@ pixel, every channel; small-integer cases are exact; and the moments image is a 
 import ctypes as C
 import os
 import re
-import shutil
 import struct
 import subprocess
 
 import numpy as np
 import pytest
 
+import host_driver
 import reproject_reference as rp
 import variance_reference as ref
+from gpu_support import assert_same_bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
@@ -113,12 +114,7 @@ def test_default_params_are_valid(pkg, api):
 # ---------------------------------------------------------------- 5. the math header, through the host driver, against NumPy
 @pytest.fixture(scope="module")
 def driver(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("c++")
-    if not cxx:
-        pytest.fail("no host C++ compiler")
-    exe = str(tmp_path_factory.mktemp("variance_math") / "driver")
-    subprocess.check_call([cxx, "-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror",
-                           os.path.join(ROOT, "tests", "variance_math_driver.cpp"), "-o", exe])
+    exe = host_driver.build(tmp_path_factory.mktemp("variance_math"), "variance_math", ["-std=c++17", "-O2", "-fno-fast-math", "-ffp-contract=off", "-Wall", "-Wextra", "-Werror"])
 
     class Driver:
         @staticmethod
@@ -136,15 +132,6 @@ def driver(tmp_path_factory):
             both = np.frombuffer(out, dtype=F).reshape(2, h, w, 4)
             return both[0], both[1]
     return Driver
-
-
-def assert_same_bits(got, want, what):
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
-    if len(bad):
-        y, x, k = bad[0]
-        raise AssertionError(f"{what}: {len(set(map(tuple, bad[:, :2])))} pixels differ; first at row {y}, column {x}, channel {k}: "
-                             f"got {got[y, x]}, want {want[y, x]}")
 
 
 def reference_denoise(orc, rgba, moments, aov, iterations, demodulate, p=PARAMS):

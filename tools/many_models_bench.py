@@ -5,9 +5,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import __graft_entry__ as g
 pkg = g.load_package(); api = pkg.load_library()
-import test_gpu_fuzz as tf
+import fuzz_scenes as tf
 for n in [int(a) for a in (sys.argv[1:] or ["100", "200", "333", "1000"])]:
-    sc = tf.crowded_scene(pkg, n, 3, seed=21)
+    sc = tf.crowded_overflow_scene(pkg, n, 3, seed=21)
     tr = api.create_tracer(0)
     mgr = sc.make_manager(tr, api, 960, 540); mgr.OnEnable(renderSeed=5)
     mgr.RenderFrames(2); tr.synchronize()

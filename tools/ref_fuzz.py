@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as g
 import test_ref_pin as T
-from test_gpu_fuzz import random_scene
+from fuzz_scenes import random_scene
 
 argv = [a for a in sys.argv[1:] if a != "--spheres"]
 with_spheres = "--spheres" in sys.argv[1:]

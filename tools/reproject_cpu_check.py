@@ -37,7 +37,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import __graft_entry__ as graft  # noqa: E402
 import motion_reference as mref  # noqa: E402
 import reproject_reference as ref  # noqa: E402
-import test_gpu_aov as ga  # noqa: E402
+import aov_support as ga  # noqa: E402
 
 SPEC = (3, {})
 OFFSET, TURN = np.array([0.25, 0.1, 0.15]), np.array([0.0, 2.0, 0.0])
