@@ -1,6 +1,6 @@
-/* rt_adaptive_launch.h — what rt_context.hip needs of rt_adaptive.hip: the calls that enqueue its kernels on a stream, and — without
+/* rt_adaptive_launch.h — what rt_post.hip and rt_context.hip need of rt_adaptive.hip: the calls that enqueue its kernels on a stream, and — without
  * HIP, so that a host test reaches them (tests/adaptive_math_driver.cpp) — the tile geometry and the check of a caller's tile list.
- * The entry points of include/rt_adaptive.h themselves live in rt_context.hip, with the context. */
+ * The entry points of include/rt_adaptive.h themselves live in rt_post.hip; the launch over a tile list (adaptive_launch) is rt_context.hip's. */
 #ifndef RT_ADAPTIVE_LAUNCH_H
 #define RT_ADAPTIVE_LAUNCH_H
 

@@ -1,5 +1,5 @@
-/* rt_denoise_launch.h — what rt_context.hip needs of rt_denoise.hip: the sizes of the filter's scratch and the call that enqueues
- * its kernels on a stream.  The entry points of include/rt_denoise.h themselves live in rt_context.hip, with the context. */
+/* rt_denoise_launch.h — what rt_post.hip needs of rt_denoise.hip: the sizes of the filter's scratch and the call that enqueues
+ * its kernels on a stream.  The entry points of include/rt_denoise.h themselves live in rt_post.hip, over the context (rt_context.h). */
 #ifndef RT_DENOISE_LAUNCH_H
 #define RT_DENOISE_LAUNCH_H
 

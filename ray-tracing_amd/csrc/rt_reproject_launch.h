@@ -1,5 +1,5 @@
-/* rt_reproject_launch.h — what rt_context.hip needs of rt_reproject.hip: the calls that enqueue its kernels on a stream.  The entry
- * points of include/rt_reproject.h and include/rt_motion.h themselves live in rt_context.hip, with the context. */
+/* rt_reproject_launch.h — what rt_post.hip needs of rt_reproject.hip: the calls that enqueue its kernels on a stream.  The entry
+ * points of include/rt_reproject.h and include/rt_motion.h themselves live in rt_post.hip, over the context (rt_context.h). */
 #ifndef RT_REPROJECT_LAUNCH_H
 #define RT_REPROJECT_LAUNCH_H
 

@@ -6,7 +6,7 @@
  * used.  The root filter boxes (make_filters) and the chunk hierarchy (make_chunks) are conservative stand-ins for whole models:
  * a box that is too small does not crash, it drops geometry.  tests/scene_prep_driver.cpp compiles this header into a
  * stand-alone program (tests/test_scene_prep.py runs it under the address and undefined-behaviour sanitizers).
- * rt_context.hip holds the device half (commit_scene, refresh_filters) and reports prepare_scene's message on its context.
+ * rt_scene_upload.hip holds the device half (commit_scene, refresh_filters) and reports prepare_scene's message on its context.
  */
 #ifndef RT_SCENE_PREP_H
 #define RT_SCENE_PREP_H

@@ -1,5 +1,5 @@
-/* rt_variance_launch.h — what rt_context.hip needs of rt_variance.hip: the sizes of the filter's scratch and the calls that enqueue
- * its kernels on a stream.  The entry points of include/rt_variance.h themselves live in rt_context.hip, with the context. */
+/* rt_variance_launch.h — what rt_post.hip needs of rt_variance.hip: the sizes of the filter's scratch and the calls that enqueue
+ * its kernels on a stream.  The entry points of include/rt_variance.h themselves live in rt_post.hip, over the context (rt_context.h). */
 #ifndef RT_VARIANCE_LAUNCH_H
 #define RT_VARIANCE_LAUNCH_H
 
